@@ -8,7 +8,7 @@ in HBM when the timed region starts: mosh construction + global hash<->barcode i
 pairs, 10 k barcodes, -B 24) — LRSIM and the yeast genomes are not available offline, so the seeded
 generator of hash10x_amd/tools/gen_fqb.c stands in.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...
 
 N > 1: one process per GPU; the workload is N times the yeast-scale set (weak scaling), its barcodes
@@ -16,9 +16,15 @@ sharded over the ranks and the global hash<->barcode index built by RCCL all-to-
 (csrc/shard.hip, DESIGN.md "Multi-GPU"). RANK / LOCAL_RANK / WORLD_SIZE / MASTER_* are read from the
 environment as torch.distributed.run sets them; torch itself is not imported (see rendezvous_unique_id).
 
-Prints ONE JSON line on rank 0 (contract in the task statement) with `roofline` for the dominant
-kernel and `cpu_baseline` (the reference binary from oracle/_ref, or the oracle port, timed on the
-host cores of this box on the same workload).
+A plain run generates the set, uploads it, warms up, times K steps and prints ONE JSON line on rank 0
+(`ms_per_step`, `value` in read-pairs/s, and `roofline` for the dominant kernel from the timers of those
+same steps). `--full` adds everything else: `cpu_baseline` (the reference binary from oracle/_ref, or
+the oracle port, timed on the host cores of this box on the same workload), the parity gates against
+the reference's digests, the side workloads, the 8-rank model and the whole record in bench_detail.json.
+
+`--dump-outputs DIR` writes what the last timed step left for a caller (the tables `--writeHash` writes:
+ClusterBlock and ClusterHash records, hashValue / hashDepth) to DIR/<name>.npy as float64, each table
+sampled to at most DUMP_ROWS rows by a fixed choice that depends only on its length (dump_outputs()).
 """
 import argparse
 import ctypes
@@ -836,6 +842,51 @@ def secondary_block(hash10x_amd, local_rank):
     return out
 
 
+DUMP_ROWS = 1 << 18          # rows per table in --dump-outputs: 15 float64 arrays of at most this many rows, 32 MB in all
+DUMP_RUN = 256               # a longer table is sampled in runs of this many consecutive rows
+DUMP_SEED = 0x48313058
+
+
+def dump_rows(n, cap=DUMP_ROWS, run=DUMP_RUN):
+    """(first, count) runs of the rows of an n-row table that --dump-outputs writes: all of them up to `cap` rows, else cap / run runs of `run` rows,
+    one at a seeded offset in each of cap / run equal strata of the table — the same rows for the same n in every run"""
+    if n <= cap:
+        return [(0, n)] if n else []
+    k = cap // run
+    stratum = n // k
+    offs = np.random.default_rng(DUMP_SEED).integers(0, stratum - run + 1, size=k)
+    return [(i * stratum + int(o), run) for i, o in enumerate(offs)]
+
+
+def dump_outputs(h, out_dir):
+    """--dump-outputs: the state the last step left, as a caller of the path receives it (the tables --writeHash writes), to out_dir/<name>.npy in float64.
+    Every field exactly: 32-bit and narrower fields as they are, the 64-bit hashValue as its high and low 32-bit halves; <table>_row = the rows written
+    (dump_rows), `sizes` = hashNumber, nBlocks, nClusHash. The heap-pointer word of ClusterBlock (always 0 here) is left out."""
+    os.makedirs(out_dir, exist_ok=True)
+    z = h.sizes()
+    block = np.dtype([("nRead", "<u4"), ("nHash", "<u4"), ("nSubCluster", "<u4"), ("clusterParent", "<u4"), ("clusHash", "<u8"), ("pointToMin", "<f8")])
+    clushash = np.dtype([("hash", "<u4"), ("read", "<u2"), ("subCluster", "u1"), ("flags", "u1")])
+    arrays = {"sizes": np.array([z["hashNumber"], z["nBlocks"], z["nClusHash"]], dtype=np.float64)}
+    # (name, [(h10x_export_slice table, record type)], rows): hashValue and hashDepth share their rows
+    for name, tables, n in (("blocks", [(3, block)], z["nBlocks"]), ("clushash", [(4, clushash)], z["nClusHash"]),
+                            ("hashes", [(1, np.dtype([("value", "<u8")])), (2, np.dtype([("depth", "<u4")]))], z["hashNumber"])):
+        runs = dump_rows(n)
+        arrays[name + "_row"] = np.concatenate([np.arange(a, a + c, dtype=np.float64) for a, c in runs]) if runs else np.zeros(0)
+        for table, dt in tables:
+            rec = np.concatenate([h.export_slice(table, a, c) for a, c in runs]).view(dt) if runs else np.zeros(0, dtype=dt)
+            for f in dt.names:
+                if f == "clusHash":
+                    continue
+                if rec[f].dtype == np.uint64:
+                    arrays["%s_%s_hi" % (name, f)] = (rec[f] >> np.uint64(32)).astype(np.float64)
+                    arrays["%s_%s_lo" % (name, f)] = (rec[f] & np.uint64(0xFFFFFFFF)).astype(np.float64)
+                else:
+                    arrays["%s_%s" % (name, f)] = rec[f].astype(np.float64)
+    for k, v in arrays.items():
+        np.save(os.path.join(out_dir, k + ".npy"), v)
+    return arrays
+
+
 _HUNG_THREADS = False        # set when virtual-rank threads were left behind in a collective: main() then leaves through os._exit
 HEADLINE_MAX_BYTES = 6000      # the driver keeps the LAST stdout line and parses it; round 5's 21 KB line did not fit its capture (VERDICT r5 item 1)
 
@@ -988,7 +1039,13 @@ def main():
                     "per-rank compute, every exchange's bytes and the modelled step instead of the benchmark line")
     ap.add_argument("--scaling", default=None, choices=["weak", "strong"], help="N > 1: weak = N x the workload (every rank generates its share of the N-fold set; "
                     "default for the yeast-scale set), strong = the SAME set on every N (default for genome3g-300M: the 3 Gb workload of BASELINE configs[3])")
+    ap.add_argument("--full", action="store_true", help="besides the headline: the CPU baseline, the parity gates against the reference's digests, per-rank exchange figures, the side "
+                    "workloads (1/10 and full configs[2], the 3 Gb set, the 8-rank model; --no-cpu-baseline / --no-secondary leave parts out) and the whole record in bench_detail.json")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write the state the last one left (sampled, float64) to DIR/<name>.npy; "
+                    "single-GPU unsharded runs")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
     if args.scaling is None:
         args.scaling = "strong" if WORKLOADS[args.workload].get("gen") == 2 else "weak"
 
@@ -1015,6 +1072,8 @@ def main():
         raise SystemExit("WORLD_SIZE %d != --gpus %d" % (world, args.gpus))
     if args.gpus > 1 and world == 1:
         raise SystemExit("--gpus %d needs torch.distributed.run (or any launcher that sets RANK/LOCAL_RANK/WORLD_SIZE/MASTER_*), one rank per GPU" % args.gpus)
+    if args.dump_outputs and (world > 1 or args.sharded):
+        raise SystemExit("--dump-outputs writes the state of one unsharded context: not with --gpus > 1 or --sharded")
 
     wl = dict(WORKLOADS[args.workload])
     comm = None
@@ -1172,7 +1231,9 @@ def main():
     }
     out["generate_seconds"] = round(gen_s, 2)
     out["build_id"] = hash10x_amd.build_id()
-    if world > 1 or args.sharded:
+    if args.dump_outputs:
+        out["dumped_outputs"] = sorted(dump_outputs(h, args.dump_outputs))
+    if args.full and (world > 1 or args.sharded):
         # what every kind of exchange moved and how long this rank waited in it, and the ranks' compute: max / sum over the ranks (so that a scaling curve can be read)
         try:
             fig = rank_figures(h)
@@ -1204,7 +1265,7 @@ def main():
                 out["parity_vs_reference_digest"] = "identical" if same else "DIFFERENT (reference %s, H %d, hashNumber %d)" % (exp["checksum"], exp["sum_nHash"], exp["hash_number"])
         except Exception as e:
             out["parity_vs_reference_digest"] = "check failed: " + str(e)[:200]
-    if rank == 0 and world == 1 and not args.sharded and wl.get("gen") == 2:
+    if args.full and rank == 0 and world == 1 and not args.sharded and wl.get("gen") == 2:
         # a generator-v2 workload on one GPU: the reference needs most of an hour for it — the parity gate is the digest of its .hash made in the
         # build container (manifest "strong_digests"), checked through the same composable checksum the N-rank runs use
         try:
@@ -1222,7 +1283,7 @@ def main():
                 out["parity_vs_reference_digest"] = "identical" if same else "DIFFERENT (reference %s, H %d, hashNumber %d)" % (exp["checksum"], exp["sum_nHash"], exp["hash_number"])
         except Exception as e:
             out["parity_vs_reference_digest"] = "check failed: " + str(e)[:200]
-    if rank == 0 and world == 1 and not args.sharded and not args.no_cpu_baseline and wl.get("gen") != 2:
+    if args.full and rank == 0 and world == 1 and not args.sharded and not args.no_cpu_baseline and wl.get("gen") != 2:
         with tempfile.TemporaryDirectory() as d:
             gp = os.path.join(d, "gpu.hash")
             h.write_hash(gp)
@@ -1242,7 +1303,7 @@ def main():
                 out["cpu_baseline"] = {"value": None, "unit": "read-pairs/s", "cores": 1, "kind": "error", "sample": str(e)[:300]}
     h.close()
     d_recs.free()
-    if rank == 0 and world == 1 and not args.no_secondary and args.workload == "yeast-like-2.5M":
+    if args.full and rank == 0 and world == 1 and not args.no_secondary and args.workload == "yeast-like-2.5M":
         try:
             out["secondary"] = secondary_block(hash10x_amd, local_rank)
         except Exception as e:                           # never lose the headline over the side block
@@ -1286,11 +1347,12 @@ def main():
                 sbk = step_bytes(blk["read_pairs"], blk["entries_H"], blk["distinct_U"], b, blk["roofline"]["algorithmic_bytes"])
                 out["roofline"]["step"][label] = {"frac": sbk / (blk["ms_per_step"] * 1e-3) / 1e9 / HBM_PEAK_GBS, "bytes": sbk, "ms": blk["ms_per_step"]}
     if rank == 0:
-        # the whole record first (file + an EARLIER line on stderr), then — last thing this process writes to stdout — the compact line the driver parses
-        write_detail(out)
-        sys.stderr.write("bench detail: " + json.dumps(out) + "\n")
-        sys.stderr.flush()
-        os.write(json_fd, (headline(out) + "\n").encode())
+        # --full: the whole record first (file + an EARLIER line on stderr), then — last thing this process writes to stdout — the compact line the driver parses
+        if args.full:
+            write_detail(out)
+            sys.stderr.write("bench detail: " + json.dumps(out) + "\n")
+            sys.stderr.flush()
+        os.write(json_fd, (headline(out, "bench_detail.json" if args.full else None) + "\n").encode())
     if comm is not None:
         comm.destroy()
     if _HUNG_THREADS:

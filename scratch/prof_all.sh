@@ -12,7 +12,7 @@ python3 -c "import json, os, sys; sys.path.insert(0, '.'); import hash10x_amd; j
 if [ -n "$ONLY_SQ" ]; then :                      # counters only (no bench, no kernel trace): quick look at one script
 elif [ -z "$SKIP_BENCH" ]; then
   if [ -z "$NO_FIRST_BENCH" ]; then                 # (NO_FIRST_BENCH=1: the bench line is taken afterwards, once the folds are in profiles/ — `traffic_stale: false`)
-    python3 bench.py --steps 10 --warmup 2 > $O/${TAG}_bench.json 2> $O/${TAG}_bench.err
+    python3 bench.py --full --steps 10 --warmup 2 > $O/${TAG}_bench.json 2> $O/${TAG}_bench.err
     echo "bench done"
   fi
   rocprofv3 --kernel-trace --stats --output-format csv -d $O/${TAG}_stats -o runc -- python3 bench.py --steps 5 --warmup 2 --no-cpu-baseline --no-secondary > $O/${TAG}_bench_under_rocprof.json 2> $O/${TAG}_rocprof.err

@@ -1188,7 +1188,7 @@ def test_bench_with_two_ranks_carries_a_parity_gate(workdir):
     ps = []
     for r in range(2):
         env = dict(os.environ, RANK=str(r), LOCAL_RANK=str(r), WORLD_SIZE="2", MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port))
-        ps.append(subprocess.Popen([sys.executable, os.path.join(orc.REPO, "bench.py"), "--gpus", "2", "--comm", "socket", "--steps", "1", "--warmup", "1"],
+        ps.append(subprocess.Popen([sys.executable, os.path.join(orc.REPO, "bench.py"), "--gpus", "2", "--comm", "socket", "--steps", "1", "--warmup", "1", "--full"],
                                    stdout=subprocess.PIPE, stderr=subprocess.PIPE, env=env, cwd=workdir.path))
     outs = [p.communicate(timeout=600) for p in ps]
     for p, (so, se) in zip(ps, outs):
@@ -1211,7 +1211,7 @@ def test_bench_strong_scaling_on_one_fixed_set(workdir, world):
     for r in range(world):
         env = dict(os.environ, RANK=str(r), LOCAL_RANK=str(r), WORLD_SIZE=str(world), MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port))
         ps.append(subprocess.Popen([sys.executable, os.path.join(orc.REPO, "bench.py"), "--workload", "genome3g-tenth-30M", "--gpus", str(world), "--comm", "socket", "--steps", "1", "--warmup", "1",
-                                    "--no-secondary"], stdout=subprocess.PIPE, stderr=subprocess.PIPE, env=env, cwd=workdir.path))
+                                    "--no-secondary", "--full"], stdout=subprocess.PIPE, stderr=subprocess.PIPE, env=env, cwd=workdir.path))
     outs = [p.communicate(timeout=900) for p in ps]
     for p, (so, se) in zip(ps, outs):
         assert p.returncode == 0, se.decode()[-1500:]
