@@ -149,6 +149,10 @@ def load_native():
     hip.h10x_last_error.restype = cs
     hip.h10x_last_error.argtypes = [vp]
     hip.h10x_export.argtypes = [vp, vp, vp, vp, vp, vp]
+    hip.h10x_neighbours.argtypes = [vp, ctypes.c_uint32, vp, vp, vp, cu64, vp]
+    hip.h10x_neighbour_max.argtypes = [vp, vp, ctypes.c_uint32, vp, vp]
+    hip.h10x_neighbour_hist.argtypes = [vp, vp, ctypes.c_uint32, vp, vp]
+    hip.h10x_neighbour_stats.argtypes = [vp, vp, ci]
     if hip.h10x_abi_version() != ABI_VERSION:
         raise RuntimeError("libh10x_hip.so speaks ABI %d, hash10x_amd/__init__.py was written for %d (include/h10x.h H10X_ABI_VERSION): rebuild with "
                            "`python -c 'import __graft_entry__ as g; g.build()'`" % (hip.h10x_abi_version(), ABI_VERSION))
@@ -613,3 +617,43 @@ class Hash10x:
         if self._hip.h10x_export(self._ctx(), None, None, d.ctypes.data, None, None):
             raise Hash10xError(self._hip.h10x_last_error(self._ctx()).decode())
         return d
+
+    # ---- neighbour census (h10x_neighbours / _max / _hist: hashNeighbours / countHashNeighbours, hash10x.c:541-586) ----
+    def neighbours(self, x):
+        """N(x) ascending in h: (hash, count = shared blocks, firstCode = lowest barcode of h) as three uint32 arrays."""
+        n = ctypes.c_uint64(0)
+        self._chk_ctx(self._hip.h10x_neighbours(self._ctx(), int(x), None, None, None, 0, ctypes.byref(n)))
+        m = n.value
+        h, c, f = (np.zeros(max(m, 1), dtype=np.uint32) for _ in range(3))
+        self._chk_ctx(self._hip.h10x_neighbours(self._ctx(), int(x), h.ctypes.data, c.ctypes.data, f.ctypes.data, m, ctypes.byref(n)))
+        return h[:m], c[:m], f[:m]
+
+    def neighbour_max(self, xs):
+        """per query: (maxKey = max of (count mod 2^16) << 32 | h, |N(x)|) as uint64 / uint32 arrays."""
+        q = np.ascontiguousarray(xs, dtype=np.uint32).reshape(-1)
+        mk = np.zeros(max(q.size, 1), dtype=np.uint64); nn = np.zeros(max(q.size, 1), dtype=np.uint32)
+        self._chk_ctx(self._hip.h10x_neighbour_max(self._ctx(), q.ctypes.data, q.size, mk.ctypes.data, nn.ctypes.data))
+        return mk[:q.size], nn[:q.size]
+
+    def neighbour_hist(self, xs, depth=None):
+        """per query the histogram H_x[0 .. depth(x)] of shared-block counts: a list of uint32 arrays."""
+        q = np.ascontiguousarray(xs, dtype=np.uint32).reshape(-1)
+        d = self.export_depth() if depth is None else depth
+        off = np.zeros(q.size + 1, dtype=np.uint64)
+        off[1:] = np.cumsum(d[q].astype(np.uint64) + 1)
+        hist = np.zeros(max(int(off[-1]), 1), dtype=np.uint32)
+        self._chk_ctx(self._hip.h10x_neighbour_hist(self._ctx(), q.ctypes.data, q.size, off.ctypes.data, hist.ctypes.data))
+        return [hist[int(off[i]):int(off[i + 1])] for i in range(q.size)]
+
+    def neighbour_stats(self, reset=True):
+        """census work since the last reset: records gathered, in-range keys sorted, batches, windows"""
+        v = np.zeros(4, dtype=np.uint64)
+        self._chk_ctx(self._hip.h10x_neighbour_stats(self._ctx(), v.ctypes.data, 1 if reset else 0))
+        return dict(zip(("gathered", "sorted", "batches", "windows"), (int(a) for a in v)))
+
+    def export_within(self):
+        """hashWithinRange[0 .. hashNumber) as uint8 (fails before --hashDepthRange)."""
+        z = self.sizes()
+        w = np.zeros(max(z["hashNumber"], 1), dtype=np.uint8)
+        self._chk_ctx(self._hip.h10x_export_slice(self._ctx(), 7, 0, z["hashNumber"], w.ctypes.data))
+        return w[:z["hashNumber"]]

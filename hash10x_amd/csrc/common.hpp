@@ -242,6 +242,8 @@ struct Ctx {
   int64_t optOwnerCut = 0;    // sharded index build, where the hash owners' value ranges are cut: 0 = at the quantiles of the canonical-hash density 2 (1 - x) (equal shares), 1 = equal value ranges (round 5: owner 0 of 8 holds 23.4 %)
   int64_t optDeltaLists = -1; // in-range barcode lists travel delta-coded between ranks: -1 = where bytes are dear (more than one rank on the host-staged TCP backend; not over xGMI: DESIGN 5), 0 never, 1 always (tests)
   int64_t optRowsFakeBase = 0; // testing knob: list offsets start at this many entries (multiple of 2^rowShift) in front of the real array: 64-bit offsets on small inputs
+  int64_t optNbBudget = 0;    // neighbour census: gathered ClusterHash records per batch (0 = default, stage_f.hip); small values force the batching and the hash-index windows
+  u64 nbStats[4] = {0, 0, 0, 0};   // neighbour census since the last reset: records gathered, in-range keys sorted, batches, windows (h10x_neighbour_stats)
   // streaming ingest (h10x_ingest_fqb): the record image grows on the device as the chunks arrive
   DevBuf<u32> ingestBuf; u64 ingestRecords = 0, ingestCap = 0; bool ingestAsync = false;   // ingestAsync: chunks came through h10x_ingest_fqb_async (the closing call then checks the count)
   static constexpr int INGEST_SLOTS = 8; hipEvent_t ingestEv[INGEST_SLOTS] = {};   // h10x_ingest_fqb_async: one event per caller's buffer
@@ -402,7 +404,7 @@ int stageA_runStarts(Ctx *c, const u32 *dRec, u64 nRec, std::vector<u64> &starts
 // start a run but not a block (an all-A barcode's run ended exactly at a chunk boundary: hash10x.c:212)
 int replayChunks(const std::vector<u64> &starts, const std::vector<u32> &zeroRuns, u64 chunk, std::vector<u64> &merges, bool eofPass);   // stable sort of .fqb records by their first 4 bytes
 int stageB_run(Ctx *c, DevBuf<u64> &entHash, DevBuf<u32> &entCode, DevBuf<u32> &entRead);
-void warm_prim(hipStream_t), warm_stageA(hipStream_t), warm_stageB(hipStream_t), warm_stageC(hipStream_t), warm_stageD(hipStream_t), warm_stageE(hipStream_t), warm_shard(hipStream_t);   // h10x_warm
+void warm_prim(hipStream_t), warm_stageA(hipStream_t), warm_stageB(hipStream_t), warm_stageC(hipStream_t), warm_stageD(hipStream_t), warm_stageE(hipStream_t), warm_stageF(hipStream_t), warm_shard(hipStream_t);   // h10x_warm
 int stageB_buildCSR(Ctx *c);                   // rows/rowStart from clusHash + hashDepth (fillHashTable)
 int stageB_finishClusHash(Ctx *c, DevBuf<u64> &key);   // key[e] = index << 32 | read16 in block order -> clusHash sorted per block
 int stageB_finishClusHashFromReplies(Ctx *c, const u32 *replyIdx, const u32 *replyPos, const u32 *entRead);   // sharded: entry e's index is replyIdx[replyPos[e]]
@@ -430,6 +432,9 @@ int stageE_histogram(Ctx *c, int which, u64 first, u64 count, u32 bins, u64 *his
 int stageE_clusterReport(Ctx *c, u32 firstBlock, u32 nBlk, h10x_block_rep *hostB, h10x_cluster_rep *hostC, u64 clusterCap, u64 *nClusters);
 int stageE_cribSummary(Ctx *c, u64 *counts12, u32 *hostSeenBase, u32 *hostSeenCluster);
 int stageE_cribWords(Ctx *c, u64 first, u64 count, u32 *hostOut);
+int stageF_neighbours(Ctx *c, u32 x, u32 *hash, u32 *count, u32 *first, u64 cap, u64 *n);
+int stageF_neighbourMax(Ctx *c, const u32 *xs, u32 nq, u64 *maxKey, u32 *nNb);
+int stageF_neighbourHist(Ctx *c, const u32 *xs, u32 nq, const u64 *offsets, u32 *hist);
 int shard_allreduceU64(Ctx *c, u64 *v, u32 n, int op);
 int shard_gatherBytes(Ctx *c, const void *send, u64 nbytes, void *recv, u64 cap, u64 *counts);
 int shard_exchangeRows(Ctx *c);

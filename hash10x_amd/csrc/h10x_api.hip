@@ -397,7 +397,7 @@ int h10x_warm(int device) {
   if (hipSetDevice(device) != hipSuccess) return -1;
   hipStream_t st = nullptr;
   if (hipStreamCreateWithFlags(&st, hipStreamNonBlocking) != hipSuccess) return -1;
-  warm_stageA(st); warm_prim(st); warm_stageB(st); warm_stageC(st); warm_stageD(st); warm_stageE(st); warm_shard(st);   // in the order a run needs them
+  warm_stageA(st); warm_prim(st); warm_stageB(st); warm_stageC(st); warm_stageD(st); warm_stageE(st); warm_stageF(st); warm_shard(st);   // in the order a run needs them
   const hipError_t e = hipStreamSynchronize(st);
   (void)hipStreamDestroy(st);
   return e == hipSuccess && hipGetLastError() == hipSuccess ? 0 : -1;
@@ -500,6 +500,23 @@ int h10x_crib_summary(h10x_ctx *h, uint64_t counts[12], uint32_t *seenBase, uint
 
 int h10x_crib_words(h10x_ctx *h, uint64_t first, uint64_t count, uint32_t *words) {
   if (!h || (count && !words)) return -1; H10X_TRY(enter(h->c)); return stageE_cribWords(&h->c, first, count, words);
+}
+
+// ---- neighbour census (stage_f.hip): hashNeighbours / countHashNeighbours, hash10x.c:541-586 ----
+int h10x_neighbours(h10x_ctx *h, uint32_t x, uint32_t *hash, uint32_t *count, uint32_t *firstCode, uint64_t cap, uint64_t *n) {
+  if (!h || !n) return -1; H10X_TRY(enter(h->c)); return stageF_neighbours(&h->c, x, hash, count, firstCode, cap, (u64 *)n);
+}
+int h10x_neighbour_max(h10x_ctx *h, const uint32_t *xs, uint32_t nq, uint64_t *maxKey, uint32_t *nNeighbours) {
+  if (!h || (nq && (!xs || !maxKey || !nNeighbours))) return -1; H10X_TRY(enter(h->c)); return stageF_neighbourMax(&h->c, xs, nq, (u64 *)maxKey, nNeighbours);
+}
+int h10x_neighbour_hist(h10x_ctx *h, const uint32_t *xs, uint32_t nq, const uint64_t *offsets, uint32_t *hist) {
+  if (!h || (nq && (!xs || !offsets || !hist))) return -1; H10X_TRY(enter(h->c)); return stageF_neighbourHist(&h->c, xs, nq, (const u64 *)offsets, hist);
+}
+int h10x_neighbour_stats(h10x_ctx *h, uint64_t out[4], int reset) {
+  if (!h || !out) return -1;
+  for (int i = 0; i < 4; ++i) out[i] = h->c.nbStats[i];
+  if (reset) for (int i = 0; i < 4; ++i) h->c.nbStats[i] = 0;
+  return 0;
 }
 
 int h10x_timing_enable(h10x_ctx *h, int on) { if (!h) return -1; h->c.timing = on != 0; return 0; }
@@ -650,6 +667,7 @@ int h10x_export_slice(h10x_ctx *h, int table, uint64_t first, uint64_t count, vo
     case H10X_TABLE_BLOCKS:    src = c.blocks.p; eb = sizeof(h10x_block); limit = c.nBlocks; break;
     case H10X_TABLE_CLUSHASH:  src = c.clusHash.p; eb = sizeof(h10x_clushash); limit = c.nEntries; break;
     case H10X_TABLE_CLUSTER_RAW: if (!c.clusterRaw.p || c.clusterRaw.n != 2 * (size_t)c.nBlocks) return c.fail("no --cluster has run on these blocks"); src = c.clusterRaw.p; eb = 8; limit = c.nBlocks; break;
+    case H10X_TABLE_WITHIN:    if (!c.haveRange) return c.fail("no hashDepthRange set"); src = c.within.p; eb = 1; limit = c.hashNumber; break;
     case H10X_TABLE_NGOOD:     if (!c.haveGood) return c.fail("!! you must set hashDepthRange before clusterReport"); src = c.nGood.p; eb = 4; limit = c.nBlocks; break;
     default: return c.fail("h10x_export_slice: unknown table %d", table);
   }
@@ -689,6 +707,7 @@ int h10x_set_option(h10x_ctx *h, const char *name, int64_t value) {
   if (!strcmp(name, "shard_owner_cut")) { if (value < 0 || value > 1) return h->c.fail("shard_owner_cut must be 0 or 1"); h->c.optOwnerCut = value; return 0; }
   if (!strcmp(name, "shard_delta_lists")) { if (value < -1 || value > 1) return h->c.fail("shard_delta_lists must be -1, 0 or 1"); h->c.optDeltaLists = value; return 0; }
   if (!strcmp(name, "shard_rows_fake_base")) { if (value < 0) return h->c.fail("shard_rows_fake_base must be >= 0"); h->c.optRowsFakeBase = value; return 0; }
+  if (!strcmp(name, "neighbour_budget")) { if (value < 0) return h->c.fail("neighbour_budget must be >= 0"); h->c.optNbBudget = value; return 0; }
   return h->c.fail("unknown option %s", name);
 }
 

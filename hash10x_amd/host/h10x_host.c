@@ -1234,3 +1234,234 @@ done:
   fclose(f); if (g) fclose(g); free(in); free(out);
   return rc;
 }
+
+/* ---- the neighbour commands: --hashInfo, --hashExplore, --doubleShared, --errorFix, --shareScan (hash10x.c:512-521, 541-718) ----
+   The census (which hashes share blocks with a query, and in how many) runs on the device: h10x_neighbours / _max / _hist. The host
+   holds hashDepth[], hashWithinRange[] and the crib labels for the texts and does the reference's arithmetic on the results. */
+typedef struct { uint32_t hashNumber; uint32_t *depth; uint8_t *within; int haveCrib; } Nb;
+static void nb_close(Nb *nb) { free(nb->depth); free(nb->within); nb->depth = 0; nb->within = 0; }
+/* 0 ready, 1 no --hashDepthRange yet (the caller prints the reference's message), -1 failure */
+static int nb_open(h10x_session *s, Nb *nb) {
+  memset(nb, 0, sizeof *nb);
+  if (!s->ctx) return 1;                                          /* nothing loaded: no range either (the reference tests hashWithinRange first) */
+  h10x_shard_info_t z; if (h10x_shard_info(s->ctx, &z)) return fail_ctx(s);
+  if (z.nranks > 1) return fail(s, "the neighbour commands do not run on a sharded session (--gpus > 1)");
+  nb->hashNumber = z.hashNumber;
+  uint32_t histDim = 0; nb->haveCrib = h10x_crib_sizes(s->ctx, &histDim, 0) == 0;
+  if (nb->haveCrib && crib_fetch(s, z.hashNumber)) return -1;
+  nb->depth = (uint32_t *)malloc((size_t)z.hashNumber * 4 + 4); nb->within = (uint8_t *)malloc((size_t)z.hashNumber + 1);
+  if (!nb->depth || !nb->within) { nb_close(nb); return fail(s, "out of host memory for the neighbour commands"); }
+  if (h10x_export_slice(s->ctx, H10X_TABLE_HASHDEPTH, 0, z.hashNumber, nb->depth)) { nb_close(nb); return fail_ctx(s); }
+  if (h10x_export_slice(s->ctx, H10X_TABLE_WITHIN, 0, z.hashNumber, nb->within)) { nb_close(nb); return 1; }
+  return 0;
+}
+/* cribText (hash10x.c:512-521) */
+static const char *nb_text(const h10x_session *s, const Nb *nb, uint32_t x, char *buf) {
+  char *p = buf; p += sprintf(p, "%d", (int)x);
+  if (nb->haveCrib) {
+    const int ty = s->cribType[x];
+    p += sprintf(p, ":%s", cribTypeName[ty]);
+    if (ty > 0 && ty < 4) p += sprintf(p, "_%d.%d", (int)s->cribChr[x], (int)s->cribPos[x]);
+  }
+  sprintf(p, "-%d", (int)nb->depth[x]);
+  return buf;
+}
+/* hashNeighbours (hash10x.c:541-567): (h, read = count mod 2^16, first code) ascending in h; N(x) empty = one entry (0, 1) */
+typedef struct { uint32_t hash; uint16_t read; uint32_t code; } NbPair;
+static int nb_list(h10x_session *s, uint32_t x, NbPair **out, uint32_t *n) {
+  uint64_t m = 0;
+  if (h10x_neighbours(s->ctx, x, 0, 0, 0, 0, &m)) return fail_ctx(s);
+  uint32_t *h = (uint32_t *)malloc((m + 1) * 4), *c = (uint32_t *)malloc((m + 1) * 4), *f = (uint32_t *)malloc((m + 1) * 4);
+  NbPair *p = (NbPair *)calloc(m + 1, sizeof *p);
+  int rc = 0; uint64_t m2 = 0;
+  if (!h || !c || !f || !p) rc = fail(s, "out of host memory for the neighbour list");
+  else if (h10x_neighbours(s->ctx, x, h, c, f, m, &m2)) rc = fail_ctx(s);
+  else if (m2 != m) rc = fail(s, "neighbour list of %u changed size", x);
+  if (!rc) {
+    for (uint64_t i = 0; i < m; ++i) { p[i].hash = h[i]; p[i].read = (uint16_t)c[i]; p[i].code = f[i]; }
+    if (!m) { p[0].hash = 0; p[0].read = 1; p[0].code = 0; m = 1; }   /* arrp(ch, 0, ...) of an empty calloc'd array (array.c:63) */
+    *out = p; *n = (uint32_t)m;
+  } else free(p);
+  free(h); free(c); free(f);
+  return rc;
+}
+static int nb_by_read(const void *a, const void *b) {          /* compareClusterRead under glibc's stable merge sort: ties keep ascending h */
+  const NbPair *x = (const NbPair *)a, *y = (const NbPair *)b;
+  if (x->read != y->read) return x->read < y->read ? -1 : 1;
+  return x->hash < y->hash ? -1 : x->hash > y->hash;
+}
+
+int h10x_session_hashInfo(h10x_session *s, int hMin, int hMax, int skip, FILE *out, FILE *err) {
+  Nb nb; const int o = nb_open(s, &nb); if (o < 0) return -1;
+  if (o == 1) { fprintf(err, "hashInfo called without hashDepthRange\n"); nb_close(&nb); return 0; }
+  int rc = 0;
+  if (hMin < hMax && (hMin < 0 || (uint32_t)hMax > nb.hashNumber)) { rc = fail(s, "!! hashInfo range %d to %d outside 0 to %u", hMin, hMax, nb.hashNumber); goto done; }
+  if (hMin < hMax && skip <= 0) { rc = fail(s, "!! hashInfo skip %d must be positive", skip); goto done; }
+  enum { CHUNK = 1 << 20 };
+  uint32_t *xs = (uint32_t *)malloc((size_t)CHUNK * 4), *nn = (uint32_t *)malloc((size_t)CHUNK * 4); uint64_t *mk = (uint64_t *)malloc((size_t)CHUNK * 8);
+  if (!xs || !nn || !mk) { rc = fail(s, "out of host memory for hashInfo"); goto free3; }
+  char t1[64], t2[64];
+  for (int64_t x0 = hMin; x0 < hMax;) {                           /* a chunk of the walk: census of its in-range hashes, then its lines */
+    int64_t x1 = x0; uint32_t nq = 0;
+    for (; x1 < hMax && nq < CHUNK; x1 += skip) if (nb.within[x1] && nb.depth[x1]) xs[nq++] = (uint32_t)x1;
+    if (nq && h10x_neighbour_max(s->ctx, xs, nq, mk, nn)) { rc = fail_ctx(s); break; }
+    uint32_t q = 0;
+    for (int64_t x = x0; x < x1; x += skip) {
+      fprintf(out, "HASH_INFO  %s", nb_text(s, &nb, (uint32_t)x, t1));
+      if (nb.within[x] && nb.depth[x]) {                          /* depth 0 in range (only with --hashDepthRange 0 ...): no census, as if out of range */
+        const uint32_t h = nn[q] ? (uint32_t)mk[q] : 0, c = nn[q] ? (uint32_t)(mk[q] >> 32) : 1;
+        fprintf(out, " max share %d with %s", (int)c, nb_text(s, &nb, h, t2));
+        ++q;
+      }
+      fputc('\n', out);
+    }
+    x0 = x1;
+  }
+free3:
+  free(xs); free(nn); free(mk);
+done:
+  nb_close(&nb);
+  return rc;
+}
+
+int h10x_session_hashExplore(h10x_session *s, int x, FILE *out, FILE *err) {
+  Nb nb; const int o = nb_open(s, &nb); if (o < 0) return -1;
+  if (o == 1) { fprintf(err, "exploreHash called without hashDepthRange\n"); nb_close(&nb); return 0; }
+  int rc = 0; NbPair *p = 0; uint32_t n = 0; char t[64];
+  if (x < 0 || (uint32_t)x >= nb.hashNumber) { rc = fail(s, "!! hashExplore hash %d outside 0 to %u", x, nb.hashNumber); goto done; }
+  if (!nb.depth[x]) goto done;                                    /* hashNeighbours returns 0: nothing printed */
+  if ((rc = nb_list(s, (uint32_t)x, &p, &n))) goto done;
+  fprintf(out, "  %d hashes sharing codes with %s\n", (int)n, nb_text(s, &nb, (uint32_t)x, t));
+  qsort(p, n, sizeof *p, nb_by_read);
+  { int count = 1, k = 0;                                         /* hash10x.c:596-605 */
+    for (uint32_t i = 0; i <= n; ++i)
+      if (i == n || p[i].read != count) {
+        fprintf(out, "    %d sharing %d codes", k, count);
+        if (k > 7) { fprintf(out, "  ..."); k = 7; }
+        while (k) { fprintf(out, " %s", nb_text(s, &nb, p[i - k].hash, t)); --k; }
+        fputc('\n', out);
+        if (i < n) count = p[i].read;
+        k = 1;
+      } else ++k;
+  }
+done:
+  free(p); nb_close(&nb);
+  return rc;
+}
+
+int h10x_session_doubleShared(h10x_session *s, int x1, int x2, FILE *out, FILE *err) {
+  Nb nb; const int o = nb_open(s, &nb); if (o < 0) return -1;
+  if (o == 1) { fprintf(err, "doubleShared called without hashDepthRange\n"); nb_close(&nb); return 0; }
+  int rc = 0; NbPair *a = 0, *b = 0; uint32_t na = 0, nbb = 0; char t[64];
+  if (x1 < 0 || x2 < 0 || (uint32_t)x1 >= nb.hashNumber || (uint32_t)x2 >= nb.hashNumber) { rc = fail(s, "!! doubleShared hashes %d %d outside 0 to %u", x1, x2, nb.hashNumber); goto done; }
+  if (!nb.depth[x1] || !nb.depth[x2]) goto done;
+  if ((rc = nb_list(s, (uint32_t)x1, &a, &na)) || (rc = nb_list(s, (uint32_t)x2, &b, &nbb))) goto done;
+  for (uint32_t i1 = 0, i2 = 0; i1 < na && i2 < nbb;)            /* hash10x.c:618-626 */
+    if (a[i1].hash == b[i2].hash && a[i1].read > 2 && b[i2].read > 2) {
+      fprintf(out, "  hash %-8d code %-6d n1 %-3d n2 %-3d crib %s\n", (int)a[i1].hash, (int)a[i1].code, a[i1].read, b[i2].read, nb_text(s, &nb, a[i1].hash, t));
+      ++i1; ++i2;
+    } else if (a[i1].hash < b[i2].hash) ++i1;
+    else ++i2;
+done:
+  free(a); free(b); nb_close(&nb);
+  return rc;
+}
+
+/* countHashNeighbours' array after errorFix / shareScan's post-processing (hash10x.c:662-663, 704-705): the top bin decremented and trailing
+   zero bins dropped; returns the new arrayMax. An empty census (no in-range neighbour) has no bin to decrement: it stays empty. */
+static uint32_t nb_trim(uint32_t *h, uint32_t dim) {
+  uint32_t m = dim; while (m && !h[m - 1]) --m;
+  if (!m) return 0;
+  --h[m - 1];
+  while (m && !h[m - 1]) --m;
+  return m;
+}
+/* per-query histogram regions of depth + 1 bins for xs[0 .. nq), census on the device */
+static int nb_hists(h10x_session *s, const Nb *nb, const uint32_t *xs, uint32_t nq, uint64_t **offOut, uint32_t **histOut) {
+  uint64_t *off = (uint64_t *)malloc(((size_t)nq + 1) * 8); if (!off) return fail(s, "out of host memory for the neighbour histograms");
+  off[0] = 0; for (uint32_t q = 0; q < nq; ++q) off[q + 1] = off[q] + nb->depth[xs[q]] + 1;
+  uint32_t *hist = (uint32_t *)malloc((size_t)off[nq] * 4 + 4);
+  if (!hist) { free(off); return fail(s, "out of host memory for the neighbour histograms"); }
+  if (nq && h10x_neighbour_hist(s->ctx, xs, nq, off, hist)) { free(off); free(hist); return fail_ctx(s); }
+  *offOut = off; *histOut = hist; return 0;
+}
+
+int h10x_session_errorFix(h10x_session *s, int hashMin, int hashMax, FILE *out, FILE *err) {
+  { uint32_t histDim = 0; if (!s->ctx || h10x_crib_sizes(s->ctx, &histDim, 0)) return fail(s, "need to set crib"); }   /* die ("need to set crib"), hash10x.c:653 */
+  Nb nb; const int o = nb_open(s, &nb); if (o < 0) return -1;
+  if (o == 1) { fprintf(err, "errorFix called without hashDepthRange\n"); nb_close(&nb); return 0; }
+  int rc = 0;
+  if (hashMin < hashMax && (hashMin < 0 || (uint32_t)hashMax > nb.hashNumber)) { nb_close(&nb); return fail(s, "!! errorFix range %d to %d outside 0 to %u", hashMin, hashMax, nb.hashNumber); }
+  int low[5] = {0}, nt[5] = {0}; double mn[5], mx[5], sum[5]; char t[64];
+  for (int i = 0; i < 5; ++i) { mn[i] = 1.0; mx[i] = 0.0; sum[i] = 0.0; }
+  enum { CHUNK = 1 << 18 }; const uint64_t BINS = 1ull << 26;    /* queries and histogram bins per census call */
+  uint32_t *xs = (uint32_t *)malloc((size_t)CHUNK * 4);
+  if (!xs) { nb_close(&nb); return fail(s, "out of host memory for errorFix"); }
+  for (int64_t x0 = hashMin; x0 < hashMax;) {
+    int64_t x1 = x0; uint32_t nq = 0; uint64_t bins = 0;
+    for (; x1 < hashMax && nq < CHUNK && bins < BINS; ++x1) if (nb.depth[x1] >= 5) { xs[nq++] = (uint32_t)x1; bins += nb.depth[x1] + 1; }
+    uint64_t *off = 0; uint32_t *hist = 0;
+    if ((rc = nb_hists(s, &nb, xs, nq, &off, &hist))) break;
+    uint32_t q = 0;
+    for (int64_t x = x0; x < x1; ++x) {                           /* hash10x.c:658-683, in x order */
+      const int type = s->cribType[x]; const int xCount = (int)nb.depth[x];
+      if (xCount < 5) { ++low[type]; continue; }
+      uint32_t *a = hist + off[q++];
+      const uint32_t m = nb_trim(a, (uint32_t)xCount + 1);
+      if (m > 4) {
+        unsigned n = 0; uint64_t sumSq = 0; uint32_t i;
+        for (i = 0; i < 4; ++i) n += a[i];
+        for (; i < m; ++i) { sumSq += (uint64_t)(int64_t)(int32_t)(a[i] * (i - 3) * (i - 3)); n += a[i]; }   /* int products, summed into a U64 */
+        const double score = sumSq / ((double)(int)n * (xCount - 3));
+        ++nt[type]; sum[type] += score;
+        if (score < mn[type]) mn[type] = score;
+        if (score > mx[type]) mx[type] = score;
+        if ((type == 0 && score > 0.00005) || (type != 0 && score < 0.00005)) {
+          fprintf(out, "  %s count %d max %d score %.6f ", nb_text(s, &nb, (uint32_t)x, t), xCount, (int)m - 1, score);
+          for (i = 5; i < m; ++i) fprintf(out, " %d", (int)a[i]);
+          fputc('\n', out);
+        }
+      } else ++low[type];                                         /* (an empty census lands here too: DESIGN.md) */
+    }
+    free(off); free(hist);
+    x0 = x1;
+  }
+  free(xs);
+  if (!rc)
+    for (int i = 0; i < 5; ++i)
+      fprintf(out, "  %s low %d n %d min %.6f av %.6f max %.6f\n", cribTypeName[i], low[i], nt[i], mn[i], sum[i] / (nt[i] ? nt[i] : 1), mx[i]);
+  nb_close(&nb);
+  return rc;
+}
+
+int h10x_session_shareScan(h10x_session *s, int countMin, int countMax, FILE *out, FILE *err) {
+  if (!s->ctx) return 0;                                          /* nothing loaded: hashNumber 0, the reference's walk is empty */
+  Nb nb; const int o = nb_open(s, &nb); if (o < 0) return -1;
+  if (o == 1) { fprintf(err, "shareScan called without hashDepthRange\n"); nb_close(&nb); return 0; }
+  if (countMin < 1 || countMax <= countMin) { nb_close(&nb); return fail(s, "!! shareScan needs 0 < countMin < countMax, not %d %d", countMin, countMax); }
+  const int nBins = countMax - countMin; int rc = 0; char t[64];
+  int *nBin = (int *)calloc((size_t)nBins, sizeof(int)); uint32_t *xBin = (uint32_t *)malloc((size_t)nBins * 10 * 4), *xs = (uint32_t *)malloc((size_t)nBins * 10 * 4);
+  uint64_t *off = 0; uint32_t *hist = 0; uint32_t *slot = (uint32_t *)malloc((size_t)nBins * 10 * 4);
+  if (!nBin || !xBin || !xs || !slot) { rc = fail(s, "out of host memory for shareScan"); goto done; }
+  uint32_t nq = 0; int nTot = 0;
+  for (uint64_t x = (uint64_t)countMax; x < nb.hashNumber; x += 100) {   /* hash10x.c:697-708: the sample depends on the depths alone */
+    const int xCount = (int)nb.depth[x];
+    if (xCount < countMin || xCount >= countMax) continue;
+    const int bin = xCount - countMin;
+    if (nBin[bin] == 10) continue;
+    xBin[10 * bin + nBin[bin]] = (uint32_t)x; slot[10 * bin + nBin[bin]] = nq; xs[nq++] = (uint32_t)x; ++nBin[bin];
+    if (++nTot == 10 * nBins) break;
+  }
+  if ((rc = nb_hists(s, &nb, xs, nq, &off, &hist))) goto done;
+  for (int i = 0; i < nBins; ++i)
+    for (int j = 0; j < nBin[i]; ++j) {
+      const uint32_t q = slot[10 * i + j]; uint32_t *a = hist + off[q];
+      const uint32_t m = nb_trim(a, nb.depth[xs[q]] + 1);
+      fprintf(out, "SHARE_SCAN %3d %24s ", i + countMin, nb_text(s, &nb, xBin[10 * i + j], t));
+      for (uint32_t k = 1; k < m; ++k) fprintf(out, " %d", (int)a[k]);
+      fputc('\n', out);
+    }
+done:
+  free(nBin); free(xBin); free(xs); free(slot); free(off); free(hist); nb_close(&nb);
+  return rc;
+}

@@ -55,6 +55,18 @@ int  h10x_session_clusterReport(h10x_session *s, int codeMin, int codeMax, FILE 
 int  h10x_session_clusterVerbose(h10x_session *s, int codeMin, int codeMax, FILE *out, FILE *err);
 int  h10x_session_cribSummary(h10x_session *s, FILE *out);
 
+/* the neighbour commands (hash10x.c:512-521, 541-718, 1220-1225, 1271-1272): --hashInfo <start> <end> <skip>, --hashExplore <hash>,
+   --doubleShared <hash1> <hash2> print to out; --errorFix <hashMin> <hashMax> prints to out (the reference's stdout) and fails with
+   "need to set crib" without one; --shareScan <countMin> <countMax> prints to out. The census runs on the device (h10x_neighbours /
+   _max / _hist) in batches of bounded memory. Without --hashDepthRange each prints the reference's "<name> called without
+   hashDepthRange" to err and returns 0; where the reference is undefined (ranges beyond hashNumber, skip <= 0, ...) they fail with a
+   "!! ..." message. Single-GPU sessions only. */
+int  h10x_session_hashInfo(h10x_session *s, int hMin, int hMax, int skip, FILE *out, FILE *err);
+int  h10x_session_hashExplore(h10x_session *s, int x, FILE *out, FILE *err);
+int  h10x_session_doubleShared(h10x_session *s, int x1, int x2, FILE *out, FILE *err);
+int  h10x_session_errorFix(h10x_session *s, int hashMin, int hashMax, FILE *out, FILE *err);
+int  h10x_session_shareScan(h10x_session *s, int countMin, int countMax, FILE *out, FILE *err);
+
 /* --sortFQB <in.fqb> <out.fqb> (addition): the record sort the reference leaves to `bsort -k 4 -r 120` (README.md:26),
    on the device: records ordered by their first 4 bytes, stably */
 int  h10x_session_sortFQB(h10x_session *s, const char *inPath, const char *outPath);

@@ -8,6 +8,7 @@
  * --readFQB / --readHash, each command is echoed as "COMMAND ..." and followed by a resource line. Fatal conditions
  * print "FATAL ERROR: <the reference's message>" and exit(-1) like die() (utils.c:18-29). The dispatch itself is a
  * table of commands, not the reference's if-chain.
+ * --interactive reads further commands from stdin, one line each, as the reference does (hash10x.c:1281-1300).
  * Additions: --device <n>, --gpus <n>, --sortFQB; the resource line also carries wall-clock seconds.
  */
 #define _GNU_SOURCE
@@ -15,6 +16,7 @@
 #include <stdlib.h>
 #include <string.h>
 #include <stdarg.h>
+#include <ctype.h>
 #include <time.h>
 #include <pthread.h>
 #include <sys/stat.h>
@@ -133,12 +135,16 @@ static void usage(void) {
   fprintf(stderr, "   -ct | --clusterThreshold <clusterThreshold> [%d]\n", h10x_session_get(s, "ct"));
   fprintf(stderr, "   -t | --threads <n> : accepted and ignored (clustering runs on the GPU)\n");
   fprintf(stderr, "   -o | --output <output filename> : '-' for stdout\n");
+  fprintf(stderr, "   --interactive: enter interactive mode: --commands only without --\n");
   fprintf(stderr, "   --device <HIP device ordinal> [0]\n");
   fprintf(stderr, "   --gpus <n> [1]: shard the barcodes of the next --readFQB / --readHash over n GPUs (devices device, device+1, ...)\n");
   fprintf(stderr, "   --sortFQB <fqb from fq2b> <sorted fqb output>: sort records by barcode on the GPU (instead of bsort -k 4 -r 120)\n");
   fprintf(stderr, "   --readFQB <sorted fqb input file name>: must have this or readHash\n");
   fprintf(stderr, "   --readHash <hash input file name>\n");
   fprintf(stderr, "   --writeHash <hash output file name>\n");
+  fprintf(stderr, "   --hashInfo <start> <end> <skip>: info for hashes in [start,end)\n");
+  fprintf(stderr, "   --hashExplore <hash>: look for structure around hash\n");
+  fprintf(stderr, "   --doubleShared <hash1> <hash2>: codes shared with both\n");
   fprintf(stderr, "   --hashDepthRange <min> <max>: set limits for hash counts for cluster\n");
   fprintf(stderr, "   --cluster <codeMin> <codeMax>: cluster reads for range of barcodes (1, 0 for all)\n");
   fprintf(stderr, "   --clusterSplit\n");
@@ -148,7 +154,11 @@ static void usage(void) {
   fprintf(stderr, "   --tables : toggle the CRIB_TABLE lines of cribBuild\n");
   fprintf(stderr, "   --hashStats : distribution of hash counts and summary info\n");
   fprintf(stderr, "   --codeStats : distribution of barcode/cluster sizes and summary info\n");
+  fprintf(stderr, "   --errorFix <hashMin> <hashMax>: score each hash of the range from its neighbours' shared codes against the crib (needs cribBuild)\n");
+  fprintf(stderr, "   --shareScan <countMin> <countMax>: shared-code histograms of up to 10 hashes per depth in [countMin,countMax)\n");
   fprintf(stderr, "   --help : print this usage message\n");
+  fprintf(stderr, "   --quit : end interactive input and exit program\n");
+  fprintf(stderr, "   --exit : end interactive input and exit program\n");
 }
 static void say_initialised(void) {
   h10x_session *s = team.s[0];
@@ -257,6 +267,21 @@ static void cmd_device(char **a) {
   for (int r = 0; r < team.n; ++r) h10x_session_set(team.s[r], "device", (atoi(a[0]) + r) % nDev);
 }
 
+/* the neighbour commands (hash10x.c:588-718): one GPU holding the whole data set */
+static void one_gpu(const char *name) {
+  if (team.n > 1) die("%s does not run on a sharded session (--gpus %d): each rank holds only its own barcodes", name, team.n);
+}
+static void nb_done(int rc) { if (rc) soft_or_die(1); }
+static void cmd_hashInfo(char **a) { one_gpu("--hashInfo"); nb_done(h10x_session_hashInfo(team.s[0], atoi(a[0]), atoi(a[1]), atoi(a[2]), outFile, stderr)); }
+static void cmd_hashExplore(char **a) { one_gpu("--hashExplore"); nb_done(h10x_session_hashExplore(team.s[0], atoi(a[0]), outFile, stderr)); }
+static void cmd_doubleShared(char **a) { one_gpu("--doubleShared"); nb_done(h10x_session_doubleShared(team.s[0], atoi(a[0]), atoi(a[1]), outFile, stderr)); }
+static void cmd_errorFix(char **a) {                                                  /* printf in the reference: stdout even with -o, and its own time line */
+  one_gpu("--errorFix");
+  if (h10x_session_errorFix(team.s[0], atoi(a[0]), atoi(a[1]), stdout, stderr)) { soft_or_die(1); return; }
+  timeUpdate(stdout, 0);
+}
+static void cmd_shareScan(char **a) { one_gpu("--shareScan"); nb_done(h10x_session_shareScan(team.s[0], atoi(a[0]), atoi(a[1]), outFile, stderr)); }
+
 typedef struct { const char *name; int nArgs; void (*run)(char **args); const char *param; } Command;
 static const Command commands[] = {
   {"-k", 1, 0, "k"}, {"-w", 1, 0, "w"}, {"-r", 1, 0, "r"}, {"-B", 1, 0, "B"}, {"-N", 1, 0, "N"}, {"-c", 1, 0, "c"},
@@ -268,8 +293,36 @@ static const Command commands[] = {
   {"--hashDepthRange", 2, cmd_hashDepthRange, 0}, {"--cluster", 2, cmd_cluster, 0}, {"--clusterSplit", 0, cmd_clusterSplit, 0},
   {"--sortFQB", 2, cmd_sortFQB, 0}, {"--cribBuild", 2, cmd_cribBuild, 0}, {"--clusterReport", 2, cmd_clusterReport, 0},
   {"--cribSummary", 0, cmd_cribSummary, 0}, {"--hashStats", 0, cmd_hashStats, 0}, {"--codeStats", 0, cmd_codeStats, 0},
+  {"--hashInfo", 3, cmd_hashInfo, 0}, {"--hashExplore", 1, cmd_hashExplore, 0}, {"--doubleShared", 2, cmd_doubleShared, 0},
+  {"--errorFix", 2, cmd_errorFix, 0}, {"--shareScan", 2, cmd_shareScan, 0},
   {"--help", 0, cmd_help, 0},
   {0, 0, 0, 0}};
+
+/* --interactive (hash10x.c:1287-1300): the next line of stdin as the next commands — leading blanks skipped, an empty line is --help,
+   the first word gets "--" in front, the words are split at blanks; end of input (also inside a line) ends the program */
+static char *inBuf; static size_t inLen, inCap;
+static char *inArgs[32];
+static void in_put(char ch) {
+  if (inLen == inCap) { inCap = inCap ? 2 * inCap : 1024; if (!(inBuf = (char *)realloc(inBuf, inCap))) die("out of memory"); }
+  inBuf[inLen++] = ch;
+}
+static int read_input_line(int *argc, char ***argv) {                                   /* 1 = end of input */
+  int ch;
+  while ((ch = getchar())) if (!isspace(ch) || ch == '\n') break;
+  if (ch == '\n') { inArgs[0] = (char *)"--help"; *argc = 1; *argv = inArgs; return 0; }
+  inLen = 0; in_put('-'); in_put('-');
+  while (ch != '\n' && ch != EOF) {
+    for (; ch != EOF && isgraph(ch); ch = getchar()) in_put((char)ch);
+    in_put(0);
+    while (ch != EOF && isspace(ch) && ch != '\n') ch = getchar();
+    if (ch != EOF && ch != '\n' && !isgraph(ch) && !isspace(ch)) ch = getchar();     /* a control character: a separator here (the reference would spin on it) */
+  }
+  if (ch == EOF) return 1;
+  int n = 0;
+  for (size_t i = 0; i < inLen && n < 32; ) { inArgs[n++] = inBuf + i; while (inBuf[i++]) ; }
+  *argc = n; *argv = inArgs;
+  return 0;
+}
 
 int main(int argc, char **argv) {
   --argc; ++argv;
@@ -277,24 +330,39 @@ int main(int argc, char **argv) {
   timeUpdate(stdout, 0);
   if (!(team.s[0] = h10x_session_new())) die("out of memory");
   if (!argc) usage();
+  int isInteractive = 0;
 
   while (argc) {
     if (**argv != '-') die("option/command %s does not start with '-': run without arguments for usage", *argv);
-    fprintf(outFile, "COMMAND %s", *argv);
-    for (int i = 1; i < argc && *argv[i] != '-'; ++i) fprintf(outFile, " %s", argv[i]);
-    fputc('\n', outFile);
-    if (outFile != stdout) {                                  /* hash10x.c:1166-1171 as it stands: the echo on stdout carries the command alone, its arguments go to the -o file a second time */
-      printf("COMMAND %s", *argv);
+    if (!isInteractive) {
+      fprintf(outFile, "COMMAND %s", *argv);
       for (int i = 1; i < argc && *argv[i] != '-'; ++i) fprintf(outFile, " %s", argv[i]);
-      putchar('\n');
+      fputc('\n', outFile);
+      if (outFile != stdout) {                                /* hash10x.c:1166-1171 as it stands: the echo on stdout carries the command alone, its arguments go to the -o file a second time */
+        printf("COMMAND %s", *argv);
+        for (int i = 1; i < argc && *argv[i] != '-'; ++i) fprintf(outFile, " %s", argv[i]);
+        putchar('\n');
+      }
     }
     if (!strcmp(*argv, "--quit") || !strcmp(*argv, "--exit")) break;
-    const Command *c = commands;
-    while (c->name && (strcmp(c->name, *argv) || argc < 1 + c->nArgs)) ++c;            /* too few arguments left: not a match, like ARGMATCH */
-    if (!c->name) die("unknown option/command %s; run without arguments for usage", *argv);
-    if (c->param) set_all(c->param, atoi(argv[1])); else c->run(argv + 1);
-    argc -= 1 + c->nArgs; argv += 1 + c->nArgs;
+    if (!strcmp(*argv, "--interactive")) { isInteractive = 1; --argc; ++argv; }
+    else {
+      const Command *c = commands;
+      while (c->name && (strcmp(c->name, *argv) || argc < 1 + c->nArgs)) ++c;          /* too few arguments left: not a match, like ARGMATCH */
+      if (!c->name) {
+        if (isInteractive) fprintf(stderr, "  unknown option/command %s", *argv + 2);   /* (no newline, as in hash10x.c:1277; the line's words stay and are reported below) */
+        else die("unknown option/command %s; run without arguments for usage", *argv);
+      } else {
+        if (c->param) set_all(c->param, atoi(argv[1])); else c->run(argv + 1);
+        argc -= 1 + c->nArgs; argv += 1 + c->nArgs;
+      }
+    }
     printf("  "); timeUpdate(stdout, 0); fflush(stdout);
+    if (isInteractive) {
+      if (argc) fprintf(stderr, "INPUT ERROR - ignoring arguments starting %s\n", *argv);
+      printf("> "); fflush(stdout);
+      if (read_input_line(&argc, &argv)) break;
+    }
   }
   fprintf(outFile, "total resources used: "); timeUpdate(outFile, 1);
   for (int r = 0; r < team.n; ++r) h10x_session_free(team.s[r]);

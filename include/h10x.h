@@ -244,7 +244,8 @@ typedef struct {
 enum { H10X_TABLE_HASHINDEX = 0, H10X_TABLE_HASHVALUE = 1, H10X_TABLE_HASHDEPTH = 2, H10X_TABLE_BLOCKS = 3, H10X_TABLE_CLUSHASH = 4,
        H10X_TABLE_NGOOD = 5,
        H10X_TABLE_CLUSTER_RAW = 6 /* per block, after h10x_cluster: u32 clusters before the read merge (bit 31: given up at the 256th, hash10x.c:810-816),
-                                     u32 good hashes with a label — the figures of the reference's --verbose line (hash10x.c:827-834) */ };
+                                     u32 good hashes with a label — the figures of the reference's --verbose line (hash10x.c:827-834) */,
+       H10X_TABLE_WITHIN = 7 /* hashWithinRange[] (hash10x.c:525-539): one byte per hash index, 1 = in a --hashDepthRange set so far; fails before the first */ };
 int  h10x_shard_info(h10x_ctx *ctx, h10x_shard_info_t *out);
 int  h10x_shard_segments(h10x_ctx *ctx, h10x_shard_seg *out, uint32_t cap);
 int  h10x_shard_prepare_export(h10x_ctx *ctx);
@@ -289,6 +290,28 @@ int  h10x_crib_summary(h10x_ctx *ctx, uint64_t counts[12], uint32_t *seenBase, u
    reference's summary is hashCount() of a HASH object fed in exactly this order (hash.c) — and that count depends on the order once such an object has doubled
    (see RefHash in host/h10x_host.c) — so the host layer replays the words through a restatement of it. */
 int  h10x_crib_words(h10x_ctx *ctx, uint64_t first, uint64_t count, uint32_t *words);
+
+/* ---- neighbour census (csrc/stage_f.hip): the hashes that share barcode blocks with a query hash ----
+   For a query x, N(x) = every hash h != x with hashWithinRange[h] in any block that holds x, and c_x(h) = the number of blocks
+   holding both (hashNeighbours / countHashNeighbours, hash10x.c:541-586; the blocks are the current ones, --clusterSplit
+   included). Each call fails before --hashDepthRange, on a sharded context, and for a query not below hashNumber.
+   h10x_neighbours: the list of --hashInfo / --hashExplore / --doubleShared (hash10x.c:541-567, 588-647): *n = |N(x)|, and the
+     first min(cap, *n) pairs ascending in h: hash[i], count[i] = c_x(hash[i]) (full count; the reference keeps it mod 2^16),
+     firstCode[i] = the lowest barcode holding hash[i] (*arr(hashCodes, h, U32*), hash10x.c:620). Any array may be NULL; call
+     again with a larger cap when *n > cap. A query of depth 0 gives *n = 0.
+   h10x_neighbour_max: per query (repeats allowed) what --hashInfo prints (hash10x.c:631-647): maxKey[q] = the maximum over N(x) of
+     (c_x(h) mod 2^16) << 32 | h — the last element after the reference's stable sort on the 16-bit count — and nNeighbours[q] = |N(x)|
+     (0: maxKey[q] = 0).
+   h10x_neighbour_hist: per query the histogram countHashNeighbours builds for --errorFix / --shareScan (hash10x.c:569-586, 651-718):
+     hist[offsets[q] + k] = the number of h in N(x) with c_x(h) = k, full int counts. offsets has nq + 1 entries; region q is
+     [offsets[q], offsets[q + 1]) and must hold depth(x) + 1 bins (c_x(h) <= depth(x)); bins above the top count are 0.
+   Work is cut into batches of at most "neighbour_budget" gathered ClusterHash records (h10x_set_option); a larger query runs in
+   windows of hash index. h10x_neighbour_stats: out[0] records gathered, out[1] in-range keys sorted, out[2] batches, out[3]
+   windows, since the last call with reset != 0. */
+int  h10x_neighbours(h10x_ctx *ctx, uint32_t x, uint32_t *hash, uint32_t *count, uint32_t *firstCode, uint64_t cap, uint64_t *n);
+int  h10x_neighbour_max(h10x_ctx *ctx, const uint32_t *xs, uint32_t nq, uint64_t *maxKey, uint32_t *nNeighbours);
+int  h10x_neighbour_hist(h10x_ctx *ctx, const uint32_t *xs, uint32_t nq, const uint64_t *offsets, uint32_t *hist);
+int  h10x_neighbour_stats(h10x_ctx *ctx, uint64_t out[4], int reset);
 
 /* ---- device memory plumbing for callers that keep the input resident in HBM (bench, pipelines) ----
    plain hipMalloc / hipMemcpy / hipDeviceSynchronize on `device`; return NULL / non-zero on failure */
@@ -364,7 +387,8 @@ int  h10x_get_counters(h10x_ctx *ctx, h10x_counters *out);
    the main stream's kernels; 0 = every exchange on the main stream),
    "shard_owner_cut" (0 default = hash owners' value ranges cut at the quantiles of the canonical-hash density, equal shares; 1 = equal value ranges),
    "shard_row_shift", "shard_rows_fake_base" (sharded list offsets beyond 32 bits on small inputs), "shard_delta_lists" (-1 default:
-   the in-range barcode lists travel delta-coded where bytes are dear — more than one rank on the host-staged TCP backend, not over xGMI; 0 never; 1 always). Unknown name: -1. */
+   the in-range barcode lists travel delta-coded where bytes are dear — more than one rank on the host-staged TCP backend, not over xGMI; 0 never; 1 always),
+   "neighbour_budget" (gathered ClusterHash records per batch of the neighbour census; 0 = default 2^26; small values force batches and hash-index windows). Unknown name: -1. */
 int  h10x_set_option(h10x_ctx *ctx, const char *name, int64_t value);
 
 #ifdef __cplusplus
