@@ -153,6 +153,9 @@ def load_native():
     hip.h10x_neighbour_max.argtypes = [vp, vp, ctypes.c_uint32, vp, vp]
     hip.h10x_neighbour_hist.argtypes = [vp, vp, ctypes.c_uint32, vp, vp]
     hip.h10x_neighbour_stats.argtypes = [vp, vp, ci]
+    hip.h10x_code_share.argtypes = [vp, vp, ctypes.c_uint32, vp, vp, vp, vp, vp, cu64]
+    hip.h10x_code_explore.argtypes = [vp, ctypes.c_int32, ctypes.c_int32, vp]
+    hip.h10x_code_crib_counts.argtypes = [vp, vp, ctypes.c_uint32, vp]
     if hip.h10x_abi_version() != ABI_VERSION:
         raise RuntimeError("libh10x_hip.so speaks ABI %d, hash10x_amd/__init__.py was written for %d (include/h10x.h H10X_ABI_VERSION): rebuild with "
                            "`python -c 'import __graft_entry__ as g; g.build()'`" % (hip.h10x_abi_version(), ABI_VERSION))
@@ -650,6 +653,33 @@ class Hash10x:
         v = np.zeros(4, dtype=np.uint64)
         self._chk_ctx(self._hip.h10x_neighbour_stats(self._ctx(), v.ctypes.data, 1 if reset else 0))
         return dict(zip(("gathered", "sorted", "batches", "windows"), (int(a) for a in v)))
+
+    # ---- barcode census and --codeExplore (h10x_code_share / _explore / _crib_counts: codeExplore, hash10x.c:1351-1470) ----
+    def code_share(self, codes):
+        """per query barcode: (barcode, count = countShare, firstRank, firstHash) of the barcodes sharing its good hashes'
+        lists, ascending in barcode — a list of dicts of uint32 arrays."""
+        q = np.ascontiguousarray(codes, dtype=np.uint32).reshape(-1)
+        off = np.zeros(q.size + 1, dtype=np.uint64)
+        self._chk_ctx(self._hip.h10x_code_share(self._ctx(), q.ctypes.data, q.size, off.ctypes.data, None, None, None, None, 0))
+        m = int(off[-1])
+        cols = [np.zeros(max(m, 1), dtype=np.uint32) for _ in range(4)]
+        self._chk_ctx(self._hip.h10x_code_share(self._ctx(), q.ctypes.data, q.size, off.ctypes.data, *(c.ctypes.data for c in cols), m))
+        names = ("barcode", "count", "firstRank", "firstHash")
+        return [{n: c[int(off[i]):int(off[i + 1])] for n, c in zip(names, cols)} for i in range(q.size)]
+
+    def code_explore(self, code, threshold=5):
+        """codeExplore's re-clustering of one barcode (state change only, no text): nHash, nGood, clustered, raw, merged, abandoned,
+        histMax (the largest countShare), nShare (barcodes sharing)."""
+        rep = np.zeros(8, dtype=np.uint32)
+        self._chk_ctx(self._hip.h10x_code_explore(self._ctx(), int(code), int(threshold), rep.ctypes.data))
+        return dict(zip(("nHash", "nGood", "clustered", "raw", "merged", "abandoned", "histMax", "nShare"), (int(v) for v in rep)))
+
+    def code_crib_counts(self, codes):
+        """per barcode the CRIB_HTA and CRIB_HTB records of its block: an (n, 2) uint32 array (needs a crib)."""
+        q = np.ascontiguousarray(codes, dtype=np.uint32).reshape(-1)
+        out = np.zeros((max(q.size, 1), 2), dtype=np.uint32)
+        self._chk_ctx(self._hip.h10x_code_crib_counts(self._ctx(), q.ctypes.data, q.size, out.ctypes.data))
+        return out[:q.size]
 
     def export_within(self):
         """hashWithinRange[0 .. hashNumber) as uint8 (fails before --hashDepthRange)."""

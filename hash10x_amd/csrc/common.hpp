@@ -425,6 +425,7 @@ int stageB_blockClassLists(Ctx *c, DevBuf<u32> &lists, DevBuf<u32> &counts);
 int stageC_depthRange(Ctx *c, int min, int max);
 int stageC_cluster(Ctx *c, int codeMin, int codeMax, int threshold);
 int stageC_split(Ctx *c);
+int stageC_readMerge(Ctx *c, u32 code);         // codeClusterReadMerge of one block (--codeExplore, stage_f.hip)
 int stageD_cribGenome(Ctx *c, const u8 *hostCodes, const u64 *seqStart, u32 nSeq, int which, u64 *nPresent, u64 *nAbsent);
 int stageD_cribFinish(Ctx *c);
 int stageE_histMax(Ctx *c, int which, u64 first, u64 count, u32 *maxValue);
@@ -435,6 +436,9 @@ int stageE_cribWords(Ctx *c, u64 first, u64 count, u32 *hostOut);
 int stageF_neighbours(Ctx *c, u32 x, u32 *hash, u32 *count, u32 *first, u64 cap, u64 *n);
 int stageF_neighbourMax(Ctx *c, const u32 *xs, u32 nq, u64 *maxKey, u32 *nNb);
 int stageF_neighbourHist(Ctx *c, const u32 *xs, u32 nq, const u64 *offsets, u32 *hist);
+int stageF_codeShare(Ctx *c, const u32 *codes, u32 nq, u64 *offsets, u32 *barcode, u32 *count, u32 *firstRank, u32 *firstHash, u64 cap);
+int stageF_codeExplore(Ctx *c, int code, int threshold, u32 *out /* 8: h10x_code_explore_rep */);
+int stageF_codeCrib(Ctx *c, const u32 *codes, u32 n, u32 *out);
 int shard_allreduceU64(Ctx *c, u64 *v, u32 n, int op);
 int shard_gatherBytes(Ctx *c, const void *send, u64 nbytes, void *recv, u64 cap, u64 *counts);
 int shard_exchangeRows(Ctx *c);

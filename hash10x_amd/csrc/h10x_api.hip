@@ -518,6 +518,22 @@ int h10x_neighbour_stats(h10x_ctx *h, uint64_t out[4], int reset) {
   if (reset) for (int i = 0; i < 4; ++i) h->c.nbStats[i] = 0;
   return 0;
 }
+// ---- barcode census and --codeExplore (stage_f.hip): codeExplore, hash10x.c:1351-1470 ----
+int h10x_code_share(h10x_ctx *h, const uint32_t *codes, uint32_t nq, uint64_t *offsets, uint32_t *barcode, uint32_t *count, uint32_t *firstRank, uint32_t *firstHash, uint64_t cap) {
+  if (!h || !offsets || (nq && !codes)) return -1; H10X_TRY(enter(h->c));
+  return stageF_codeShare(&h->c, codes, nq, (u64 *)offsets, barcode, count, firstRank, firstHash, cap);
+}
+int h10x_code_explore(h10x_ctx *h, int32_t code, int32_t threshold, h10x_code_explore_rep *rep) {
+  static_assert(sizeof(h10x_code_explore_rep) == 32, "h10x_code_explore_rep: eight u32");
+  if (!h || !rep) return -1; H10X_TRY(enter(h->c));
+  u32 out[8];
+  H10X_TRY(stageF_codeExplore(&h->c, code, threshold, out));
+  rep->nHash = out[0]; rep->nGood = out[1]; rep->clustered = out[2]; rep->raw = out[3]; rep->merged = out[4]; rep->abandoned = out[5]; rep->histMax = out[6]; rep->nShare = out[7];
+  return 0;
+}
+int h10x_code_crib_counts(h10x_ctx *h, const uint32_t *codes, uint32_t n, uint32_t *out) {
+  if (!h || (n && (!codes || !out))) return -1; H10X_TRY(enter(h->c)); return stageF_codeCrib(&h->c, codes, n, out);
+}
 
 int h10x_timing_enable(h10x_ctx *h, int on) { if (!h) return -1; h->c.timing = on != 0; return 0; }
 int h10x_timing_count(const h10x_ctx *) { return T_COUNT; }

@@ -2613,6 +2613,18 @@ static int cluster_local_range(Ctx *c, int codeMin, int codeMax, int threshold, 
   return 0;
 }
 
+// codeExplore's read merge (hash10x.c:1415-1436, codeClusterReadMerge's algorithm) on block `code` alone, after stage_f.hip replayed
+// its clustering: the same kernels as --cluster's, one workgroup (the class that does not hold the block returns at once)
+int stageC_readMerge(Ctx *c, u32 code) {
+  hipStream_t st = c->stream;
+  const size_t ldsSmall = mergeBytes(MERGE_SMALL_READS), ldsBig = mergeBytes(65536);
+  read_merge_kernel<false><<<1, MERGE_THREADS, ldsSmall, st>>>(c->blocks.p, c->blockOff.p, c->nGood.p, c->clusHash.p, code);
+  H10X_HIP(c, hipFuncSetAttribute((const void *)read_merge_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsBig));
+  read_merge_kernel<true><<<1, MERGE_THREADS, ldsBig, st>>>(c->blocks.p, c->blockOff.p, c->nGood.p, c->clusHash.p, code);
+  H10X_HIP(c, hipGetLastError());
+  return 0;
+}
+
 // the --cluster loop over GLOBAL block numbers [codeMin, codeMax): every segment of this context runs its part
 int stageC_cluster(Ctx *c, int codeMin, int codeMax, int threshold) {
   if (!c->haveGood) return c->fail("!! you must set hashDepthRange before cluster");          // hash10x.c:1258

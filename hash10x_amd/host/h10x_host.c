@@ -1465,3 +1465,54 @@ done:
   free(nBin); free(xBin); free(xs); free(slot); free(off); free(hist); nb_close(&nb);
   return rc;
 }
+
+/* ---- --codeExplore (hash10x.c:1351-1470): the clustering, the barcode census and the crib counts run on the device (h10x_code_explore,
+   h10x_code_share, h10x_code_crib_counts); the host prints. ---- */
+typedef struct { uint32_t code, count, rank, hash; } CeRow;
+static int ce_by_count(const void *a, const void *b) {          /* compareCount under glibc's stable sort, walked backwards: count descending, ties by barcode descending */
+  const CeRow *x = (const CeRow *)a, *y = (const CeRow *)b;
+  if (x->count != y->count) return x->count > y->count ? -1 : 1;
+  return x->code > y->code ? -1 : x->code < y->code;
+}
+int h10x_session_codeExplore(h10x_session *s, int code, FILE *out, FILE *err) {
+  if (!s->ctx) return fail(s, "!! you must set hashDepthRange before codeExplore");   /* nothing loaded: no range either */
+  h10x_shard_info_t z; if (h10x_shard_info(s->ctx, &z)) return fail_ctx(s);
+  if (z.nranks > 1) return fail(s, "codeExplore does not run on a sharded session (--gpus > 1)");
+  h10x_code_explore_rep rep;
+  if (h10x_code_explore(s->ctx, code, s->ct, &rep)) return fail_ctx(s);
+  if (!rep.nGood) return 0;                                       /* hash10x.c:1361 */
+  if (rep.abandoned) fprintf(err, "    code %d with %d good hashes has too many clusters\n", code, (int)rep.nGood);
+  if (!rep.raw) { fprintf(out, "  code %d with %d hashes, %d good hashes, 0 clusters\n", code, (int)rep.nHash, (int)rep.nGood); return 0; }
+  fprintf(out, "  code %d with %d hashes, %d good hashes, of which %d cluster into %d raw", code, (int)rep.nHash, (int)rep.nGood, (int)rep.clustered, (int)rep.raw);
+  fprintf(out, " then %d merged clusters\n", (int)rep.merged);
+  int rc = 0; Nb nb; memset(&nb, 0, sizeof nb); char t[64];
+  uint64_t off[2]; const uint32_t q = (uint32_t)code; uint64_t m = 0;
+  uint32_t *bc = 0, *cnt = 0, *fr = 0, *fh = 0, *crib = 0, *sel = 0; uint64_t *hist = 0; CeRow *rows = 0;
+  if (h10x_code_share(s->ctx, &q, 1, off, 0, 0, 0, 0, 0)) { rc = fail_ctx(s); goto done; }
+  m = off[1];
+  bc = (uint32_t *)malloc((m + 1) * 4); cnt = (uint32_t *)malloc((m + 1) * 4); fr = (uint32_t *)malloc((m + 1) * 4); fh = (uint32_t *)malloc((m + 1) * 4);
+  rows = (CeRow *)malloc((m + 1) * sizeof *rows); hist = (uint64_t *)calloc((size_t)rep.histMax + 1, 8);
+  if (!bc || !cnt || !fr || !fh || !rows || !hist) { rc = fail(s, "out of host memory for codeExplore"); goto done; }
+  if (h10x_code_share(s->ctx, &q, 1, off, bc, cnt, fr, fh, m)) { rc = fail_ctx(s); goto done; }
+  if (off[1] != m || m != rep.nShare) { rc = fail(s, "codeExplore: the census of %d changed size", code); goto done; }
+  /* COUNT_SHARE over countShare[] of every block 0 .. nBlocks - 1 (hash10x.c:1444-1451) */
+  hist[0] = (uint64_t)z.nBlocksGlobal - m;
+  for (uint64_t i = 0; i < m; ++i) { ++hist[cnt[i]]; rows[i].code = bc[i]; rows[i].count = cnt[i]; rows[i].rank = fr[i]; rows[i].hash = fh[i]; }
+  write_histogram(out, "COUNT_SHARE", hist, (int)rep.histMax + 1);
+  if (h10x_session_clusterReport(s, code, code + 1, out)) { rc = -1; goto done; }
+  { uint32_t histDim = 0; if (h10x_crib_sizes(s->ctx, &histDim, 0)) { rc = fail(s, "!! codeExplore needs --cribBuild for its SHARE lines"); goto done; } }   /* the reference reads a NULL cribType */
+  if ((rc = nb_open(s, &nb))) { if (rc > 0) rc = fail(s, "!! you must set hashDepthRange before codeExplore"); goto done; }
+  qsort(rows, m, sizeof *rows, ce_by_count);
+  uint64_t listed = 0;                                            /* the walk stops after the first line below the threshold (hash10x.c:1464) */
+  while (listed < m && rows[listed++].count >= (uint32_t)s->ct) {}
+  sel = (uint32_t *)malloc((listed + 1) * 4); crib = (uint32_t *)malloc((listed + 1) * 8);
+  if (!sel || !crib) { rc = fail(s, "out of host memory for codeExplore"); goto done; }
+  for (uint64_t i = 0; i < listed; ++i) sel[i] = rows[i].code;
+  if (h10x_code_crib_counts(s->ctx, sel, (uint32_t)listed, crib)) { rc = fail_ctx(s); goto done; }
+  for (uint64_t i = 0; i < listed; ++i)                          /* minShare = first[cj], and cribText of the hash at that rank */
+    fprintf(out, "  SHARE code %d shared_hashes %d counts %d htA %d htB minShare %d %s\n", (int)rows[i].code, (int)rows[i].count, (int)crib[2 * i], (int)crib[2 * i + 1],
+            (int)rows[i].rank, nb_text(s, &nb, rows[i].hash, t));
+done:
+  free(bc); free(cnt); free(fr); free(fh); free(rows); free(hist); free(sel); free(crib); nb_close(&nb);
+  return rc;
+}

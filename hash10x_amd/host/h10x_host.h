@@ -66,6 +66,11 @@ int  h10x_session_hashExplore(h10x_session *s, int x, FILE *out, FILE *err);
 int  h10x_session_doubleShared(h10x_session *s, int x1, int x2, FILE *out, FILE *err);
 int  h10x_session_errorFix(h10x_session *s, int hashMin, int hashMax, FILE *out, FILE *err);
 int  h10x_session_shareScan(h10x_session *s, int countMin, int countMax, FILE *out, FILE *err);
+/* --codeExplore <code> (hash10x.c:1226-1232, 1351-1470) with the session's -ct: re-clusters the barcode's good hashes on the device
+   (h10x_code_explore), then prints its line, the COUNT_SHARE histogram, codeClusterReport's lines of the barcode and the SHARE lines
+   to out, and the "too many clusters" note to err. Fails with "!! ..." before --hashDepthRange, for a code outside 0 .. nBlocks - 1,
+   for -ct < 1, and — after everything else is printed and the state changed — without a crib. Single-GPU sessions only. */
+int  h10x_session_codeExplore(h10x_session *s, int code, FILE *out, FILE *err);
 
 /* --sortFQB <in.fqb> <out.fqb> (addition): the record sort the reference leaves to `bsort -k 4 -r 120` (README.md:26),
    on the device: records ordered by their first 4 bytes, stably */

@@ -156,6 +156,7 @@ static void usage(void) {
   fprintf(stderr, "   --codeStats : distribution of barcode/cluster sizes and summary info\n");
   fprintf(stderr, "   --errorFix <hashMin> <hashMax>: score each hash of the range from its neighbours' shared codes against the crib (needs cribBuild)\n");
   fprintf(stderr, "   --shareScan <countMin> <countMax>: shared-code histograms of up to 10 hashes per depth in [countMin,countMax)\n");
+  fprintf(stderr, "   --codeExplore <code>: recluster one barcode and list the barcodes that share its good hashes (needs hashDepthRange; cribBuild for the SHARE lines)\n");
   fprintf(stderr, "   --help : print this usage message\n");
   fprintf(stderr, "   --quit : end interactive input and exit program\n");
   fprintf(stderr, "   --exit : end interactive input and exit program\n");
@@ -281,6 +282,7 @@ static void cmd_errorFix(char **a) {                                            
   timeUpdate(stdout, 0);
 }
 static void cmd_shareScan(char **a) { one_gpu("--shareScan"); nb_done(h10x_session_shareScan(team.s[0], atoi(a[0]), atoi(a[1]), outFile, stderr)); }
+static void cmd_codeExplore(char **a) { one_gpu("--codeExplore"); nb_done(h10x_session_codeExplore(team.s[0], atoi(a[0]), outFile, stderr)); }   /* hash10x.c:1226-1232 */
 
 typedef struct { const char *name; int nArgs; void (*run)(char **args); const char *param; } Command;
 static const Command commands[] = {
@@ -294,7 +296,7 @@ static const Command commands[] = {
   {"--sortFQB", 2, cmd_sortFQB, 0}, {"--cribBuild", 2, cmd_cribBuild, 0}, {"--clusterReport", 2, cmd_clusterReport, 0},
   {"--cribSummary", 0, cmd_cribSummary, 0}, {"--hashStats", 0, cmd_hashStats, 0}, {"--codeStats", 0, cmd_codeStats, 0},
   {"--hashInfo", 3, cmd_hashInfo, 0}, {"--hashExplore", 1, cmd_hashExplore, 0}, {"--doubleShared", 2, cmd_doubleShared, 0},
-  {"--errorFix", 2, cmd_errorFix, 0}, {"--shareScan", 2, cmd_shareScan, 0},
+  {"--errorFix", 2, cmd_errorFix, 0}, {"--shareScan", 2, cmd_shareScan, 0}, {"--codeExplore", 1, cmd_codeExplore, 0},
   {"--help", 0, cmd_help, 0},
   {0, 0, 0, 0}};
 

@@ -313,6 +313,37 @@ int  h10x_neighbour_max(h10x_ctx *ctx, const uint32_t *xs, uint32_t nq, uint64_t
 int  h10x_neighbour_hist(h10x_ctx *ctx, const uint32_t *xs, uint32_t nq, const uint64_t *offsets, uint32_t *hist);
 int  h10x_neighbour_stats(h10x_ctx *ctx, uint64_t out[4], int reset);
 
+/* ---- barcode census and --codeExplore (csrc/stage_f.hip, codeExplore: hash10x.c:1351-1470) ----
+   For a barcode `code` with good hashes g[0 .. n) (the --hashDepthRange lists, ranks in depth order), every entry cj != code of the
+   barcode list of hash(g[i]), i = 0 .. n-1 (repeats as the list holds them): countShare[cj] = the number of such entries,
+   first[cj] = the lowest rank i whose list holds cj. Every call fails on a sharded context, before --hashDepthRange and after
+   --clusterSplit until a new range is set ("!! you must set hashDepthRange before ..."), and for a barcode not below nBlocks.
+   h10x_code_share: per query (repeats allowed) the rows (barcode, count = countShare, firstRank = first, firstHash = hash index
+     at g[first]) of the barcodes with countShare > 0, ascending in barcode; rows of query q = [offsets[q], offsets[q + 1]) (offsets:
+     nq + 1 entries, always filled). The first min(cap, offsets[nq]) rows are written (any array may be NULL): call with cap 0 for
+     the sizes, then again. Batches and windows (of barcode index) as the neighbour census, counted in h10x_neighbour_stats.
+   h10x_code_explore: codeExplore's state change for one barcode — the good hashes' labels wiped and re-clustered with i from 0 (not
+     1 as in --cluster), clusters numbered in founding order, the 256th abandons the block (labels 0, nSubCluster 0, pointToMin
+     keeps the partial sum: hash10x.c:1392-1397), pointToMin = the fp64 sum in rank order, then the read merge of --cluster. A
+     barcode without good hashes is left as it is (rep: nHash, nGood only). Also fails for code < 0 ("!! codeExplore code ...
+     outside 0 to nBlocks") and threshold < 1 ("!! clusterThreshold ... must be >= 1 ..."). The COUNT_SHARE histogram has
+     histMax + 1 bins: bin 0 = nBlocks - nShare, bin k = rows of h10x_code_share with count k.
+   h10x_code_crib_counts: per listed barcode the CRIB_HTA and CRIB_HTB records of its block (out[2 q], out[2 q + 1]: the htA / htB
+     figures of the SHARE lines); fails without a crib ("!! codeExplore needs --cribBuild for its SHARE lines"). */
+typedef struct {
+  uint32_t nHash, nGood;   /* the block's records and good hashes */
+  uint32_t clustered;      /* good hashes labelled before the read merge (0 when abandoned) */
+  uint32_t raw;            /* clusters before the read merge (0 when abandoned) */
+  uint32_t merged;         /* clusters after it: the block's nSubCluster */
+  uint32_t abandoned;      /* 1 = the 256th cluster gave the block up */
+  uint32_t histMax;        /* the largest countShare */
+  uint32_t nShare;         /* barcodes with countShare > 0 */
+} h10x_code_explore_rep;
+int  h10x_code_share(h10x_ctx *ctx, const uint32_t *codes, uint32_t nq, uint64_t *offsets, uint32_t *barcode, uint32_t *count,
+                     uint32_t *firstRank, uint32_t *firstHash, uint64_t cap);
+int  h10x_code_explore(h10x_ctx *ctx, int32_t code, int32_t threshold, h10x_code_explore_rep *rep);
+int  h10x_code_crib_counts(h10x_ctx *ctx, const uint32_t *codes, uint32_t n, uint32_t *out);
+
 /* ---- device memory plumbing for callers that keep the input resident in HBM (bench, pipelines) ----
    plain hipMalloc / hipMemcpy / hipDeviceSynchronize on `device`; return NULL / non-zero on failure */
 void *h10x_device_malloc(int device, uint64_t bytes);
