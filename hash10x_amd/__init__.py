@@ -47,6 +47,21 @@ class _ShardSeg(ctypes.Structure):
                 ("entries", ctypes.c_uint64), ("localEntryStart", ctypes.c_uint64), ("globalEntryStart", ctypes.c_uint64)]
 
 
+class _MoshInfo(ctypes.Structure):
+    _fields_ = [("B", ctypes.c_int32), ("k", ctypes.c_int32), ("w", ctypes.c_int32), ("reserved", ctypes.c_int32),
+                ("factor1", ctypes.c_uint64), ("factor2", ctypes.c_uint64), ("max", ctypes.c_uint32), ("size", ctypes.c_uint32)]
+
+
+class _SeqhashRec(ctypes.Structure):
+    _fields_ = [("k", ctypes.c_int32), ("w", ctypes.c_int32), ("mask", ctypes.c_uint64), ("shift1", ctypes.c_int32), ("shift2", ctypes.c_int32),
+                ("factor1", ctypes.c_uint64), ("factor2", ctypes.c_uint64), ("patternRC", ctypes.c_uint64 * 4)]
+
+
+class _MoshFile(ctypes.Structure):
+    _fields_ = [("B", ctypes.c_int32), ("size", ctypes.c_uint32), ("sh", _SeqhashRec), ("index", ctypes.c_void_p), ("value", ctypes.c_void_p),
+                ("depth", ctypes.c_void_p), ("info", ctypes.c_void_p)]
+
+
 _BLOCK_REP = np.dtype([("nGood", "<u4"), ("nClusHash", "<u4"), ("nClusRead", "<u4"), ("reserved", "<u4")])
 _CLUSTER_REP = np.dtype([("n", "<u4"), ("nRead", "<u4"), ("nt", "<u4", (5,)), ("nBad", "<u4"), ("chr", "<i2"), ("pMin", "<u2"), ("pMax", "<u2"), ("nOtherListed", "<u2"), ("other", "<u4", (10,))])
 assert _BLOCK_REP.itemsize == 16 and _CLUSTER_REP.itemsize == 80       # h10x_block_rep / h10x_cluster_rep (include/h10x.h)
@@ -156,6 +171,33 @@ def load_native():
     hip.h10x_code_share.argtypes = [vp, vp, ctypes.c_uint32, vp, vp, vp, vp, vp, cu64]
     hip.h10x_code_explore.argtypes = [vp, ctypes.c_int32, ctypes.c_int32, vp]
     hip.h10x_code_crib_counts.argtypes = [vp, vp, ctypes.c_uint32, vp]
+    # mosh sets (csrc/stage_g.hip, host/mosh_host.c)
+    pvp, ci32, cu32 = ctypes.POINTER(vp), ctypes.c_int32, ctypes.c_uint32
+    hip.h10x_factors_from_seed.restype = None; hip.h10x_factors_from_seed.argtypes = [ci32, ctypes.POINTER(cu64), ctypes.POINTER(cu64)]
+    hip.h10x_mosh_create.argtypes = [pvp, ci32, ci32, ci32, ci32, ci, cs, ci]
+    hip.h10x_mosh_load.argtypes = [pvp, ci32, ci32, ci32, cu64, cu64, vp, vp, vp, vp, cu32, ci, cs, ci]
+    hip.h10x_mosh_destroy.restype = None; hip.h10x_mosh_destroy.argtypes = [vp]
+    hip.h10x_mosh_error.restype = cs; hip.h10x_mosh_error.argtypes = [vp]
+    hip.h10x_mosh_info.argtypes = [vp, ctypes.POINTER(_MoshInfo)]
+    hip.h10x_mosh_set_option.argtypes = [vp, cs, ctypes.c_int64]
+    hip.h10x_mosh_add.argtypes = [vp, vp, vp, cu32, ci, cu64, ctypes.POINTER(cu64)]
+    hip.h10x_mosh_scan.argtypes = [vp, vp, vp, cu32, ci, cu64, vp, vp, vp, cu64, ctypes.POINTER(cu64)]
+    hip.h10x_mosh_merge.argtypes = [vp, ci32, ci32, cu64, vp, vp, vp, cu32, ctypes.POINTER(ci)]
+    hip.h10x_mosh_prune.argtypes = [vp, ci32, ci32, ctypes.POINTER(cu32), ctypes.POINTER(cu32)]
+    hip.h10x_mosh_set_copy.argtypes = [vp, ci32, ci32, ci32]
+    hip.h10x_mosh_set_copy_m.argtypes = [vp, ci32]
+    hip.h10x_mosh_summary.argtypes = [vp, vp, vp]
+    hip.h10x_mosh_export.argtypes = [vp, cu64, cu64, vp, vp, vp, vp]
+    hip.h10x_mosh_lookup.argtypes = [vp, vp, cu64, vp, vp]
+    host.h10x_seq_open.restype = vp; host.h10x_seq_open.argtypes = [cs, cs, ci, ctypes.POINTER(ci)]
+    host.h10x_seq_next.argtypes = [vp, cu64, pvp, pvp, ctypes.POINTER(cu32)]
+    host.h10x_seq_error.restype = cs; host.h10x_seq_error.argtypes = [vp]
+    host.h10x_seq_warning.restype = cs; host.h10x_seq_warning.argtypes = [vp]
+    host.h10x_seq_close.restype = None; host.h10x_seq_close.argtypes = [vp]
+    host.h10x_moshfile_read.argtypes = [cs, ctypes.POINTER(_MoshFile), cs, ci]
+    host.h10x_moshfile_free.restype = None; host.h10x_moshfile_free.argtypes = [ctypes.POINTER(_MoshFile)]
+    host.h10x_mosh_set_write.argtypes = [vp, cs, cs, ci]
+    host.h10x_mosh_set_add_file.argtypes = [vp, cs, ci, cu64, ctypes.POINTER(cu64), ctypes.POINTER(cu64), ctypes.POINTER(cu64), cs, ci, cs, ci]
     if hip.h10x_abi_version() != ABI_VERSION:
         raise RuntimeError("libh10x_hip.so speaks ABI %d, hash10x_amd/__init__.py was written for %d (include/h10x.h H10X_ABI_VERSION): rebuild with "
                            "`python -c 'import __graft_entry__ as g; g.build()'`" % (hip.h10x_abi_version(), ABI_VERSION))
@@ -687,3 +729,206 @@ class Hash10x:
         w = np.zeros(max(z["hashNumber"], 1), dtype=np.uint8)
         self._chk_ctx(self._hip.h10x_export_slice(self._ctx(), 7, 0, z["hashNumber"], w.ctypes.data))
         return w[:z["hashNumber"]]
+
+
+# ---- mosh sets: the reference's moshutils (moshset.c, moshutils.c) on the GPU — csrc/stage_g.hip, host/mosh_host.c -------------------
+def _from_ptr(ptr, dtype, n):
+    if not ptr or n == 0:
+        return np.zeros(0, dtype=dtype)
+    buf = (ctypes.c_char * (np.dtype(dtype).itemsize * n)).from_address(ptr)
+    return np.frombuffer(buf, dtype=dtype, count=n).copy()
+
+
+def read_sequences(path, slab=0):
+    """A FASTA / FASTQ file (gzip or plain) through the host reader (seqio.c's rules; no device needed): returns
+    (codes uint8, seq_start uint64 with nSeq + 1 entries, warning text). Raises Hash10xError with the reference's message."""
+    _, host = load_native()
+    msg = ctypes.create_string_buffer(512); fatal = ctypes.c_int(0)
+    r = host.h10x_seq_open(os.fsencode(path), msg, 512, ctypes.byref(fatal))
+    if not r:
+        raise Hash10xError((msg.value.decode() + "\n" if msg.value and not fatal.value else "") +
+                           (msg.value.decode() if fatal.value else "failed to open sequence file %s" % path))
+    try:
+        codes, starts = [], [np.zeros(1, np.uint64)]
+        total = 0
+        while True:
+            c, st, n = ctypes.c_void_p(), ctypes.c_void_p(), ctypes.c_uint32(0)
+            rc = host.h10x_seq_next(r, int(slab), ctypes.byref(c), ctypes.byref(st), ctypes.byref(n))
+            if rc < 0:
+                raise Hash10xError(host.h10x_seq_error(r).decode())
+            if rc == 0:
+                break
+            s = _from_ptr(st.value, np.uint64, n.value + 1)
+            codes.append(_from_ptr(c.value, np.uint8, int(s[-1])))
+            starts.append(s[1:] + np.uint64(total))
+            total += int(s[-1])
+        return (np.concatenate(codes) if codes else np.zeros(0, np.uint8)), np.concatenate(starts), host.h10x_seq_warning(r).decode()
+    finally:
+        host.h10x_seq_close(r)
+
+
+def read_mosh_file(path):
+    """A MSHSTv1 file through the host reader's checks: dict with B, size, k, w, factor1, factor2, index, value, depth, info."""
+    _, host = load_native()
+    m = _MoshFile(); err = ctypes.create_string_buffer(512)
+    if host.h10x_moshfile_read(os.fsencode(path), ctypes.byref(m), err, 512):
+        raise Hash10xError(err.value.decode())
+    try:
+        return dict(B=m.B, size=m.size, k=m.sh.k, w=m.sh.w, factor1=m.sh.factor1, factor2=m.sh.factor2,
+                    index=_from_ptr(m.index, np.uint32, 1 << m.B), value=_from_ptr(m.value, np.uint64, m.size),
+                    depth=_from_ptr(m.depth, np.uint16, m.size), info=_from_ptr(m.info, np.uint8, m.size))
+    finally:
+        host.h10x_moshfile_free(ctypes.byref(m))
+
+
+class MoshSet:
+    """The reference's Moshset on one MI355X: -c / -r / -w / -a / -x / -m / -p / -s / -sM / -H / -d of moshutils as methods."""
+
+    def __init__(self, B=28, k=19, w=31, seed=17, device=0, _handle=None):
+        self._hip, self._host = load_native()
+        self.h = _handle
+        if self.h is None:
+            h = ctypes.c_void_p(); err = ctypes.create_string_buffer(512)
+            if self._hip.h10x_mosh_create(ctypes.byref(h), B, k, w, seed, device, err, 512):
+                raise Hash10xError(err.value.decode())
+            self.h = h
+
+    @classmethod
+    def read(cls, path, device=0):
+        """-r: a set read from a file is full (moshsetRead sizes the arrays to the file)"""
+        f = read_mosh_file(path)
+        return cls.from_arrays(f["B"], f["k"], f["w"], f["factor1"], f["factor2"], f["index"], f["value"], f["depth"], f["info"], device)
+
+    @classmethod
+    def from_arrays(cls, B, k, w, factor1, factor2, index, value, depth, info, device=0):
+        hip, _ = load_native()
+        index = np.ascontiguousarray(index, np.uint32); value = np.ascontiguousarray(value, np.uint64)
+        depth = np.ascontiguousarray(depth, np.uint16); info = np.ascontiguousarray(info, np.uint8)
+        assert len(index) == 1 << B and len(value) == len(depth) == len(info)
+        h = ctypes.c_void_p(); err = ctypes.create_string_buffer(512)
+        if hip.h10x_mosh_load(ctypes.byref(h), B, k, w, int(factor1), int(factor2), index.ctypes.data, value.ctypes.data, depth.ctypes.data,
+                              info.ctypes.data, len(value), device, err, 512):
+            raise Hash10xError(err.value.decode())
+        return cls(_handle=h)
+
+    def close(self):
+        if getattr(self, "h", None):
+            self._hip.h10x_mosh_destroy(self.h)
+        self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _chk(self, rc):
+        if rc:
+            raise Hash10xError(self._hip.h10x_mosh_error(self.h).decode())
+
+    def info(self):
+        i = _MoshInfo()
+        self._hip.h10x_mosh_info(self.h, ctypes.byref(i))
+        return i
+
+    @property
+    def max(self):
+        return self.info().max
+
+    def set_option(self, name, value):
+        if self._hip.h10x_mosh_set_option(self.h, name.encode(), int(value)):
+            raise Hash10xError("unknown mosh option %s" % name)
+
+    @staticmethod
+    def _seqs(codes, seq_start):
+        c = np.ascontiguousarray(codes, np.uint8); s = np.ascontiguousarray(seq_start, np.uint64)
+        assert len(s) >= 1 and int(s[-1]) <= len(c)
+        return c, s
+
+    def add(self, codes, seq_start, is10x=False, seq_base=0):
+        """-a / -x over sequences in memory; returns the number of mosh occurrences"""
+        c, s = self._seqs(codes, seq_start)
+        n = ctypes.c_uint64(0)
+        self._chk(self._hip.h10x_mosh_add(self.h, c.ctypes.data, s.ctypes.data, len(s) - 1, int(bool(is10x)), int(seq_base), ctypes.byref(n)))
+        return n.value
+
+    def add_file(self, path, is10x=False, slab=0):
+        """-a / -x of a sequence file: (sequences, bases, occurrences, warning)"""
+        a, b, c = ctypes.c_uint64(0), ctypes.c_uint64(0), ctypes.c_uint64(0)
+        msg = ctypes.create_string_buffer(512); warn = ctypes.create_string_buffer(256)
+        rc = self._host.h10x_mosh_set_add_file(self.h, os.fsencode(path), int(bool(is10x)), int(slab), ctypes.byref(a), ctypes.byref(b), ctypes.byref(c), msg, 512, warn, 256)
+        if rc > 0:
+            raise Hash10xError((msg.value.decode() + "\n" if msg.value else "") + "failed to open sequence file %s" % path)
+        if rc < 0:
+            raise Hash10xError(msg.value.decode())
+        return a.value, b.value, c.value, warn.value.decode()
+
+    def scan(self, codes, seq_start, is10x=False, seq_base=0):
+        """every mosh of the sequences in order: (hash uint64, sequence uint32, position uint32); the set is not changed"""
+        c, s = self._seqs(codes, seq_start)
+        n = ctypes.c_uint64(0)
+        cap = max(1024, 2 * len(c) // max(1, self.info().w) + 1024)
+        while True:
+            h = np.zeros(cap, np.uint64); q = np.zeros(cap, np.uint32); p = np.zeros(cap, np.uint32)
+            self._chk(self._hip.h10x_mosh_scan(self.h, c.ctypes.data, s.ctypes.data, len(s) - 1, int(bool(is10x)), int(seq_base),
+                                               h.ctypes.data, q.ctypes.data, p.ctypes.data, cap, ctypes.byref(n)))
+            if n.value <= cap:
+                return h[:n.value], q[:n.value], p[:n.value]
+            cap = n.value
+
+    def merge_arrays(self, k, w, factor1, value, depth, info):
+        value = np.ascontiguousarray(value, np.uint64); depth = np.ascontiguousarray(depth, np.uint16); info = np.ascontiguousarray(info, np.uint8)
+        ok = ctypes.c_int(0)
+        self._chk(self._hip.h10x_mosh_merge(self.h, k, w, int(factor1), value.ctypes.data, depth.ctypes.data, info.ctypes.data, len(value), ctypes.byref(ok)))
+        return bool(ok.value)
+
+    def merge(self, path):
+        """-m: False when the file's k, w or factor1 differ (nothing merged)"""
+        f = read_mosh_file(path)
+        return self.merge_arrays(f["k"], f["w"], f["factor1"], f["value"], f["depth"], f["info"])
+
+    def prune(self, lo, hi):
+        a, b = ctypes.c_uint32(0), ctypes.c_uint32(0)
+        self._chk(self._hip.h10x_mosh_prune(self.h, lo, hi, ctypes.byref(a), ctypes.byref(b)))
+        return a.value, b.value
+
+    def set_copy(self, c1, c2, cM):
+        self._chk(self._hip.h10x_mosh_set_copy(self.h, c1, c2, cM))
+
+    def set_copy_m(self, cM):
+        self._chk(self._hip.h10x_mosh_set_copy_m(self.h, cM))
+
+    def hist(self):
+        """(depth histogram with 65536 bins, the four copy counts)"""
+        h = np.zeros(65536, np.uint32); c = np.zeros(4, np.uint32)
+        self._chk(self._hip.h10x_mosh_summary(self.h, h.ctypes.data, c.ctypes.data))
+        return h, c
+
+    def export(self, index=True):
+        """(index or None, value, depth, info) as moshsetWrite stores them"""
+        i = self.info()
+        ix = np.zeros(1 << i.B, np.uint32) if index else None
+        v = np.zeros(i.max + 1, np.uint64); d = np.zeros(i.max + 1, np.uint16); f = np.zeros(i.max + 1, np.uint8)
+        self._chk(self._hip.h10x_mosh_export(self.h, 0, len(ix) if index else 0, ix.ctypes.data if index else None, v.ctypes.data, d.ctypes.data, f.ctypes.data))
+        return ix, v, d, f
+
+    def lookup(self, hashes):
+        """(index, depth) per hash; 0, 0 where the set does not hold it"""
+        q = np.ascontiguousarray(hashes, np.uint64)
+        ix = np.zeros(len(q), np.uint32); d = np.zeros(len(q), np.uint16)
+        self._chk(self._hip.h10x_mosh_lookup(self.h, q.ctypes.data, len(q), ix.ctypes.data, d.ctypes.data))
+        return ix, d
+
+    def write(self, path):
+        err = ctypes.create_string_buffer(512)
+        if self._host.h10x_mosh_set_write(self.h, os.fsencode(path), err, 512):
+            raise Hash10xError(err.value.decode())
+
+
+def mosh_scan(codes, seq_start, k, w, seed, device=0):
+    """The moshes of these sequences as the reference's moshRCiterator yields them: (hash, sequence, position)."""
+    s = MoshSet(B=20, k=k, w=w, seed=seed, device=device)
+    try:
+        return s.scan(codes, seq_start)
+    finally:
+        s.close()

@@ -446,4 +446,22 @@ int shard_split(Ctx *c, const u32 *dSubBefore, u32 totalSubLocal);   // collecti
 int shard_refreshLayout(Ctx *c);                // collective: allSegs / global totals from every rank's current segments
 int shard_materializeTables(Ctx *c);            // collective: hashValue[] + hashIndex[] on every rank (deferred by the sharded --readFQB)                 // sharded --hashDepthRange: allgather the in-range barcode lists
 
+// mosh sets (stage_g.hip): the object of moshset.c behind the h10x_mosh_* entry points
+struct Mosh;
+int stageG_create(Mosh **out, int B, int k, int w, u64 factor1, u64 factor2, int device, char *err, int errlen);
+int stageG_load(Mosh **out, int B, int k, int w, u64 factor1, u64 factor2, const u32 *index, const u64 *value, const u16 *depth, const u8 *info, u32 size,
+                int device, char *err, int errlen);
+void stageG_destroy(Mosh *m);
+const char *stageG_error(const Mosh *m);
+int stageG_setOption(Mosh *m, const char *name, int64_t v);
+int stageG_add(Mosh *m, const u8 *codes, const u64 *seqStart, u32 nSeq, int skipOdd, u64 seqBase, u64 *nHashes);
+int stageG_scan(Mosh *m, const u8 *codes, const u64 *seqStart, u32 nSeq, int skipOdd, u64 seqBase, u64 *hash, u32 *seq, u32 *pos, u64 cap, u64 *nOut);
+int stageG_merge(Mosh *m, int k2, int w2, u64 factor12, const u64 *value2, const u16 *depth2, const u8 *info2, u32 size2, int *merged);
+int stageG_prune(Mosh *m, int mn, int mx, u32 *before, u32 *after);
+int stageG_setCopy(Mosh *m, int c1, int c2, int cM, int onlyM);
+int stageG_summary(Mosh *m, u32 *hist65536, u32 *copy4);
+void stageG_info(const Mosh *m, int *B, int *k, int *w, u64 *factor1, u64 *factor2, u32 *max, u32 *size);
+int stageG_export(Mosh *m, u64 indexFirst, u64 indexCount, u32 *index, u64 *value, u16 *depth, u8 *info);
+int stageG_lookup(Mosh *m, const u64 *hashes, u64 n, u32 *index, u16 *depth);
+
 }  // namespace h10x

@@ -42,6 +42,59 @@ uint64_t h10x_factor1_from_seed(int32_t seed) {
   return ((uint64_t)(uint32_t)a << 32) | (uint64_t)(uint32_t)b | 1;
 }
 
+void h10x_factors_from_seed(int32_t seed, uint64_t *factor1, uint64_t *factor2) {
+  // moshutils.c:150-151 srandom(s); seqhashCreate: seqhash.c:29 factor1, seqhash.c:31 factor2 — the next two draws of the same private state
+  struct random_data rd; char state[128]; int32_t v[4] = {0, 0, 0, 0};
+  memset(&rd, 0, sizeof rd); memset(state, 0, sizeof state);
+  initstate_r((unsigned)seed, state, sizeof state, &rd);
+  for (int i = 0; i < 4; ++i) random_r(&rd, &v[i]);
+  if (factor1) *factor1 = ((uint64_t)(uint32_t)v[0] << 32) | (uint64_t)(uint32_t)v[1] | 1;
+  if (factor2) *factor2 = ((uint64_t)(uint32_t)v[2] << 32) | (uint64_t)(uint32_t)v[3] | 1;
+}
+
+// ---- mosh sets: thin wrappers over stage_g.hip
+struct h10x_mosh;                                            // == h10x::Mosh
+static inline Mosh *M(h10x_mosh *s) { return reinterpret_cast<Mosh *>(s); }
+static inline const Mosh *M(const h10x_mosh *s) { return reinterpret_cast<const Mosh *>(s); }
+int h10x_mosh_create(h10x_mosh **set, int32_t B, int32_t k, int32_t w, int32_t seed, int device, char *err, int errlen) {
+  if (!set) return -1;
+  uint64_t f1, f2; h10x_factors_from_seed(seed, &f1, &f2);
+  return stageG_create(reinterpret_cast<Mosh **>(set), B, k, w, f1, f2, device, err, errlen);
+}
+int h10x_mosh_load(h10x_mosh **set, int32_t B, int32_t k, int32_t w, uint64_t factor1, uint64_t factor2, const uint32_t *index,
+                   const uint64_t *value, const uint16_t *depth, const uint8_t *info, uint32_t size, int device, char *err, int errlen) {
+  if (!set || !index || !value || !depth || !info) { if (err && errlen > 0) snprintf(err, (size_t)errlen, "h10x_mosh_load: null argument"); return -1; }
+  return stageG_load(reinterpret_cast<Mosh **>(set), B, k, w, factor1, factor2, index, (const u64 *)value, depth, info, size, device, err, errlen);
+}
+void h10x_mosh_destroy(h10x_mosh *s) { stageG_destroy(M(s)); }
+const char *h10x_mosh_error(const h10x_mosh *s) { return stageG_error(M(s)); }
+int h10x_mosh_info(const h10x_mosh *s, h10x_mosh_info_t *o) {
+  if (!s || !o) return -1;
+  memset(o, 0, sizeof *o);
+  int B, k, w; stageG_info(M(s), &B, &k, &w, (u64 *)&o->factor1, (u64 *)&o->factor2, &o->max, &o->size);
+  o->B = B; o->k = k; o->w = w;
+  return 0;
+}
+int h10x_mosh_set_option(h10x_mosh *s, const char *name, int64_t v) { return s && name ? stageG_setOption(M(s), name, v) : -1; }
+int h10x_mosh_add(h10x_mosh *s, const uint8_t *codes, const uint64_t *seqStart, uint32_t nSeq, int skipOdd23, uint64_t seqBase, uint64_t *nHashes) {
+  return s ? stageG_add(M(s), codes, (const u64 *)seqStart, nSeq, skipOdd23, seqBase, (u64 *)nHashes) : -1;
+}
+int h10x_mosh_scan(h10x_mosh *s, const uint8_t *codes, const uint64_t *seqStart, uint32_t nSeq, int skipOdd23, uint64_t seqBase,
+                   uint64_t *hash, uint32_t *seq, uint32_t *pos, uint64_t cap, uint64_t *n) {
+  return s ? stageG_scan(M(s), codes, (const u64 *)seqStart, nSeq, skipOdd23, seqBase, (u64 *)hash, seq, pos, cap, (u64 *)n) : -1;
+}
+int h10x_mosh_merge(h10x_mosh *s, int32_t k2, int32_t w2, uint64_t f12, const uint64_t *value2, const uint16_t *depth2, const uint8_t *info2, uint32_t size2, int *merged) {
+  return s ? stageG_merge(M(s), k2, w2, f12, (const u64 *)value2, depth2, info2, size2, merged) : -1;
+}
+int h10x_mosh_prune(h10x_mosh *s, int32_t mn, int32_t mx, uint32_t *nBefore, uint32_t *nAfter) { return s ? stageG_prune(M(s), mn, mx, nBefore, nAfter) : -1; }
+int h10x_mosh_set_copy(h10x_mosh *s, int32_t c1, int32_t c2, int32_t cM) { return s ? stageG_setCopy(M(s), c1, c2, cM, 0) : -1; }
+int h10x_mosh_set_copy_m(h10x_mosh *s, int32_t cM) { return s ? stageG_setCopy(M(s), 0, 0, cM, 1) : -1; }
+int h10x_mosh_summary(h10x_mosh *s, uint32_t *hist65536, uint32_t *copy4) { return s ? stageG_summary(M(s), hist65536, copy4) : -1; }
+int h10x_mosh_export(h10x_mosh *s, uint64_t indexFirst, uint64_t indexCount, uint32_t *index, uint64_t *value, uint16_t *depth, uint8_t *info) {
+  return s ? stageG_export(M(s), indexFirst, indexCount, index, (u64 *)value, depth, info) : -1;
+}
+int h10x_mosh_lookup(h10x_mosh *s, const uint64_t *hashes, uint64_t n, uint32_t *index, uint16_t *depth) { return s ? stageG_lookup(M(s), (const u64 *)hashes, n, index, depth) : -1; }
+
 static int create_fail(char *err, int errlen, const char *fmt, ...) {
   if (err && errlen > 0) { va_list ap; va_start(ap, fmt); vsnprintf(err, (size_t)errlen, fmt, ap); va_end(ap); }
   return -1;

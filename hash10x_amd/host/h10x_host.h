@@ -106,6 +106,36 @@ int  h10x_host_partition_file(const char *path, uint64_t nRecords, int nParts, u
 
 /* starts loading the library's device code for `device` on a thread of its own (once per process and device; --readFQB joins it before its first kernels) */
 void h10x_host_warm_start(int device);
+/* ---- moshutils-amd (mosh_host.c): sequence files, MSHSTv1 files and the file-level commands over h10x_mosh_* ----
+   Sequence reader (seqio.c:15-190 for FASTA / FASTQ, gzip or plain; needs no device). h10x_seq_open: NULL on failure with msg = the
+   reference's stderr line ("sequence file %s unreadable or empty", "... is unknown type"; empty when the file cannot be opened) and
+   *fatal = 1 where this program stops instead (seqio's binary format). h10x_seq_next reads whole sequences until slabBases bases are
+   in (0 = 2^26): codes = one byte per base (A C G T N, either case -> 0 1 2 3 0), sequence s = codes[seqStart[s] .. seqStart[s+1]);
+   1 = sequences delivered, 0 = end of file, -1 = fatal (h10x_seq_error: the reference's die texts, "bad base 0x.. in FASTQ line n").
+   The arrays of one call stay valid until the call after the next returns. h10x_seq_warning: "incomplete sequence record line n" once
+   the file has ended inside a record (that record is dropped, seqio.c:91-95). */
+typedef struct h10x_seqreader h10x_seqreader;
+h10x_seqreader *h10x_seq_open(const char *path, char *msg, int msglen, int *fatal);
+int  h10x_seq_next(h10x_seqreader *r, uint64_t slabBases, const uint8_t **codes, const uint64_t **seqStart, uint32_t *nSeq);
+const char *h10x_seq_error(const h10x_seqreader *r);
+const char *h10x_seq_warning(const h10x_seqreader *r);
+void h10x_seq_totals(const h10x_seqreader *r, uint64_t *nSeq, uint64_t *bases);
+void h10x_seq_close(h10x_seqreader *r);
+/* == Seqhash as seqhashWrite stores it (seqhash.h:15-22, 72 bytes, no padding holes) */
+typedef struct { int32_t k, w; uint64_t mask; int32_t shift1, shift2; uint64_t factor1, factor2, patternRC[4]; } h10x_seqhash_rec;
+/* a parsed MSHSTv1 file (moshset.c:78-103): index 2^B entries, value / depth / info `size` = max + 1 entries. The reader refuses a
+   file whose entries are not each found through their own probe walk (so the values are distinct: h10x_mosh_merge relies on it). */
+typedef struct { int32_t B; uint32_t size; h10x_seqhash_rec sh; uint32_t *index; uint64_t *value; uint16_t *depth; uint8_t *info; } h10x_moshfile;
+int  h10x_moshfile_read(const char *path, h10x_moshfile *out, char *err, int errlen);
+void h10x_moshfile_free(h10x_moshfile *m);
+void h10x_moshfile_counts(const h10x_moshfile *m, uint32_t *hist65536, uint32_t copy4[4]);
+/* moshsetSummary's text (moshset.c:122-144) from the counts; with max = 0 the line ends without a newline, as in the reference */
+void h10x_mosh_summary_print(FILE *f, int k, int w, int B, uint32_t max, const uint32_t *hist65536, const uint32_t *copy4);
+int  h10x_mosh_set_summary(h10x_mosh *set, FILE *f);
+int  h10x_mosh_set_write(h10x_mosh *set, const char *path, char *err, int errlen);                     /* moshsetWrite */
+/* addSequenceFile (moshutils.c:32-50): 0 = done, 1 = the file could not be opened (msg = line for stderr, may be empty), -1 = fatal */
+int  h10x_mosh_set_add_file(h10x_mosh *set, const char *path, int is10x, uint64_t slabBases, uint64_t *nSeq, uint64_t *totLen, uint64_t *totHash,
+                            char *msg, int msglen, char *warn, int warnlen);
 #ifdef __cplusplus
 }
 #endif

@@ -344,6 +344,63 @@ int  h10x_code_share(h10x_ctx *ctx, const uint32_t *codes, uint32_t nq, uint64_t
 int  h10x_code_explore(h10x_ctx *ctx, int32_t code, int32_t threshold, h10x_code_explore_rep *rep);
 int  h10x_code_crib_counts(h10x_ctx *ctx, const uint32_t *codes, uint32_t n, uint32_t *out);
 
+/* ---- mosh sets (csrc/stage_g.hip): the Moshset object of the reference's moshutils (moshset.h, moshset.c, moshutils.c) ----
+   A second opaque handle beside the context. A set is the probe table index[2^B] (moshsetIndexFind, moshset.c:45-61) and, per index
+   1 .. max in order of first appearance, value (the hash), depth (saturating at 65535) and info (low two bits = copy class 0, 1, 2, M).
+   Every function returns 0 on success; h10x_mosh_error() then holds the message otherwise — the reference's die() text where it
+   would have died ("hashTableSize %u is too small for %u", moshset.c:57). One host thread per set. No CPU fallback. */
+typedef struct h10x_mosh h10x_mosh;
+typedef struct {
+  int32_t  B, k, w, reserved;
+  uint64_t factor1, factor2;    /* seqhashCreate's two multipliers (seqhash.c:29-31); only factor1 hashes, factor2 goes into the file */
+  uint32_t max;                 /* ms->max: number of entries */
+  uint32_t size;                /* ms->size: the per-index arrays hold this many; the entry that makes max reach it dies */
+} h10x_mosh_info_t;
+/* srandom(seed); seqhashCreate: factor1 then factor2, two random() draws each (moshutils.c:150-151, seqhash.c:29-31).
+   factor1 is h10x_factor1_from_seed(seed). */
+void h10x_factors_from_seed(int32_t seed, uint64_t *factor1, uint64_t *factor2);
+/* moshsetCreate(seqhashCreate(k, w), B, 0) after srandom(seed) (moshutils.c:150-152, moshset.c:15-31): an empty set that holds up to
+   2^(B-2) - 2 hashes. B 20..34; a set that does not fit the device fails with the bytes it asked for. */
+int  h10x_mosh_create(h10x_mosh **set, int32_t B, int32_t k, int32_t w, int32_t seed, int device, char *err, int errlen);
+/* the state moshsetRead leaves (moshset.c:89-103) from the arrays of a parsed MSHSTv1 file: index 2^B entries, value / depth / info
+   `size` = max + 1 entries. The set is FULL, as in the reference (its arrays are sized to the file): the first new hash dies. */
+int  h10x_mosh_load(h10x_mosh **set, int32_t B, int32_t k, int32_t w, uint64_t factor1, uint64_t factor2, const uint32_t *index,
+                    const uint64_t *value, const uint16_t *depth, const uint8_t *info, uint32_t size, int device, char *err, int errlen);
+void h10x_mosh_destroy(h10x_mosh *set);
+const char *h10x_mosh_error(const h10x_mosh *set);
+int  h10x_mosh_info(const h10x_mosh *set, h10x_mosh_info_t *out);
+/* "mosh_slab": bases per device batch of h10x_mosh_add / h10x_mosh_scan (0 = default 2^26; a longer sequence goes alone). Results
+   do not depend on it. Unknown name: -1. */
+int  h10x_mosh_set_option(h10x_mosh *set, const char *name, int64_t value);
+/* addSequence over sequences (moshutils.c:19-30, 41-45): codes = one byte per base (0..3, N -> 0), sequence s =
+   codes[seqStart[s] .. seqStart[s+1]). Every mosh occurrence is found or added in file order and its depth incremented.
+   skipOdd23 != 0 is -x: the 1st, 3rd, ... sequence (counting seqBase sequences before this call) starts 23 bases in; one shorter
+   than 23 fails (the reference aborts on an assert). *nHashes = occurrences. */
+int  h10x_mosh_add(h10x_mosh *set, const uint8_t *codes, const uint64_t *seqStart, uint32_t nSeq, int skipOdd23, uint64_t seqBase,
+                   uint64_t *nHashes);
+/* the moshes themselves, as moshRCiterator / moshRCnext yield them (seqhash.c:154-195), in order: hash, sequence number (0-based),
+   position of the k-mer. The set is not changed. *n = how many there are; the first min(cap, *n) are written (NULL = skip). */
+int  h10x_mosh_scan(h10x_mosh *set, const uint8_t *codes, const uint64_t *seqStart, uint32_t nSeq, int skipOdd23, uint64_t seqBase,
+                    uint64_t *hash, uint32_t *seq, uint32_t *pos, uint64_t cap, uint64_t *n);
+/* moshsetMerge (moshset.c:105-120) of another set given by its per-index arrays (size2 = its max + 1 entries, entry 0 unused):
+   *merged = 0 and nothing done if k, w or factor1 differ (the caller prints the reference's "incompatible" line). value2[1 ..] must be
+   distinct, as they are in any set (h10x_moshfile_read checks a file's); repeated values are undefined here. */
+int  h10x_mosh_merge(h10x_mosh *set, int32_t k2, int32_t w2, uint64_t factor1_2, const uint64_t *value2, const uint16_t *depth2,
+                     const uint8_t *info2, uint32_t size2, int *merged);
+/* moshsetDepthPrune (moshset.c:63-76): keeps depth >= min && (!max || depth < max), renumbers, rebuilds the table */
+int  h10x_mosh_prune(h10x_mosh *set, int32_t min, int32_t max, uint32_t *nBefore, uint32_t *nAfter);
+/* -s (moshutils.c:170-178) and -sM (moshutils.c:181-184) */
+int  h10x_mosh_set_copy(h10x_mosh *set, int32_t copy1min, int32_t copy2min, int32_t copyMmin);
+int  h10x_mosh_set_copy_m(h10x_mosh *set, int32_t copyMmin);
+/* what moshsetSummary and depthHistogram count (moshset.c:127-133, moshutils.c:52-62): hist[65536] by depth, copy[4] by class */
+int  h10x_mosh_summary(h10x_mosh *set, uint32_t *hist65536, uint32_t *copy4);
+/* copy-out for moshsetWrite (moshset.c:78-87): entries [indexFirst, indexFirst + indexCount) of the table, and value / depth / info
+   with max + 1 entries each (NULL = skip). value[0] is 0 (uninitialised heap in the reference). */
+int  h10x_mosh_export(h10x_mosh *set, uint64_t indexFirst, uint64_t indexCount, uint32_t *index, uint64_t *value, uint16_t *depth,
+                      uint8_t *info);
+/* moshsetIndexFind(ms, hash, FALSE) per hash (reportDepths, moshutils.c:64-76): index (0 = absent) and depth (0 when absent) */
+int  h10x_mosh_lookup(h10x_mosh *set, const uint64_t *hashes, uint64_t n, uint32_t *index, uint16_t *depth);
+
 /* ---- device memory plumbing for callers that keep the input resident in HBM (bench, pipelines) ----
    plain hipMalloc / hipMemcpy / hipDeviceSynchronize on `device`; return NULL / non-zero on failure */
 void *h10x_device_malloc(int device, uint64_t bytes);
