@@ -62,6 +62,22 @@ class _MoshFile(ctypes.Structure):
                 ("depth", ctypes.c_void_p), ("info", ctypes.c_void_p)]
 
 
+class _ReadsetInfo(ctypes.Structure):
+    _fields_ = [("nReads", ctypes.c_uint32), ("dim", ctypes.c_uint32), ("totHit", ctypes.c_uint64)]
+
+
+class _ReadsetFile(ctypes.Structure):
+    _fields_ = [("totHit", ctypes.c_uint64), ("dim", ctypes.c_uint32), ("max", ctypes.c_uint32), ("reads", ctypes.c_void_p), ("hit", ctypes.c_void_p),
+                ("dx", ctypes.c_void_p)]
+
+
+# h10x_read_t (the 72-byte Read of the RSMSHv2 file) and h10x_overlap_t (include/h10x.h)
+READ_DTYPE = np.dtype([("len", "<i4"), ("nHit", "<i4"), ("hitPtr", "<u8"), ("dxPtr", "<u8"), ("bad", "u1"), ("otherFlags", "u1"), ("pad1", "<u2"), ("nMiss", "<i4"),
+                       ("contained", "<i4"), ("nCopy", "<i4", (4,)), ("pad2", "<u4", (4,)), ("tail", "<u4")])
+OVERLAP_DTYPE = np.dtype([("iy", "<u4"), ("nHit", "<i4"), ("offset", "<i4"), ("isPlus", "u1"), ("isBad", "u1"), ("visited", "u1"), ("pad", "u1"), ("nPlus", "<i4"),
+                          ("nMinus", "<i4"), ("d", "<f8"), ("sd", "<f8"), ("sumZ", "<i8"), ("sumZ2", "<i8")])
+assert READ_DTYPE.itemsize == 72 and OVERLAP_DTYPE.itemsize == 56
+
 _BLOCK_REP = np.dtype([("nGood", "<u4"), ("nClusHash", "<u4"), ("nClusRead", "<u4"), ("reserved", "<u4")])
 _CLUSTER_REP = np.dtype([("n", "<u4"), ("nRead", "<u4"), ("nt", "<u4", (5,)), ("nBad", "<u4"), ("chr", "<i2"), ("pMin", "<u2"), ("pMax", "<u2"), ("nOtherListed", "<u2"), ("other", "<u4", (10,))])
 assert _BLOCK_REP.itemsize == 16 and _CLUSTER_REP.itemsize == 80       # h10x_block_rep / h10x_cluster_rep (include/h10x.h)
@@ -198,6 +214,24 @@ def load_native():
     host.h10x_moshfile_free.restype = None; host.h10x_moshfile_free.argtypes = [ctypes.POINTER(_MoshFile)]
     host.h10x_mosh_set_write.argtypes = [vp, cs, cs, ci]
     host.h10x_mosh_set_add_file.argtypes = [vp, cs, ci, cu64, ctypes.POINTER(cu64), ctypes.POINTER(cu64), ctypes.POINTER(cu64), cs, ci, cs, ci]
+    # readsets (csrc/stage_h.hip, host/asm_host.c)
+    hip.h10x_readset_create.argtypes = [pvp, vp]
+    hip.h10x_readset_load.argtypes = [pvp, vp, vp, cu32, cu32, vp, vp]
+    hip.h10x_readset_destroy.restype = None; hip.h10x_readset_destroy.argtypes = [vp]
+    hip.h10x_readset_error.restype = cs; hip.h10x_readset_error.argtypes = [vp]
+    hip.h10x_readset_add.argtypes = [vp, vp, vp, cu32]
+    hip.h10x_readset_info.argtypes = [vp, ctypes.POINTER(_ReadsetInfo)]
+    hip.h10x_readset_export.argtypes = [vp, pvp, pvp, pvp, pvp]
+    hip.h10x_readset_overlap_cap.argtypes = [vp, cu32, ctypes.POINTER(cu32)]
+    hip.h10x_readset_overlaps.argtypes = [vp, cu32, vp, cu32, ctypes.POINTER(cu32), vp]
+    hip.h10x_readset_mark_bad.argtypes = [vp, vp]
+    hip.h10x_readset_mark_contained.argtypes = [vp, ctypes.POINTER(ci32), ctypes.POINTER(ci32), ctypes.POINTER(cu64)]
+    hip.h10x_readset_stats_sums.argtypes = [vp, vp]
+    host.h10x_readsetfile_read.argtypes = [cs, cu32, ctypes.POINTER(_ReadsetFile), cs, ci]
+    host.h10x_readsetfile_free.restype = None; host.h10x_readsetfile_free.argtypes = [ctypes.POINTER(_ReadsetFile)]
+    host.h10x_readsetfile_write.argtypes = [cs, cu64, cu32, vp, cu32, vp, vp, vp, cs, ci]
+    host.h10x_readset_write_file.argtypes = [vp, cs, cs, ci]
+    host.h10x_readset_add_file.argtypes = [vp, cs, cu64, cs, ci, cs, ci]
     if hip.h10x_abi_version() != ABI_VERSION:
         raise RuntimeError("libh10x_hip.so speaks ABI %d, hash10x_amd/__init__.py was written for %d (include/h10x.h H10X_ABI_VERSION): rebuild with "
                            "`python -c 'import __graft_entry__ as g; g.build()'`" % (hip.h10x_abi_version(), ABI_VERSION))
@@ -932,3 +966,136 @@ def mosh_scan(codes, seq_start, k, w, seed, device=0):
         return s.scan(codes, seq_start)
     finally:
         s.close()
+
+
+# ---- readsets: the reference's moshasm (moshasm.c) on the GPU — csrc/stage_h.hip, host/asm_host.c --------------------------------
+def read_readset_file(path, set_max):
+    """A RSMSHv2 file through the host reader's checks (no device needed): dict with totHit, dim, reads (READ_DTYPE), hit, dx."""
+    _, host = load_native()
+    r = _ReadsetFile(); err = ctypes.create_string_buffer(512)
+    if host.h10x_readsetfile_read(os.fsencode(path), int(set_max), ctypes.byref(r), err, 512):
+        raise Hash10xError(err.value.decode())
+    try:
+        return dict(totHit=r.totHit, dim=r.dim, reads=_from_ptr(r.reads, READ_DTYPE, r.max), hit=_from_ptr(r.hit, np.uint32, r.totHit), dx=_from_ptr(r.dx, np.uint16, r.totHit))
+    finally:
+        host.h10x_readsetfile_free(ctypes.byref(r))
+
+
+def write_readset_file(path, tot_hit, dim, reads, hit_start, hit, dx):
+    _, host = load_native()
+    reads = np.ascontiguousarray(reads, READ_DTYPE); hs = np.ascontiguousarray(hit_start, np.uint64)
+    hit = np.ascontiguousarray(hit, np.uint32); dx = np.ascontiguousarray(dx, np.uint16)
+    assert len(hs) == len(reads) + 1 and int(hs[-1]) <= len(hit) and len(hit) == len(dx)
+    err = ctypes.create_string_buffer(512)
+    if host.h10x_readsetfile_write(os.fsencode(path), int(tot_hit), int(dim), reads.ctypes.data, len(reads), hs.ctypes.data, hit.ctypes.data, dx.ctypes.data, err, 512):
+        raise Hash10xError(err.value.decode())
+
+
+class ReadSet:
+    """The reference's Readset over a MoshSet on one MI355X: -f / -r / -w / -S / -o1 / -b / -c of moshasm as methods. The readset borrows
+    the set: keep the set open while the readset lives. A new ReadSet zeroes the set's depths, which its reads then rebuild."""
+
+    def __init__(self, moshset, _handle=None):
+        self._hip, self._host = load_native()
+        self.ms = moshset
+        self.h = _handle
+        if self.h is None:
+            h = ctypes.c_void_p()
+            if self._hip.h10x_readset_create(ctypes.byref(h), moshset.h):
+                raise Hash10xError(self._hip.h10x_mosh_error(moshset.h).decode())
+            self.h = h
+
+    @classmethod
+    def from_arrays(cls, moshset, reads, dim, hit, dx):
+        hip, _ = load_native()
+        reads = np.ascontiguousarray(reads, READ_DTYPE); hit = np.ascontiguousarray(hit, np.uint32); dx = np.ascontiguousarray(dx, np.uint16)
+        h = ctypes.c_void_p()
+        if hip.h10x_readset_load(ctypes.byref(h), moshset.h, reads.ctypes.data, len(reads), int(dim), hit.ctypes.data, dx.ctypes.data):
+            raise Hash10xError(hip.h10x_mosh_error(moshset.h).decode())
+        rs = cls(moshset, _handle=h)
+        rs.export()                                             # invBuild: the set's depths must be this readset's
+        return rs
+
+    @classmethod
+    def read(cls, stem, device=0):
+        """-r: <stem>.mosh and <stem>.readset; returns the ReadSet (its set is .ms)"""
+        f = read_mosh_file(stem + ".mosh")
+        r = read_readset_file(stem + ".readset", f["size"] - 1)
+        ms = MoshSet.from_arrays(f["B"], f["k"], f["w"], f["factor1"], f["factor2"], f["index"], f["value"], f["depth"], f["info"], device)
+        return cls.from_arrays(ms, r["reads"], r["dim"], r["hit"], r["dx"])
+
+    def close(self):
+        if getattr(self, "h", None):
+            self._hip.h10x_readset_destroy(self.h)
+        self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _chk(self, rc):
+        if rc:
+            raise Hash10xError(self._hip.h10x_readset_error(self.h).decode())
+
+    def info(self):
+        i = _ReadsetInfo()
+        self._chk(self._hip.h10x_readset_info(self.h, ctypes.byref(i)))
+        return i
+
+    def add(self, codes, seq_start):
+        """the reads of -f from memory, appended in order"""
+        c, s = MoshSet._seqs(codes, seq_start)
+        self._chk(self._hip.h10x_readset_add(self.h, c.ctypes.data, s.ctypes.data, len(s) - 1))
+
+    def add_file(self, path, slab=0):
+        """-f: returns the reader's warning text"""
+        msg = ctypes.create_string_buffer(512); warn = ctypes.create_string_buffer(256)
+        rc = self._host.h10x_readset_add_file(self.h, os.fsencode(path), int(slab), msg, 512, warn, 256)
+        if rc > 0:
+            raise Hash10xError((msg.value.decode() + "\n" if msg.value else "") + "failed to open sequence file %s" % path)
+        if rc < 0:
+            raise Hash10xError(msg.value.decode())
+        return warn.value.decode()
+
+    def export(self):
+        """(reads as READ_DTYPE records, hit_start uint64, hit uint32, dx uint16): what -w stores"""
+        i = self.info()
+        r, s, h, d = ctypes.c_void_p(), ctypes.c_void_p(), ctypes.c_void_p(), ctypes.c_void_p()
+        self._chk(self._hip.h10x_readset_export(self.h, ctypes.byref(r), ctypes.byref(s), ctypes.byref(h), ctypes.byref(d)))
+        return (_from_ptr(r.value, READ_DTYPE, i.nReads), _from_ptr(s.value, np.uint64, i.nReads + 1), _from_ptr(h.value, np.uint32, i.totHit),
+                _from_ptr(d.value, np.uint16, i.totHit))
+
+    def write(self, stem):
+        """-w: <stem>.mosh and <stem>.readset"""
+        self.ms.write(stem + ".mosh")
+        err = ctypes.create_string_buffer(512)
+        if self._host.h10x_readset_write_file(self.h, os.fsencode(stem + ".readset"), err, 512):
+            raise Hash10xError(err.value.decode())
+
+    def stats(self):
+        """the sums of -S: dict with reads (records), totHit and, per copy class, nCopy, hitCopy, hit2Copy, depthCopy of the set"""
+        s = np.zeros(16, np.uint64)
+        self._chk(self._hip.h10x_readset_stats_sums(self.h, s.ctypes.data))
+        return dict(reads=self.export()[0], totHit=self.info().totHit, nCopy=s[0:4], hitCopy=s[4:8], hit2Copy=s[8:12], depthCopy=s[12:16])
+
+    def overlaps(self, ix):
+        """findOverlaps for read ix, flags of ix updated as it does: (array of OVERLAP_DTYPE, nRepeat, nGood, nBad)"""
+        cap = ctypes.c_uint32(0); n = ctypes.c_uint32(0)
+        self._chk(self._hip.h10x_readset_overlap_cap(self.h, int(ix), ctypes.byref(cap)))
+        out = np.zeros(cap.value, OVERLAP_DTYPE); cnt = np.zeros(3, np.int32)
+        self._chk(self._hip.h10x_readset_overlaps(self.h, int(ix), out.ctypes.data, cap.value, ctypes.byref(n), cnt.ctypes.data))
+        return out[:n.value], int(cnt[0]), int(cnt[1]), int(cnt[2])
+
+    def mark_bad(self):
+        """-b: the reads each of the three passes marks"""
+        f = np.zeros(3, np.int32)
+        self._chk(self._hip.h10x_readset_mark_bad(self.h, f.ctypes.data))
+        return [int(x) for x in f]
+
+    def mark_contained(self):
+        """-c: (contained, not contained, total length of the reads not contained)"""
+        a, b, t = ctypes.c_int32(0), ctypes.c_int32(0), ctypes.c_uint64(0)
+        self._chk(self._hip.h10x_readset_mark_contained(self.h, ctypes.byref(a), ctypes.byref(b), ctypes.byref(t)))
+        return a.value, b.value, t.value

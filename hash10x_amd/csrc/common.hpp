@@ -463,5 +463,21 @@ int stageG_summary(Mosh *m, u32 *hist65536, u32 *copy4);
 void stageG_info(const Mosh *m, int *B, int *k, int *w, u64 *factor1, u64 *factor2, u32 *max, u32 *size);
 int stageG_export(Mosh *m, u64 indexFirst, u64 indexCount, u32 *index, u64 *value, u16 *depth, u8 *info);
 int stageG_lookup(Mosh *m, const u64 *hashes, u64 n, u32 *index, u16 *depth);
+// readsets over a mosh set (stage_h.hip)
+struct ReadSet;
+int stageH_create(ReadSet **out, Mosh *m);
+int stageH_load(ReadSet **out, Mosh *m, const h10x_read_t *reads, u32 nReads, u32 dim, const u32 *hit, const u16 *dx);
+void stageH_destroy(ReadSet *rs);
+const char *stageH_error(const ReadSet *rs);
+int stageH_oom(Mosh *m);
+Mosh *stageH_set(ReadSet *rs);
+int stageH_add(ReadSet *rs, const u8 *codes, const u64 *seqStart, u32 nSeq);
+int stageH_info(ReadSet *rs, h10x_readset_info_t *out);
+int stageH_export(ReadSet *rs, const h10x_read_t **reads, const u64 **hitStart, const u32 **hit, const u16 **dx);
+int stageH_overlapCap(ReadSet *rs, u32 ix, u32 *cap);
+int stageH_overlaps(ReadSet *rs, u32 ix, h10x_overlap_t *out, u32 cap, u32 *nOut, int32_t counts[3]);
+int stageH_markBad(ReadSet *rs, int32_t found[3]);
+int stageH_markContained(ReadSet *rs, int32_t *nContained, int32_t *nNot, u64 *totLen);
+int stageH_statsSums(ReadSet *rs, u64 out[16]);
 
 }  // namespace h10x

@@ -5,6 +5,7 @@
 #include <cstdlib>
 #include <ctime>
 #include <new>
+#include <stdexcept>
 
 using namespace h10x;
 
@@ -94,6 +95,45 @@ int h10x_mosh_export(h10x_mosh *s, uint64_t indexFirst, uint64_t indexCount, uin
   return s ? stageG_export(M(s), indexFirst, indexCount, index, (u64 *)value, depth, info) : -1;
 }
 int h10x_mosh_lookup(h10x_mosh *s, const uint64_t *hashes, uint64_t n, uint32_t *index, uint16_t *depth) { return s ? stageG_lookup(M(s), (const u64 *)hashes, n, index, depth) : -1; }
+
+// ---- readsets: thin wrappers over stage_h.hip; the host vectors' std::bad_alloc stops here and becomes the error text
+struct h10x_readset;                                         // == h10x::ReadSet
+static inline ReadSet *RS(h10x_readset *s) { return reinterpret_cast<ReadSet *>(s); }
+extern "C++" {
+template <typename F> static int rsGuard(Mosh *m, F &&f) {
+  try { return f(); } catch (const std::bad_alloc &) { return stageH_oom(m); } catch (const std::length_error &) { return stageH_oom(m); }
+}
+}
+int h10x_readset_create(h10x_readset **rs, h10x_mosh *set) {
+  if (!rs || !set) return -1;
+  return rsGuard(M(set), [&] { return stageH_create(reinterpret_cast<ReadSet **>(rs), M(set)); });
+}
+int h10x_readset_load(h10x_readset **rs, h10x_mosh *set, const h10x_read_t *reads, uint32_t nReads, uint32_t dim, const uint32_t *hit, const uint16_t *dx) {
+  if (!rs || !set) return -1;
+  return rsGuard(M(set), [&] { return stageH_load(reinterpret_cast<ReadSet **>(rs), M(set), reads, nReads, dim, hit, dx); });
+}
+void h10x_readset_destroy(h10x_readset *rs) { stageH_destroy(RS(rs)); }
+const char *h10x_readset_error(const h10x_readset *rs) { return stageH_error(reinterpret_cast<const ReadSet *>(rs)); }
+int h10x_readset_add(h10x_readset *rs, const uint8_t *codes, const uint64_t *seqStart, uint32_t nSeq) {
+  return rs ? rsGuard(stageH_set(RS(rs)), [&] { return stageH_add(RS(rs), codes, (const u64 *)seqStart, nSeq); }) : -1;
+}
+int h10x_readset_info(h10x_readset *rs, h10x_readset_info_t *out) { return rs && out ? stageH_info(RS(rs), out) : -1; }
+int h10x_readset_export(h10x_readset *rs, const h10x_read_t **reads, const uint64_t **hitStart, const uint32_t **hit, const uint16_t **dx) {
+  return rs ? rsGuard(stageH_set(RS(rs)), [&] { return stageH_export(RS(rs), reads, (const u64 **)hitStart, hit, dx); }) : -1;
+}
+int h10x_readset_overlap_cap(h10x_readset *rs, uint32_t ix, uint32_t *cap) {
+  return rs && cap ? rsGuard(stageH_set(RS(rs)), [&] { return stageH_overlapCap(RS(rs), ix, cap); }) : -1;
+}
+int h10x_readset_overlaps(h10x_readset *rs, uint32_t ix, h10x_overlap_t *out, uint32_t cap, uint32_t *n, int32_t counts3[3]) {
+  return rs ? rsGuard(stageH_set(RS(rs)), [&] { return stageH_overlaps(RS(rs), ix, out, cap, n, counts3); }) : -1;
+}
+int h10x_readset_mark_bad(h10x_readset *rs, int32_t found3[3]) { return rs ? rsGuard(stageH_set(RS(rs)), [&] { return stageH_markBad(RS(rs), found3); }) : -1; }
+int h10x_readset_mark_contained(h10x_readset *rs, int32_t *nContained, int32_t *nNotContained, uint64_t *totLen) {
+  return rs ? rsGuard(stageH_set(RS(rs)), [&] { return stageH_markContained(RS(rs), nContained, nNotContained, (u64 *)totLen); }) : -1;
+}
+int h10x_readset_stats_sums(h10x_readset *rs, uint64_t out16[16]) {
+  return rs && out16 ? rsGuard(stageH_set(RS(rs)), [&] { return stageH_statsSums(RS(rs), (u64 *)out16); }) : -1;
+}
 
 static int create_fail(char *err, int errlen, const char *fmt, ...) {
   if (err && errlen > 0) { va_list ap; va_start(ap, fmt); vsnprintf(err, (size_t)errlen, fmt, ap); va_end(ap); }

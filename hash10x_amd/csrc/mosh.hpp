@@ -1,0 +1,41 @@
+// mosh.hpp — the mosh set object shared by stage_g.hip (moshutils) and stage_h.hip (moshasm's readsets over a set)
+#pragma once
+#include "common.hpp"
+
+namespace h10x {
+
+constexpr int MOSH_RUN = 64;                                 // k-mer start positions per lane
+constexpr int MOSH_X_SKIP = 23;                              // moshutils.c:43: barcode + spacer of the first read of a 10x pair
+constexpr u64 MOSH_SLAB_DEFAULT = (u64)1 << 26;              // bases per batch
+
+struct Mosh {
+  Ctx c;                                                     // stream, error text, block cache scope; c.hashIndex = index[], c.hashValue = value[]
+  int B = 0, k = 0, w = 0; u64 factor1 = 0, factor2 = 0;
+  u32 size = 0, max = 0;                                     // ms->size (capacity of the per-index arrays: max stays below it), ms->max
+  DevBuf<u16> depth; DevBuf<u8> info; DevBuf<u32> acc;
+  u64 slab = MOSH_SLAB_DEFAULT;
+};
+
+static inline int moshEnter(Mosh *m) {
+  Ctx &c = m->c;
+  if (hipSetDevice(c.device) != hipSuccess) return c.fail("hipSetDevice(%d) failed", c.device);
+  AllocScope::stream() = c.stream; AllocScope::device() = c.device;
+  DevCache::noteStream(c.device, c.stream);
+  c.pendingReads.clear(); c.mailUsed = 0; c.mailDirect = false;
+  return 0;
+}
+
+// batches = as many whole sequences as fit the slab; a longer sequence goes alone
+template <typename F> static int moshBatches(Mosh *m, const u64 *seqStart, u32 nSeq, F &&f) {
+  u32 s = 0;
+  while (s < nSeq) {
+    u32 e = s + 1;
+    while (e < nSeq && seqStart[e + 1] - seqStart[s] <= m->slab) ++e;
+    H10X_TRY(f(s, e - s));
+    s = e;
+  }
+  return 0;
+}
+
+
+}  // namespace h10x

@@ -136,6 +136,22 @@ int  h10x_mosh_set_write(h10x_mosh *set, const char *path, char *err, int errlen
 /* addSequenceFile (moshutils.c:32-50): 0 = done, 1 = the file could not be opened (msg = line for stderr, may be empty), -1 = fatal */
 int  h10x_mosh_set_add_file(h10x_mosh *set, const char *path, int is10x, uint64_t slabBases, uint64_t *nSeq, uint64_t *totLen, uint64_t *totHash,
                             char *msg, int msglen, char *warn, int warnlen);
+/* ---- moshasm-amd (asm_host.c): the RSMSHv2 file, the text reports and the file-level commands over h10x_readset_* ----
+   a parsed RSMSHv2 file (moshasm.c:84-123): `max` records, hit / dx of all reads back to back. The reader checks the header, the record
+   size, max <= dim, that the hit counts fit the file and that every mosh index lies in 1 .. setMax; it fails with a message. */
+typedef struct { uint64_t totHit; uint32_t dim, max; h10x_read_t *reads; uint32_t *hit; uint16_t *dx; } h10x_readsetfile;
+int  h10x_readsetfile_read(const char *path, uint32_t setMax, h10x_readsetfile *out, char *err, int errlen);
+void h10x_readsetfile_free(h10x_readsetfile *r);
+int  h10x_readsetfile_write(const char *path, uint64_t totHit, uint32_t dim, const h10x_read_t *reads, uint32_t nReads, const uint64_t *hitStart,
+                            const uint32_t *hit, const uint16_t *dx, char *err, int errlen);
+int  h10x_readset_write_file(h10x_readset *rs, const char *path, char *err, int errlen);                /* the .readset half of readsetWrite */
+/* the loop of readsetFileRead: 0 = done, 1 = the file could not be opened (msg = line for stderr, may be empty), -1 = fatal */
+int  h10x_readset_add_file(h10x_readset *rs, const char *path, uint64_t slabBases, char *msg, int msglen, char *warn, int warnlen);
+int  h10x_readset_print_stats(h10x_readset *rs, h10x_mosh *set, FILE *f, char *err, int errlen);        /* 1 = empty readset */
+int  h10x_readset_print_overlaps(h10x_readset *rs, uint32_t ix, int level, FILE *f, h10x_overlap_t **olap, uint32_t *nOlap, char *err, int errlen);
+int  h10x_readset_print_pair(h10x_readset *rs, h10x_mosh *set, uint32_t ix, uint32_t iy, FILE *f, char *err, int errlen);
+int  h10x_readset_print_assembly(h10x_readset *rs, h10x_mosh *set, uint32_t ix, FILE *f, FILE *fstd, char *err, int errlen);
+
 #ifdef __cplusplus
 }
 #endif

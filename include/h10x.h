@@ -401,6 +401,58 @@ int  h10x_mosh_export(h10x_mosh *set, uint64_t indexFirst, uint64_t indexCount, 
 /* moshsetIndexFind(ms, hash, FALSE) per hash (reportDepths, moshutils.c:64-76): index (0 = absent) and depth (0 when absent) */
 int  h10x_mosh_lookup(h10x_mosh *set, const uint64_t *hashes, uint64_t n, uint32_t *index, uint16_t *depth);
 
+/* ---- readsets (csrc/stage_h.hip): the Readset object of the reference's moshasm (moshasm.c) over a mosh set ----
+   Long reads kept as their mosh hits only: per read the set indices hit, in position order (top bit = the forward hash was strictly
+   the smaller, seqhash.c:67), and the 16-bit distance of each hit to the one before it. Read 0 is the reference's burned entry. The
+   readset borrows the set: the set must outlive it and must not be changed by other calls while the readset lives. The pairwise
+   classification of findOverlaps (moshasm.c:286-365) is computed once per readset, for every directed pair of reads that share a
+   first-occurrence copy-1 mosh, and kept on the device; the calls below that depend on the bad flags (moshasm.c:325, 367-371) resolve
+   them in read order on the host. Every function returns 0 on success; h10x_readset_error() holds the message otherwise. */
+typedef struct h10x_readset h10x_readset;
+typedef struct {              /* the 72-byte Read of moshasm.c:31-53 as readsetWrite stores it; the two pointers are always 0 here */
+  int32_t  len, nHit;
+  uint64_t hitPtr, dxPtr;
+  uint8_t  bad, otherFlags;   /* bad: bit 0 repeat, 1 order10, 2 order1, 3 no_match, 4 low_hit, 5 low_copy1 */
+  uint16_t pad1;
+  int32_t  nMiss, contained;
+  int32_t  nCopy[4];
+  uint32_t pad2[4];
+  uint32_t tail;
+} h10x_read_t;
+typedef struct {              /* one Overlap of findOverlaps' array (moshasm.c:264-270) with what its RH line prints */
+  uint32_t iy; int32_t nHit, offset;
+  uint8_t  isPlus, isBad, visited, pad;   /* visited = 0: y was bad when x was looked at, or nHit < 3 (the array's last entry) */
+  int32_t  nPlus, nMinus;
+  double   d, sd;             /* d /= nHit ; sqrt(d2 / nHit - d * d) (moshasm.c:355) from the device's integer sums */
+  int64_t  sumZ, sumZ2;
+} h10x_overlap_t;
+typedef struct { uint32_t nReads /* arrayMax: read 0 included */, dim /* of the reference's reads array */; uint64_t totHit; } h10x_readset_info_t;
+/* readsetCreate + the start of readsetFileRead (moshasm.c:65-73, 132): an empty readset; the set's depth[] is zeroed, to be rebuilt
+   from the sequences added */
+int  h10x_readset_create(h10x_readset **rs, h10x_mosh *set);
+/* the loop of readsetFileRead (moshasm.c:135-160) over sequences as for h10x_mosh_add; a read with more than 65534 hits is refused */
+int  h10x_readset_add(h10x_readset *rs, const uint8_t *codes, const uint64_t *seqStart, uint32_t nSeq);
+/* readsetRead's state (moshasm.c:102-123) from the arrays of a parsed RSMSHv2 file: nReads records, hit / dx of all reads back to
+   back in read order. The set's depth[] is kept and must be the one this readset gave it: checked (invBuild, moshasm.c:232-260) */
+int  h10x_readset_load(h10x_readset **rs, h10x_mosh *set, const h10x_read_t *reads, uint32_t nReads, uint32_t dim, const uint32_t *hit,
+                       const uint16_t *dx);
+void h10x_readset_destroy(h10x_readset *rs);                                         /* readsetDestroy (moshasm.c:75-82) */
+const char *h10x_readset_error(const h10x_readset *rs);
+int  h10x_readset_info(h10x_readset *rs, h10x_readset_info_t *out);
+/* what readsetWrite stores (moshasm.c:84-100), nCopy as invBuild leaves it: pointers into the object, valid until the next call that
+   changes it; hitStart[i] .. hitStart[i + 1] are read i's entries of hit / dx */
+int  h10x_readset_export(h10x_readset *rs, const h10x_read_t **reads, const uint64_t **hitStart, const uint32_t **hit, const uint16_t **dx);
+/* findOverlaps (rs, read ix, ..) (moshasm.c:286-384): its side effects on the flags of read ix, the array it returns (at most
+   h10x_readset_overlap_cap(rs, ix) entries, sorted by descending nHit, ties in the order first met) and nRepeat, nGood, nBad */
+int  h10x_readset_overlap_cap(h10x_readset *rs, uint32_t ix, uint32_t *cap);
+int  h10x_readset_overlaps(h10x_readset *rs, uint32_t ix, h10x_overlap_t *out, uint32_t cap, uint32_t *n, int32_t counts3[3]);
+/* markBadReads (moshasm.c:436-461): found3 = the reads each of the three passes marks */
+int  h10x_readset_mark_bad(h10x_readset *rs, int32_t found3[3]);
+/* markContained (moshasm.c:471-497) */
+int  h10x_readset_mark_contained(h10x_readset *rs, int32_t *nContained, int32_t *nNotContained, uint64_t *totLenNotContained);
+/* the per-class sums of readsetStats' last line (moshasm.c:216-224): nCopy[4], hitCopy[4], hit2Copy[4], depthCopy[4] */
+int  h10x_readset_stats_sums(h10x_readset *rs, uint64_t out16[16]);
+
 /* ---- device memory plumbing for callers that keep the input resident in HBM (bench, pipelines) ----
    plain hipMalloc / hipMemcpy / hipDeviceSynchronize on `device`; return NULL / non-zero on failure */
 void *h10x_device_malloc(int device, uint64_t bytes);
