@@ -66,6 +66,10 @@ class _ReadsetInfo(ctypes.Structure):
     _fields_ = [("nReads", ctypes.c_uint32), ("dim", ctypes.c_uint32), ("totHit", ctypes.c_uint64)]
 
 
+class _RefmapInfo(ctypes.Structure):
+    _fields_ = [("size", ctypes.c_uint32), ("max", ctypes.c_uint32), ("setMax", ctypes.c_uint32), ("packed", ctypes.c_int32)]
+
+
 class _ReadsetFile(ctypes.Structure):
     _fields_ = [("totHit", ctypes.c_uint64), ("dim", ctypes.c_uint32), ("max", ctypes.c_uint32), ("reads", ctypes.c_void_p), ("hit", ctypes.c_void_p),
                 ("dx", ctypes.c_void_p)]
@@ -232,6 +236,17 @@ def load_native():
     host.h10x_readsetfile_write.argtypes = [cs, cu64, cu32, vp, cu32, vp, vp, vp, cs, ci]
     host.h10x_readset_write_file.argtypes = [vp, cs, cs, ci]
     host.h10x_readset_add_file.argtypes = [vp, cs, cu64, cs, ci, cs, ci]
+    # reference maps (csrc/stage_i.hip)
+    hip.h10x_refmap_create.argtypes = [pvp, vp, cu32]
+    hip.h10x_refmap_load.argtypes = [pvp, vp, vp, vp, vp, vp, vp, vp, cu32, cu32]
+    hip.h10x_refmap_destroy.restype = None; hip.h10x_refmap_destroy.argtypes = [vp]
+    hip.h10x_refmap_error.restype = cs; hip.h10x_refmap_error.argtypes = [vp]
+    hip.h10x_refmap_info.argtypes = [vp, ctypes.POINTER(_RefmapInfo)]
+    hip.h10x_refmap_add.argtypes = [vp, vp, vp, cu32, cu32, ctypes.POINTER(cu64)]
+    hip.h10x_refmap_pack.argtypes = [vp, ctypes.POINTER(cu32), ctypes.POINTER(cu32), ctypes.POINTER(cu32)]
+    hip.h10x_refmap_export.argtypes = [vp, pvp, pvp, pvp, pvp, pvp, pvp]
+    hip.h10x_refmap_query.argtypes = [vp, vp, vp, cu32, ci]
+    hip.h10x_refmap_results.argtypes = [vp, ctypes.POINTER(cu32), pvp, pvp, pvp, pvp, pvp, pvp]
     if hip.h10x_abi_version() != ABI_VERSION:
         raise RuntimeError("libh10x_hip.so speaks ABI %d, hash10x_amd/__init__.py was written for %d (include/h10x.h H10X_ABI_VERSION): rebuild with "
                            "`python -c 'import __graft_entry__ as g; g.build()'`" % (hip.h10x_abi_version(), ABI_VERSION))
@@ -1099,3 +1114,93 @@ class ReadSet:
         a, b, t = ctypes.c_int32(0), ctypes.c_int32(0), ctypes.c_uint64(0)
         self._chk(self._hip.h10x_readset_mark_contained(self.h, ctypes.byref(a), ctypes.byref(b), ctypes.byref(t)))
         return a.value, b.value, t.value
+
+
+# ---- reference maps: the Reference of the reference's moshmap (moshmap.c) on the GPU — csrc/stage_i.hip ------------------------------------
+MAPSEED_DTYPE = np.dtype([("loc", "<u4"), ("loc2", "<u4"), ("idClass", "<u4"), ("id2", "<u4")])
+MAPREC_DTYPE = np.dtype([("pos0", "<u4"), ("posN", "<u4"), ("loc0", "<u4"), ("locN", "<u4"), ("n1", "<u4"), ("n2", "<u4"), ("query", "<u4")])
+
+
+class RefMap:
+    """The reference's Reference over a MoshSet on one MI355X: the loop of -f (add), its end (pack) and -q (query) of moshmap as methods.
+    The map borrows the set: keep the set open while the map lives (closing the set first leaves the map's handle unreleased: close() then
+    only forgets it). A new RefMap needs a set whose 16-bit depths are all 0, as MoshSet(...) leaves them — add() keeps them 0, the counts
+    live in the map's own 32-bit depth — and is refused over any other. Names and lengths of the sequences are the caller's."""
+
+    def __init__(self, moshset, size=1 << 26, _handle=None):
+        self._hip, self._host = load_native()
+        self.ms = moshset
+        self.h = _handle
+        if self.h is None:
+            h = ctypes.c_void_p()
+            if self._hip.h10x_refmap_create(ctypes.byref(h), moshset.h, int(size)):
+                raise Hash10xError(self._hip.h10x_mosh_error(moshset.h).decode())
+            self.h = h
+
+    @classmethod
+    def from_arrays(cls, moshset, index, offset, id, depth, rev, loc, n_ids):
+        """-r: the arrays of a .ref file over the set of its .mosh file"""
+        hip, _ = load_native()
+        a = [np.ascontiguousarray(x, np.uint32) for x in (index, offset, id, depth, rev, loc)]
+        assert len(a[0]) == len(a[1]) == len(a[2]) == len(a[4]) and len(a[3]) == len(a[5]) == moshset.max + 1
+        h = ctypes.c_void_p()
+        if hip.h10x_refmap_load(ctypes.byref(h), moshset.h, *[x.ctypes.data for x in a], len(a[0]), int(n_ids)):
+            raise Hash10xError(hip.h10x_mosh_error(moshset.h).decode())
+        return cls(moshset, _handle=h)
+
+    def close(self):
+        if getattr(self, "h", None) and getattr(self.ms, "h", None):     # (the destroy reads the set: not after the set is gone)
+            self._hip.h10x_refmap_destroy(self.h)
+        self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _chk(self, rc):
+        if rc:
+            raise Hash10xError(self._hip.h10x_refmap_error(self.h).decode())
+
+    def info(self):
+        i = _RefmapInfo()
+        self._chk(self._hip.h10x_refmap_info(self.h, ctypes.byref(i)))
+        return i
+
+    def add(self, codes, seq_start, id_base=0):
+        """the reference sequences of -f from memory, appended in order; returns the hits appended"""
+        c, s = MoshSet._seqs(codes, seq_start)
+        n = ctypes.c_uint64(0)
+        self._chk(self._hip.h10x_refmap_add(self.h, c.ctypes.data, s.ctypes.data, len(s) - 1, int(id_base), ctypes.byref(n)))
+        return n.value
+
+    def pack(self):
+        """copy classes, loc and rev: (copy 1, copy 2, multiple)"""
+        a, b, c = ctypes.c_uint32(0), ctypes.c_uint32(0), ctypes.c_uint32(0)
+        self._chk(self._hip.h10x_refmap_pack(self.h, ctypes.byref(a), ctypes.byref(b), ctypes.byref(c)))
+        return a.value, b.value, c.value
+
+    def export(self):
+        """dict of index, offset, id, rev (max entries) and depth, loc (the set's max + 1): what -w stores"""
+        i = self.info()
+        p = [ctypes.c_void_p() for _ in range(6)]
+        self._chk(self._hip.h10x_refmap_export(self.h, *[ctypes.byref(x) for x in p]))
+        n = dict(index=i.max, offset=i.max, id=i.max, depth=i.setMax + 1, rev=i.max, loc=i.setMax + 1)
+        return {k: _from_ptr(x.value, np.uint32, n[k]) for k, x in zip(("index", "offset", "id", "depth", "rev", "loc"), p)}
+
+    def query(self, codes, seq_start, seeds=False):
+        """-q over sequences in memory: dict of counts (n x 4: missed, copy 1, copy 2, multi), rec_start (n + 1), recs (MAPREC_DTYPE) and,
+        with seeds=True, seed_start, seeds (MAPSEED_DTYPE), seed_pos"""
+        c, s = MoshSet._seqs(codes, seq_start)
+        self._chk(self._hip.h10x_refmap_query(self.h, c.ctypes.data, s.ctypes.data, len(s) - 1, int(bool(seeds))))
+        n = ctypes.c_uint32(0)
+        p = [ctypes.c_void_p() for _ in range(6)]
+        self._chk(self._hip.h10x_refmap_results(self.h, ctypes.byref(n), *[ctypes.byref(x) for x in p]))
+        rec_start = _from_ptr(p[1].value, np.uint64, n.value + 1)
+        out = dict(counts=_from_ptr(p[0].value, np.uint32, 4 * n.value).reshape(-1, 4), rec_start=rec_start, recs=_from_ptr(p[2].value, MAPREC_DTYPE, int(rec_start[-1])))
+        if seeds:
+            out["seed_start"] = _from_ptr(p[3].value, np.uint64, n.value + 1)
+            out["seeds"] = _from_ptr(p[4].value, MAPSEED_DTYPE, int(out["seed_start"][-1]))
+            out["seed_pos"] = _from_ptr(p[5].value, np.uint32, int(out["seed_start"][-1]))
+        return out

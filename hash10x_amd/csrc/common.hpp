@@ -479,5 +479,19 @@ int stageH_overlaps(ReadSet *rs, u32 ix, h10x_overlap_t *out, u32 cap, u32 *nOut
 int stageH_markBad(ReadSet *rs, int32_t found[3]);
 int stageH_markContained(ReadSet *rs, int32_t *nContained, int32_t *nNot, u64 *totLen);
 int stageH_statsSums(ReadSet *rs, u64 out[16]);
+// reference maps over a mosh set (stage_i.hip)
+struct RefMap;
+int stageI_create(RefMap **out, Mosh *m, u32 size);
+int stageI_load(RefMap **out, Mosh *m, const u32 *index, const u32 *offset, const u32 *id, const u32 *depth, const u32 *rev, const u32 *loc, u32 max, u32 nIds);
+void stageI_destroy(RefMap *rm);
+const char *stageI_error(const RefMap *rm);
+Mosh *stageI_set(RefMap *rm);
+void stageI_info(const RefMap *rm, h10x_refmap_info_t *out);
+int stageI_add(RefMap *rm, const u8 *codes, const u64 *seqStart, u32 nSeq, u32 idBase, u64 *nHits);
+int stageI_pack(RefMap *rm, u32 *n1, u32 *n2, u32 *nM);
+int stageI_export(RefMap *rm, const u32 **index, const u32 **offset, const u32 **id, const u32 **depth, const u32 **rev, const u32 **loc);
+int stageI_query(RefMap *rm, const u8 *codes, const u64 *seqStart, u32 nSeq, int wantSeeds);
+int stageI_results(RefMap *rm, u32 *nQueries, const u32 **counts4, const u64 **recStart, const h10x_maprec_t **recs, const u64 **seedStart,
+                   const h10x_mapseed_t **seeds, const u32 **seedPos);
 
 }  // namespace h10x

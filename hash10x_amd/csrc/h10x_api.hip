@@ -135,6 +135,38 @@ int h10x_readset_stats_sums(h10x_readset *rs, uint64_t out16[16]) {
   return rs && out16 ? rsGuard(stageH_set(RS(rs)), [&] { return stageH_statsSums(RS(rs), (u64 *)out16); }) : -1;
 }
 
+// ---- reference maps: thin wrappers over stage_i.hip
+struct h10x_refmap;                                          // == h10x::RefMap
+static inline RefMap *RM(h10x_refmap *s) { return reinterpret_cast<RefMap *>(s); }
+int h10x_refmap_create(h10x_refmap **rm, h10x_mosh *set, uint32_t size) {
+  if (!rm || !set) return -1;
+  return rsGuard(M(set), [&] { return stageI_create(reinterpret_cast<RefMap **>(rm), M(set), size); });
+}
+int h10x_refmap_load(h10x_refmap **rm, h10x_mosh *set, const uint32_t *index, const uint32_t *offset, const uint32_t *id, const uint32_t *depth, const uint32_t *rev,
+                     const uint32_t *loc, uint32_t max, uint32_t nIds) {
+  if (!rm || !set) return -1;
+  return rsGuard(M(set), [&] { return stageI_load(reinterpret_cast<RefMap **>(rm), M(set), index, offset, id, depth, rev, loc, max, nIds); });
+}
+void h10x_refmap_destroy(h10x_refmap *rm) { stageI_destroy(RM(rm)); }
+const char *h10x_refmap_error(const h10x_refmap *rm) { return stageI_error(reinterpret_cast<const RefMap *>(rm)); }
+int h10x_refmap_info(const h10x_refmap *rm, h10x_refmap_info_t *out) { if (!rm || !out) return -1; stageI_info(reinterpret_cast<const RefMap *>(rm), out); return 0; }
+int h10x_refmap_add(h10x_refmap *rm, const uint8_t *codes, const uint64_t *seqStart, uint32_t nSeq, uint32_t idBase, uint64_t *nHits) {
+  return rm ? rsGuard(stageI_set(RM(rm)), [&] { return stageI_add(RM(rm), codes, (const u64 *)seqStart, nSeq, idBase, (u64 *)nHits); }) : -1;
+}
+int h10x_refmap_pack(h10x_refmap *rm, uint32_t *n1, uint32_t *n2, uint32_t *nM) {
+  return rm ? rsGuard(stageI_set(RM(rm)), [&] { return stageI_pack(RM(rm), n1, n2, nM); }) : -1;
+}
+int h10x_refmap_export(h10x_refmap *rm, const uint32_t **index, const uint32_t **offset, const uint32_t **id, const uint32_t **depth, const uint32_t **rev, const uint32_t **loc) {
+  return rm ? stageI_export(RM(rm), index, offset, id, depth, rev, loc) : -1;
+}
+int h10x_refmap_query(h10x_refmap *rm, const uint8_t *codes, const uint64_t *seqStart, uint32_t nSeq, int wantSeeds) {
+  return rm ? rsGuard(stageI_set(RM(rm)), [&] { return stageI_query(RM(rm), codes, (const u64 *)seqStart, nSeq, wantSeeds); }) : -1;
+}
+int h10x_refmap_results(h10x_refmap *rm, uint32_t *nQueries, const uint32_t **counts4, const uint64_t **recStart, const h10x_maprec_t **recs, const uint64_t **seedStart,
+                        const h10x_mapseed_t **seeds, const uint32_t **seedPos) {
+  return rm ? stageI_results(RM(rm), nQueries, counts4, (const u64 **)recStart, recs, (const u64 **)seedStart, seeds, seedPos) : -1;
+}
+
 static int create_fail(char *err, int errlen, const char *fmt, ...) {
   if (err && errlen > 0) { va_list ap; va_start(ap, fmt); vsnprintf(err, (size_t)errlen, fmt, ap); va_end(ap); }
   return -1;

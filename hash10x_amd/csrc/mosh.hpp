@@ -37,5 +37,9 @@ template <typename F> static int moshBatches(Mosh *m, const u64 *seqStart, u32 n
   return 0;
 }
 
+// one uploaded batch and the list its scan left (stage_g.hip)
+struct MoshBatch { DevBuf<u8> codes; DevBuf<u64> seq, run, tallies, outHash; DevBuf<u32> outOrd; u64 nRuns = 0, total = 0, listed = 0, found = 0; };
+int moshIota(Mosh *m, u32 *v, u64 n);
+int moshScanOrdered(Mosh *m, MoshBatch &b, DevBuf<u64> &sh, DevBuf<u32> &so, const u8 *codes, const u64 *seqStart, u32 nSeq, int skipOdd, u64 seqBase);
 
 }  // namespace h10x

@@ -331,8 +331,6 @@ static int moshPlace(Mosh *m, u32 D) {
   return 0;
 }
 
-struct MoshBatch { DevBuf<u8> codes; DevBuf<u64> seq, run, tallies, outHash; DevBuf<u32> outOrd; u64 nRuns = 0, total = 0, listed = 0, found = 0; };
-
 // upload a batch and run the scan; the list is sized by an estimate and the scan repeated with the exact size if it was too small
 static int moshScanBatch(Mosh *m, MoshBatch &b, const u8 *codes, const u64 *seqStart, u32 nSeq, int skipOdd, u64 seqBase, bool add) {
   Ctx *c = &m->c; hipStream_t st = c->stream; const int k = m->k;
@@ -433,6 +431,31 @@ int stageG_add(Mosh *m, const u8 *codes, const u64 *seqStart, u32 nSeq, int skip
   return rc;
 }
 
+int moshIota(Mosh *m, u32 *v, u64 n) {                       // v[i] = i
+  if (!n) return 0;
+  mosh_iota_kernel<<<divUp(n, 256), 256, 0, m->c.stream>>>(v, n);
+  H10X_HIP(&m->c, hipGetLastError());
+  return 0;
+}
+
+// every mosh of one batch in order, on the device: sh[i] = hash, so[i] = ordinal of its k-mer in the batch, i < b.listed; b.seq = the
+// batch's sequence starts. What stageG_scan copies out, and what stage_i.hip looks up.
+int moshScanOrdered(Mosh *m, MoshBatch &b, DevBuf<u64> &sh, DevBuf<u32> &so, const u8 *codes, const u64 *seqStart, u32 nSeq, int skipOdd, u64 seqBase) {
+  Ctx *c = &m->c; hipStream_t st = c->stream; PrimTemp pt;
+  H10X_TRY(moshScanBatch(m, b, codes, seqStart, nSeq, skipOdd, seqBase, false));
+  const u64 n = b.listed;
+  if (!n) return 0;
+  if (n > 0xFFFFFFFFull) return c->fail("mosh scan: %llu moshes in one batch", n);
+  DevBuf<u32> iota, sp;
+  H10X_HIP(c, iota.alloc(n)); H10X_HIP(c, so.alloc(n)); H10X_HIP(c, sp.alloc(n)); H10X_HIP(c, sh.alloc(n));
+  H10X_TRY(moshIota(m, iota.p, n));
+  H10X_TRY(prim_sort_pairs_u32_u32(c, pt, b.outOrd.p, so.p, iota.p, sp.p, n, 0, 32));
+  mosh_gather_kernel<<<divUp(n, 256), 256, 0, st>>>(sp.p, b.outHash.p, n, sh.p);
+  H10X_HIP(c, hipGetLastError());
+  H10X_HIP(c, hipStreamSynchronize(st));                     // the temporaries above go back to the block cache behind finished work
+  return 0;
+}
+
 // every mosh of the sequences in order: (hash, sequence, position of the k-mer in the sequence as moshRCnext reports it)
 int stageG_scan(Mosh *m, const u8 *codes, const u64 *seqStart, u32 nSeq, int skipOdd, u64 seqBase, u64 *hash, u32 *seq, u32 *pos, u64 cap, u64 *nOut) {
   H10X_TRY(moshEnter(m));
@@ -440,18 +463,10 @@ int stageG_scan(Mosh *m, const u8 *codes, const u64 *seqStart, u32 nSeq, int ski
   if (nSeq && (!codes || !seqStart)) return c->fail("h10x_mosh_scan: null argument");
   u64 done = 0;
   const int rc = moshBatches(m, seqStart, nSeq, [&](u32 s0, u32 ns) -> int {
-    PrimTemp pt; MoshBatch b;
-    H10X_TRY(moshScanBatch(m, b, codes, seqStart + s0, ns, skipOdd, seqBase + s0, false));
+    MoshBatch b; DevBuf<u32> so; DevBuf<u64> sh;
+    H10X_TRY(moshScanOrdered(m, b, sh, so, codes, seqStart + s0, ns, skipOdd, seqBase + s0));
     const u64 n = b.listed;
     if (!n) return 0;
-    if (n > 0xFFFFFFFFull) return c->fail("mosh scan: %llu moshes in one batch", n);
-    DevBuf<u32> iota, so, sp; DevBuf<u64> sh;
-    H10X_HIP(c, iota.alloc(n)); H10X_HIP(c, so.alloc(n)); H10X_HIP(c, sp.alloc(n)); H10X_HIP(c, sh.alloc(n));
-    mosh_iota_kernel<<<divUp(n, 256), 256, 0, st>>>(iota.p, n);
-    H10X_HIP(c, hipGetLastError());
-    H10X_TRY(prim_sort_pairs_u32_u32(c, pt, b.outOrd.p, so.p, iota.p, sp.p, n, 0, 32));
-    mosh_gather_kernel<<<divUp(n, 256), 256, 0, st>>>(sp.p, b.outHash.p, n, sh.p);
-    H10X_HIP(c, hipGetLastError());
     std::vector<u64> hh(n); std::vector<u32> oo(n);
     H10X_HIP(c, hipMemcpyAsync(hh.data(), sh.p, n * 8, hipMemcpyDeviceToHost, st));
     H10X_HIP(c, hipMemcpyAsync(oo.data(), so.p, n * 4, hipMemcpyDeviceToHost, st));

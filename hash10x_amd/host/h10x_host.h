@@ -117,6 +117,8 @@ void h10x_host_warm_start(int device);
 typedef struct h10x_seqreader h10x_seqreader;
 h10x_seqreader *h10x_seq_open(const char *path, char *msg, int msglen, int *fatal);
 int  h10x_seq_next(h10x_seqreader *r, uint64_t slabBases, const uint8_t **codes, const uint64_t **seqStart, uint32_t *nSeq);
+/* the same with the names: sequence s is called names + nameOff[s], the header up to its first blank or tab (readseq.c:82-88) */
+int  h10x_seq_next_named(h10x_seqreader *r, uint64_t slabBases, const uint8_t **codes, const uint64_t **seqStart, uint32_t *nSeq, const char **names, const uint64_t **nameOff);
 const char *h10x_seq_error(const h10x_seqreader *r);
 const char *h10x_seq_warning(const h10x_seqreader *r);
 void h10x_seq_totals(const h10x_seqreader *r, uint64_t *nSeq, uint64_t *bases);
@@ -151,6 +153,34 @@ int  h10x_readset_print_stats(h10x_readset *rs, h10x_mosh *set, FILE *f, char *e
 int  h10x_readset_print_overlaps(h10x_readset *rs, uint32_t ix, int level, FILE *f, h10x_overlap_t **olap, uint32_t *nOlap, char *err, int errlen);
 int  h10x_readset_print_pair(h10x_readset *rs, h10x_mosh *set, uint32_t ix, uint32_t iy, FILE *f, char *err, int errlen);
 int  h10x_readset_print_assembly(h10x_readset *rs, h10x_mosh *set, uint32_t ix, FILE *f, FILE *fstd, char *err, int errlen);
+/* ---- moshmap-amd (map_host.c): the name dictionary, the RFMSHv1 file, the Q / M / -v texts and the file-level commands over h10x_refmap_* ----
+   h10x_namedict: the reference's DICT (dict.c): names numbered from 0 in order of arrival behind a probe table of 2^dim entries that
+   doubles when max > 0.3 * size. table[] holds index + 1; names[1 .. max]. */
+typedef struct { int32_t dim, max, size; int32_t *table; char **names; } h10x_namedict;
+h10x_namedict *h10x_namedict_create(int size);
+void h10x_namedict_destroy(h10x_namedict *d);
+int  h10x_namedict_add(h10x_namedict *d, const char *s, int *ip);           /* 1 = added, 0 = already there, -1 = out of memory */
+int  h10x_namedict_find(const h10x_namedict *d, const char *s, int *ip);
+const char *h10x_namedict_name(const h10x_namedict *d, uint32_t i);
+/* a parsed RFMSHv1 file (moshmap.c:135-181): index / offset / id / rev of max entries, depth / loc of setMax + 1, the lengths (an Array of
+   lenDim entries, lenMax used) and the names. The reader fails with a message unless: the header is right, size == max, every array fits
+   the file, index <= setMax, id < names, loc is the running sum of depth and ends within max, rev < max, the dict's dim is 10 .. 30 and
+   holds its names, every name fits the file. */
+typedef struct { uint32_t max, setMax; uint32_t *index, *offset, *id, *depth, *rev, *loc; int32_t lenDim, lenMax; uint32_t *len; h10x_namedict *dict; } h10x_reffile;
+int  h10x_reffile_read(const char *path, uint32_t setMax, h10x_reffile *out, char *err, int errlen);
+int  h10x_reffile_write(const char *path, const h10x_reffile *r, char *err, int errlen);
+int  h10x_reffile_set_len(h10x_reffile *r, uint32_t id, uint32_t len);        /* array(ref->len, id, int) = len with arrayExtend's growth */
+void h10x_reffile_free(h10x_reffile *r);
+void h10x_map_print_q(FILE *f, const char *name, int len, const uint32_t counts4[4]);
+void h10x_map_print_m(FILE *f, const char *name, int len, const h10x_maprec_t *m, const char *refName, uint32_t off0, uint32_t offN, uint32_t copy1);
+void h10x_map_print_seed(FILE *f, uint32_t pos, int copyClass, const char *name1, uint32_t off1, const char *name2, uint32_t off2);
+/* a Reference on the device with its names and lengths */
+typedef struct { h10x_refmap *rm; h10x_namedict *dict; uint32_t *len; int32_t lenDim, lenMax; } h10x_mapref;
+int  h10x_mapref_from_fasta(h10x_mapref **out, h10x_mosh *set, uint32_t size, const char *path, uint64_t slabBases, FILE *outFile, char *msg, int msglen);
+int  h10x_mapref_from_file(h10x_mapref **out, h10x_mosh *set, h10x_reffile *rf, char *msg, int msglen);   /* takes rf's names and lengths */
+int  h10x_mapref_write_file(h10x_mapref *r, const char *path, char *err, int errlen);
+int  h10x_mapref_query_file(h10x_mapref *r, const char *path, uint64_t slabBases, int verbose, FILE *f, FILE *fverbose, char *msg, int msglen);
+void h10x_mapref_destroy(h10x_mapref *r);
 
 #ifdef __cplusplus
 }

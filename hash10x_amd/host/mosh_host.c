@@ -13,7 +13,7 @@
 /* ------------------------------------------------------------------------------------------------ sequence reader */
 enum { SEQ_FASTA = 1, SEQ_FASTQ = 2 };
 enum { RD_BUF = 1 << 20 };
-typedef struct { uint8_t *codes; uint64_t nCodes, capCodes; uint64_t *start; uint32_t nSeq, capSeq; } SeqSlab;
+typedef struct { uint8_t *codes; uint64_t nCodes, capCodes; uint64_t *start; uint32_t nSeq, capSeq; char *names; uint64_t nNames, capNames, *nameOff; } SeqSlab;
 struct h10x_seqreader {
   gzFile f; int type; int line; int done;
   unsigned char *buf; int pos, n; int eof;                  /* buf[pos] is the current byte while !eof */
@@ -66,7 +66,7 @@ void h10x_seq_close(h10x_seqreader *r) {
   if (!r) return;
   if (r->f) gzclose(r->f);
   free(r->buf);
-  for (int i = 0; i < 2; ++i) { free(r->slab[i].codes); free(r->slab[i].start); }
+  for (int i = 0; i < 2; ++i) { free(r->slab[i].codes); free(r->slab[i].start); free(r->slab[i].names); free(r->slab[i].nameOff); }
   free(r);
 }
 const char *h10x_seq_error(const h10x_seqreader *r) { return r ? r->err : "null reader"; }
@@ -83,13 +83,28 @@ static int slab_push(h10x_seqreader *r, SeqSlab *s, int code) {
   s->codes[s->nCodes++] = (uint8_t)code;
   return 0;
 }
-static int slab_close_seq(h10x_seqreader *r, SeqSlab *s) {   /* start[nSeq] = end of the sequence just read */
+/* the record's name: the header up to the first blank or tab, as readSequence cuts it (readseq.c:82-88) */
+static int name_push(h10x_seqreader *r, SeqSlab *s, int ch) {
+  if (s->nNames == s->capNames) {
+    uint64_t cap = s->capNames ? s->capNames * 2 : (1u << 12);
+    char *p = (char *)realloc(s->names, cap);
+    if (!p) return set_msg(r->err, sizeof r->err, "out of host memory for %llu bytes of names", (unsigned long long)cap);
+    s->names = p; s->capNames = cap;
+  }
+  s->names[s->nNames++] = (char)ch;
+  return 0;
+}
+static int slab_close_seq(h10x_seqreader *r, SeqSlab *s, uint64_t nameAt) {   /* start[nSeq] = end of the sequence just read */
   if (s->nSeq + 2 > s->capSeq) {
     uint32_t cap = s->capSeq ? s->capSeq * 2 : 1024;
     uint64_t *p = (uint64_t *)realloc(s->start, (size_t)cap * sizeof *p);
     if (!p) return set_msg(r->err, sizeof r->err, "out of host memory for %u sequences", cap);
-    s->start = p; s->capSeq = cap;
+    s->start = p;
+    p = (uint64_t *)realloc(s->nameOff, (size_t)cap * sizeof *p);
+    if (!p) return set_msg(r->err, sizeof r->err, "out of host memory for %u sequences", cap);
+    s->nameOff = p; s->capSeq = cap;
   }
+  s->nameOff[s->nSeq] = nameAt;
   if (s->nSeq == 0) s->start[0] = 0;
   const uint64_t len = s->nCodes - s->start[s->nSeq];
   if (len >= (1ull << 31)) return set_msg(r->err, sizeof r->err, "sequence %llu has %llu bases: 2^31 or more are not supported", (unsigned long long)(r->nSeqTotal + 1), (unsigned long long)len);
@@ -107,7 +122,12 @@ static int read_record(h10x_seqreader *r, SeqSlab *s) {
   if (r->type == SEQ_FASTA) {
     if (rd_cur(r) != '>') return set_msg(r->err, sizeof r->err, "no initial > for FASTA record line %d", r->line);
     ADV_IN(r);
-    while (rd_cur(r) != '\n') ADV_IN(r);                     /* identifier and description */
+    for (int inName = 1; rd_cur(r) != '\n'; ) {              /* identifier and description */
+      if (rd_cur(r) == ' ' || rd_cur(r) == '\t') inName = 0;
+      if (inName && name_push(r, s, rd_cur(r))) return -1;
+      ADV_IN(r);
+    }
+    if (name_push(r, s, 0)) return -1;
     ++r->line; ADV_IN(r);
     while (!r->eof && rd_cur(r) != '>') {                    /* a record runs to the next LINE that starts with '>' */
       while (rd_cur(r) != '\n') {
@@ -122,7 +142,12 @@ static int read_record(h10x_seqreader *r, SeqSlab *s) {
   } else {
     if (rd_cur(r) != '@') return set_msg(r->err, sizeof r->err, "no initial @ for FASTQ record line %d", r->line);
     ADV_IN(r);
-    while (rd_cur(r) != '\n') ADV_IN(r);
+    for (int inName = 1; rd_cur(r) != '\n'; ) {
+      if (rd_cur(r) == ' ' || rd_cur(r) == '\t') inName = 0;
+      if (inName && name_push(r, s, rd_cur(r))) return -1;
+      ADV_IN(r);
+    }
+    if (name_push(r, s, 0)) return -1;
     ++r->line; ADV_IN(r);
     uint64_t len = 0, qlen = 0;
     while (rd_cur(r) != '\n') {                              /* the sequence line is taken whole */
@@ -144,20 +169,25 @@ static int read_record(h10x_seqreader *r, SeqSlab *s) {
 }
 
 int h10x_seq_next(h10x_seqreader *r, uint64_t slabBases, const uint8_t **codes, const uint64_t **seqStart, uint32_t *nSeq) {
+  return h10x_seq_next_named(r, slabBases, codes, seqStart, nSeq, 0, 0);
+}
+int h10x_seq_next_named(h10x_seqreader *r, uint64_t slabBases, const uint8_t **codes, const uint64_t **seqStart, uint32_t *nSeq, const char **names, const uint64_t **nameOff) {
   if (!r) return -1;
   SeqSlab *s = &r->slab[r->which]; r->which ^= 1;
-  s->nCodes = 0; s->nSeq = 0;
+  s->nCodes = 0; s->nSeq = 0; s->nNames = 0;
   if (!slabBases) slabBases = 1ull << 26;
   while (!r->done && (s->nSeq == 0 || s->nCodes < slabBases) && s->nSeq < 0x7FFFFFFFu) {
-    const uint64_t mark = s->nCodes;
+    const uint64_t mark = s->nCodes, nameMark = s->nNames;
     const int rc = read_record(r, s);
     if (rc < 0) { r->done = 1; return -1; }
-    if (rc == 0) { s->nCodes = mark; r->done = 1; break; }   /* (a record the file ended in leaves nothing behind) */
-    if (slab_close_seq(r, s)) { r->done = 1; return -1; }
+    if (rc == 0) { s->nCodes = mark; s->nNames = nameMark; r->done = 1; break; }   /* (a record the file ended in leaves nothing behind) */
+    if (slab_close_seq(r, s, nameMark)) { r->done = 1; return -1; }
   }
   if (codes) *codes = s->codes;
   if (seqStart) *seqStart = s->start;
   if (nSeq) *nSeq = s->nSeq;
+  if (names) *names = s->names;
+  if (nameOff) *nameOff = s->nameOff;
   return s->nSeq ? 1 : 0;
 }
 

@@ -453,6 +453,51 @@ int  h10x_readset_mark_contained(h10x_readset *rs, int32_t *nContained, int32_t 
 /* the per-class sums of readsetStats' last line (moshasm.c:216-224): nCopy[4], hitCopy[4], hit2Copy[4], depthCopy[4] */
 int  h10x_readset_stats_sums(h10x_readset *rs, uint64_t out16[16]);
 
+/* ---- reference maps (csrc/stage_i.hip): the Reference object of the reference's moshmap (moshmap.c) over a mosh set ----
+   Reference sequences kept as their mosh hits: per hit in file order index (the set index), offset (position of the k-mer) and id
+   (sequence number); per set index a 32-bit depth; once packed, loc[] (where an index's hits start in rev[]) and rev[] (the hit
+   ordinals of each index, ascending). The map borrows the set, as a readset does. Sequence names and lengths are the caller's
+   (host/map_host.c keeps the reference's DICT). Every function returns 0 on success; h10x_refmap_error() holds the message otherwise —
+   the reference's die() text where it would have died ("reference size overflow", moshmap.c:109). */
+typedef struct h10x_refmap h10x_refmap;
+typedef struct { uint32_t size /* ref->size */, max /* ref->max: hits */, setMax /* ms->max */; int32_t packed; } h10x_refmap_info_t;
+typedef struct {              /* one seed of a query, resolved: class = idClass >> 30 (0 = not in the set, 1, 2, 3 = M); for class 1 and 2 */
+  uint32_t loc, loc2;         /* loc = rev[loc[index]], and for class 2 loc2 = rev[loc[index] + 1] (moshmap.c:217, 224)                 */
+  uint32_t idClass, id2;      /* idClass & 0x3fffffff = id[loc]; id2 = id[loc2]                                                       */
+} h10x_mapseed_t;
+typedef struct {              /* what one M line is printed from (moshmap.c:255-260, 267-272)                                          */
+  uint32_t pos0, posN;        /* positions in the query of seeds i0 and iN                                                           */
+  uint32_t loc0, locN, n1, n2, query;
+} h10x_maprec_t;
+/* referenceCreate (moshmap.c:48-63) over a set that moshsetCreate left: its 16-bit depths must all be 0 (checked here and by every
+   h10x_refmap_add, which fail otherwise); the program passes size = 1 << 26. Destroy the map before its set. */
+int  h10x_refmap_create(h10x_refmap **rm, h10x_mosh *set, uint32_t size);
+/* the loop of referenceFastaRead (moshmap.c:99-119) over sequences as for h10x_mosh_add: every mosh is found or added in file order
+   (the numbering and the table of h10x_mosh_add), appended as (index, position, idBase + sequence number) and counted in the 32-bit
+   depth. The set's own 16-bit depth[] stays 0. *nHits = hits appended by this call. */
+int  h10x_refmap_add(h10x_refmap *rm, const uint8_t *codes, const uint64_t *seqStart, uint32_t nSeq, uint32_t idBase, uint64_t *nHits);
+/* the rest of referenceFastaRead and referencePack (moshmap.c:73-90, 124-132): copy classes from the 32-bit depth (1, 2, else M)
+   into the set's info, loc[], rev[] */
+int  h10x_refmap_pack(h10x_refmap *rm, uint32_t *n1, uint32_t *n2, uint32_t *nM);
+/* referenceRead's state (moshmap.c:157-181) from the arrays of a parsed RFMSHv1 file: index / offset / id / rev of max entries, depth /
+   loc of the set's max + 1. Checked again here: loc is the running sum of depth and ends within max, every index within the set,
+   id < nIds, rev < max, and no index of the set with copy class 0 (-f leaves none; the reference would walk it as copy 2) or copy-1 /
+   copy-2 with fewer than 1 / 2 hits. */
+int  h10x_refmap_load(h10x_refmap **rm, h10x_mosh *set, const uint32_t *index, const uint32_t *offset, const uint32_t *id, const uint32_t *depth, const uint32_t *rev,
+                      const uint32_t *loc, uint32_t max, uint32_t nIds);
+void h10x_refmap_destroy(h10x_refmap *rm);
+const char *h10x_refmap_error(const h10x_refmap *rm);
+int  h10x_refmap_info(const h10x_refmap *rm, h10x_refmap_info_t *out);
+/* what referenceWrite stores (moshmap.c:143-150) of a packed map: pointers into the object, valid while it lives */
+int  h10x_refmap_export(h10x_refmap *rm, const uint32_t **index, const uint32_t **offset, const uint32_t **id, const uint32_t **depth, const uint32_t **rev, const uint32_t **loc);
+/* queryProcess (moshmap.c:187-278) over query sequences as for h10x_mosh_add. The results stay in the object until the next query:
+   counts4[4 q ..] = missed, copy 1, copy 2, multi of query q; recs[recStart[q] .. recStart[q + 1]) its M records in the order the
+   reference prints them; with wantSeeds != 0 also seeds / seedPos [seedStart[q] .. seedStart[q + 1]), every mosh of q in order (the -v
+   lines, moshmap.c:219-229). */
+int  h10x_refmap_query(h10x_refmap *rm, const uint8_t *codes, const uint64_t *seqStart, uint32_t nSeq, int wantSeeds);
+int  h10x_refmap_results(h10x_refmap *rm, uint32_t *nQueries, const uint32_t **counts4, const uint64_t **recStart, const h10x_maprec_t **recs, const uint64_t **seedStart,
+                         const h10x_mapseed_t **seeds, const uint32_t **seedPos);
+
 /* ---- device memory plumbing for callers that keep the input resident in HBM (bench, pipelines) ----
    plain hipMalloc / hipMemcpy / hipDeviceSynchronize on `device`; return NULL / non-zero on failure */
 void *h10x_device_malloc(int device, uint64_t bytes);
