@@ -155,6 +155,7 @@ def load_native():
     hip.h10x_device_free.argtypes = [ci, vp]
     hip.h10x_device_upload.argtypes = [ci, vp, vp, cu64]
     hip.h10x_device_synchronize.argtypes = [ci]
+    hip.h10x_device_download.argtypes = [ci, vp, vp, cu64]
     hip.h10x_device_mem_info.argtypes = [ci, ctypes.POINTER(cu64), ctypes.POINTER(cu64)]
     hip.h10x_crib_genome.argtypes = [vp, vp, vp, ctypes.c_uint32, ci, ctypes.POINTER(cu64), ctypes.POINTER(cu64)]
     hip.h10x_crib_finish.argtypes = [vp]
@@ -191,6 +192,22 @@ def load_native():
     hip.h10x_code_share.argtypes = [vp, vp, ctypes.c_uint32, vp, vp, vp, vp, vp, cu64]
     hip.h10x_code_explore.argtypes = [vp, ctypes.c_int32, ctypes.c_int32, vp]
     hip.h10x_code_crib_counts.argtypes = [vp, vp, ctypes.c_uint32, vp]
+    # barcode census and whitelist correction (csrc/stage_j.hip)
+    hip.h10x_census_begin.argtypes = [vp, cu64]
+    hip.h10x_census_add.argtypes = [vp, vp, cu64]
+    hip.h10x_census_add_device.argtypes = [vp, vp, cu64]
+    hip.h10x_census_close.argtypes = [vp, ctypes.c_int64, vp]
+    hip.h10x_census_export.argtypes = [vp, ci, vp, vp, cu64]
+    hip.h10x_whitelist_set.argtypes = [vp, vp, cu64]
+    hip.h10x_fix_fqb.argtypes = [vp, vp, cu64, vp, ctypes.POINTER(cu64), vp]
+    hip.h10x_fix_fqb_device.argtypes = [vp, vp, cu64, vp, ctypes.POINTER(cu64), vp]
+    host.h10x_session_codeCensus.argtypes = [vp, ci, cs, cs, vp]
+    host.h10x_session_fixFQB.argtypes = [vp, cs, cs, cs, vp]
+    host.h10x_session_fixFQBThresh.argtypes = [vp, ci, cs, cs, vp]
+    host.h10x_host_whitelist_read.argtypes = [cs, ctypes.POINTER(vp), ctypes.POINTER(cu64), cs, ci]
+    host.h10x_host_whitelist_free.restype = None; host.h10x_host_whitelist_free.argtypes = [vp]
+    host.h10x_host_whitelist_write.argtypes = [cs, vp, cu64, cs, ci]
+    host.h10x_host_whitelist_lines.argtypes = [vp, cu64, vp, cu64, vp]
     # mosh sets (csrc/stage_g.hip, host/mosh_host.c)
     pvp, ci32, cu32 = ctypes.POINTER(vp), ctypes.c_int32, ctypes.c_uint32
     hip.h10x_factors_from_seed.restype = None; hip.h10x_factors_from_seed.argtypes = [ci32, ctypes.POINTER(cu64), ctypes.POINTER(cu64)]
@@ -287,15 +304,23 @@ def build_id():
 class DeviceRecords:
     """A sorted .fqb image resident in HBM (hipMalloc through the library, no torch involved)."""
 
-    def __init__(self, records, device=0):
+    def __init__(self, records, device=0, _words=0):
         hip = load_native()[0]
         r = np.ascontiguousarray(records, dtype=np.uint32).reshape(-1)
         self.n_records, self.device, self._hip = r.size // 30, device, hip
-        self.ptr = hip.h10x_device_malloc(device, r.nbytes)
+        nbytes = max(r.nbytes, 4 * int(_words))                 # _words: room for that many words, contents undefined (an output buffer)
+        self.ptr = hip.h10x_device_malloc(device, nbytes)
         if not self.ptr:
-            raise Hash10xError("hipMalloc of %d bytes failed on device %d" % (r.nbytes, device))
-        if hip.h10x_device_upload(device, self.ptr, r.ctypes.data, r.nbytes):
+            raise Hash10xError("hipMalloc of %d bytes failed on device %d" % (nbytes, device))
+        if r.nbytes and hip.h10x_device_upload(device, self.ptr, r.ctypes.data, r.nbytes):
             raise Hash10xError("upload to device %d failed" % device)
+
+    def download(self):
+        """the records as an (n_records, 30) uint32 array"""
+        out = np.zeros(max(self.n_records * 30, 1), dtype=np.uint32)
+        if self.n_records and self._hip.h10x_device_download(self.device, out.ctypes.data, self.ptr, self.n_records * 120):
+            raise Hash10xError("download from device %d failed" % self.device)
+        return out[:self.n_records * 30].reshape(-1, 30)
 
     def free(self):
         if getattr(self, "ptr", None):
@@ -771,6 +796,60 @@ class Hash10x:
         out = np.zeros((max(q.size, 1), 2), dtype=np.uint32)
         self._chk_ctx(self._hip.h10x_code_crib_counts(self._ctx(), q.ctypes.data, q.size, out.ctypes.data))
         return out[:q.size]
+
+    # ---- barcode census and whitelist correction of unsorted records (h10x_census_* / h10x_whitelist_set / h10x_fix_fqb: fq2b.c:71-104) ----
+    def _need_ctx(self):
+        if not self._ctx():
+            self._chk(self._host.h10x_session_begin(self._s))
+            self._after_init()
+        return self._ctx()
+
+    def code_census(self, records, thresh):
+        """Census of the barcodes (record word 0) of an unsorted .fqb image, a host array or DeviceRecords: (codes, counts, good) =
+        the distinct barcodes ascending by packed word, how often each occurs, and those that occur at least `thresh` times.
+        The good barcodes become the session's whitelist, in ascending order."""
+        ctx = self._need_ctx()
+        if isinstance(records, DeviceRecords):
+            self._chk_ctx(self._hip.h10x_census_begin(ctx, records.n_records))
+            self._chk_ctx(self._hip.h10x_census_add_device(ctx, records.ptr, records.n_records))
+        else:
+            r = np.ascontiguousarray(records, dtype=np.uint32).reshape(-1)
+            if r.size % 30:
+                raise Hash10xError("records: %d words are no multiple of the 30-word record" % r.size)
+            self._chk_ctx(self._hip.h10x_census_begin(ctx, r.size // 30))
+            self._chk_ctx(self._hip.h10x_census_add(ctx, r.ctypes.data, r.size // 30))
+        z = np.zeros(4, dtype=np.uint64)
+        self._chk_ctx(self._hip.h10x_census_close(ctx, int(thresh), z.ctypes.data))
+        d, g = int(z[1]), int(z[2])
+        codes, counts, good = np.zeros(max(d, 1), dtype=np.uint32), np.zeros(max(d, 1), dtype=np.uint32), np.zeros(max(g, 1), dtype=np.uint32)
+        self._chk_ctx(self._hip.h10x_census_export(ctx, 0, codes.ctypes.data, counts.ctypes.data, d))
+        self._chk_ctx(self._hip.h10x_census_export(ctx, 1, good.ctypes.data, None, g))
+        return codes[:d], counts[:d], good[:g]
+
+    def set_whitelist(self, codes):
+        """The whitelist from packed barcodes in line order (read10xWhitelist, fq2b.c:71-94): a repeated code keeps its latest line."""
+        c = np.ascontiguousarray(codes, dtype=np.uint32).reshape(-1)
+        self._chk_ctx(self._hip.h10x_whitelist_set(self._need_ctx(), c.ctypes.data, c.size))
+
+    def fix_fqb(self, records):
+        """What fq2b -10x does to the reads, on records (a host array or DeviceRecords): (records_out, stats). Records without a
+        whitelist barcode within one substitution are dropped, the others get the candidate of the latest whitelist line as
+        word 0 and keep their order. records_out is an (n_kept, 30) uint32 array, or for DeviceRecords a DeviceRecords holding
+        n_records = n_kept; stats = {"dropped", "corrected", "correctedAt": 16 counts by base position}."""
+        ctx = self._need_ctx()
+        st, kept = np.zeros(18, dtype=np.uint64), ctypes.c_uint64(0)
+        if isinstance(records, DeviceRecords):
+            out = DeviceRecords(np.zeros(0, dtype=np.uint32), records.device, _words=records.n_records * 30)
+            self._chk_ctx(self._hip.h10x_fix_fqb_device(ctx, records.ptr, records.n_records, out.ptr, ctypes.byref(kept), st.ctypes.data))
+            out.n_records = kept.value
+        else:
+            r = np.ascontiguousarray(records, dtype=np.uint32).reshape(-1)
+            if r.size % 30:
+                raise Hash10xError("records: %d words are no multiple of the 30-word record" % r.size)
+            buf = np.zeros(max(r.size, 30), dtype=np.uint32)
+            self._chk_ctx(self._hip.h10x_fix_fqb(ctx, r.ctypes.data, r.size // 30, buf.ctypes.data, ctypes.byref(kept), st.ctypes.data))
+            out = buf[:kept.value * 30].reshape(-1, 30)
+        return out, {"dropped": int(st[0]), "corrected": int(st[1]), "correctedAt": [int(v) for v in st[2:]]}
 
     def export_within(self):
         """hashWithinRange[0 .. hashNumber) as uint8 (fails before --hashDepthRange)."""

@@ -244,6 +244,12 @@ struct Ctx {
   int64_t optRowsFakeBase = 0; // testing knob: list offsets start at this many entries (multiple of 2^rowShift) in front of the real array: 64-bit offsets on small inputs
   int64_t optNbBudget = 0;    // neighbour census: gathered ClusterHash records per batch (0 = default, stage_f.hip); small values force the batching and the hash-index windows
   u64 nbStats[4] = {0, 0, 0, 0};   // neighbour census since the last reset: records gathered, in-range keys sorted, batches, windows (h10x_neighbour_stats)
+  // barcode census and whitelist of unsorted .fqb records (stage_j.hip): the packed barcode words of the batches added so far, then — after the close — the
+  // distinct barcodes with their counts and the good ones; the whitelist is a probe table of 64-bit slots, barcode << 32 | line (line >= 1, 0 = empty slot)
+  DevBuf<u32> censusKeys; u64 censusN = 0; bool censusOpen = false;
+  DevBuf<u32> censusCodes, censusCounts, censusGoodCodes, censusGoodCounts; u64 censusDistinct = 0, censusGood = 0; bool censusClosed = false;
+  DevBuf<u64> wlSlots; u64 wlMask = 0, wlCodes = 0; bool haveWhitelist = false;
+  int64_t optFqbSlab = 0;     // records per device batch of the host forms of the census and the fix (0 = default 2^22); results do not depend on it
   // streaming ingest (h10x_ingest_fqb): the record image grows on the device as the chunks arrive
   DevBuf<u32> ingestBuf; u64 ingestRecords = 0, ingestCap = 0; bool ingestAsync = false;   // ingestAsync: chunks came through h10x_ingest_fqb_async (the closing call then checks the count)
   static constexpr int INGEST_SLOTS = 8; hipEvent_t ingestEv[INGEST_SLOTS] = {};   // h10x_ingest_fqb_async: one event per caller's buffer
@@ -439,6 +445,13 @@ int stageF_neighbourHist(Ctx *c, const u32 *xs, u32 nq, const u64 *offsets, u32 
 int stageF_codeShare(Ctx *c, const u32 *codes, u32 nq, u64 *offsets, u32 *barcode, u32 *count, u32 *firstRank, u32 *firstHash, u64 cap);
 int stageF_codeExplore(Ctx *c, int code, int threshold, u32 *out /* 8: h10x_code_explore_rep */);
 int stageF_codeCrib(Ctx *c, const u32 *codes, u32 n, u32 *out);
+int stageJ_censusBegin(Ctx *c, u64 hint);
+int stageJ_censusAdd(Ctx *c, const u32 *dRec, u64 n);
+int stageJ_censusClose(Ctx *c, int64_t thresh, h10x_census_t *out);
+int stageJ_censusExport(Ctx *c, int goodOnly, u32 *codes, u32 *counts, u64 cap);
+int stageJ_whitelistSet(Ctx *c, const u32 *hostCodes, u64 n);
+int stageJ_fix(Ctx *c, const u32 *dIn, u64 n, u32 *dOut, u64 *nKept, h10x_fix_stats *acc);
+u64 stageJ_slab(const Ctx *c);
 int shard_allreduceU64(Ctx *c, u64 *v, u32 n, int op);
 int shard_gatherBytes(Ctx *c, const void *send, u64 nbytes, void *recv, u64 cap, u64 *counts);
 int shard_exchangeRows(Ctx *c);

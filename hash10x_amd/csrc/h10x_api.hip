@@ -460,6 +460,9 @@ int h10x_device_upload(int device, void *dst, const void *src, uint64_t bytes) {
   // at the end of an upload when several rank threads shared one device)
   return (hipSetDevice(device) == hipSuccess && hipMemcpy(dst, src, bytes, hipMemcpyHostToDevice) == hipSuccess && hipDeviceSynchronize() == hipSuccess) ? 0 : -1;
 }
+int h10x_device_download(int device, void *dst, const void *src, uint64_t bytes) {
+  return (hipSetDevice(device) == hipSuccess && hipDeviceSynchronize() == hipSuccess && hipMemcpy(dst, src, bytes, hipMemcpyDeviceToHost) == hipSuccess) ? 0 : -1;
+}
 int h10x_device_synchronize(int device) { return (hipSetDevice(device) == hipSuccess && hipDeviceSynchronize() == hipSuccess) ? 0 : -1; }
 
 }  // extern "C"
@@ -716,6 +719,67 @@ int h10x_sort_fqb(h10x_ctx *h, const uint32_t *in, uint64_t n, uint32_t *out) {
   return 0;
 }
 
+// ---- barcode census and whitelist correction (stage_j.hip): the README's goodcodes pipeline (README.md:44) and fq2b -10x (fq2b.c:71-104) on packed records ----
+int h10x_census_begin(h10x_ctx *h, uint64_t hint) { if (!h) return -1; Ctx &c = h->c; H10X_TRY(enter(c)); return stageJ_censusBegin(&c, hint); }
+int h10x_census_add_device(h10x_ctx *h, const uint32_t *dRec, uint64_t n) {
+  if (!h) return -1;
+  Ctx &c = h->c; H10X_TRY(enter(c));
+  if (n && !dRec) return c.fail("h10x_census_add_device: null buffer");
+  return stageJ_censusAdd(&c, dRec, n);
+}
+int h10x_census_add(h10x_ctx *h, const uint32_t *rec, uint64_t n) {
+  if (!h) return -1;
+  Ctx &c = h->c; H10X_TRY(enter(c));
+  if (n && !rec) return c.fail("h10x_census_add: null buffer");
+  const u64 slab = stageJ_slab(&c);
+  DevBuf<u32> d; if (n) H10X_HIP(&c, d.alloc(hmin<u64>(n, slab) * 30));
+  for (u64 at = 0; at < n; at += slab) {
+    const u64 m = hmin<u64>(slab, n - at);
+    H10X_HIP(&c, hipMemcpyAsync(d.p, rec + at * 30, m * 120, hipMemcpyHostToDevice, c.stream));
+    H10X_TRY(stageJ_censusAdd(&c, d.p, m));
+    H10X_HIP(&c, hipStreamSynchronize(c.stream));                                    // the batch buffer is written again by the next upload
+  }
+  return 0;
+}
+int h10x_census_close(h10x_ctx *h, int64_t thresh, h10x_census_t *out) { if (!h) return -1; Ctx &c = h->c; H10X_TRY(enter(c)); return stageJ_censusClose(&c, thresh, out); }
+int h10x_census_export(h10x_ctx *h, int goodOnly, uint32_t *codes, uint32_t *counts, uint64_t cap) {
+  if (!h) return -1; Ctx &c = h->c; H10X_TRY(enter(c)); return stageJ_censusExport(&c, goodOnly, codes, counts, cap);
+}
+int h10x_whitelist_set(h10x_ctx *h, const uint32_t *codes, uint64_t n) {
+  if (!h) return -1;
+  Ctx &c = h->c; H10X_TRY(enter(c));
+  if (n && !codes) return c.fail("h10x_whitelist_set: null buffer");
+  return stageJ_whitelistSet(&c, codes, n);
+}
+int h10x_fix_fqb_device(h10x_ctx *h, const uint32_t *dIn, uint64_t n, uint32_t *dOut, uint64_t *nKept, h10x_fix_stats *acc) {
+  if (!h) return -1;
+  Ctx &c = h->c; H10X_TRY(enter(c));
+  if (n && (!dIn || !dOut)) return c.fail("h10x_fix_fqb_device: null buffer");
+  u64 kept = 0;
+  H10X_TRY(stageJ_fix(&c, dIn, n, dOut, &kept, acc));
+  if (nKept) *nKept = kept;
+  return 0;
+}
+int h10x_fix_fqb(h10x_ctx *h, const uint32_t *in, uint64_t n, uint32_t *out, uint64_t *nKept, h10x_fix_stats *acc) {
+  if (!h) return -1;
+  Ctx &c = h->c; H10X_TRY(enter(c));
+  if (n && (!in || !out)) return c.fail("h10x_fix_fqb: null buffer");
+  if (!c.haveWhitelist) return c.fail("no whitelist: close a census with a good barcode or set one first");
+  const u64 slab = stageJ_slab(&c);
+  DevBuf<u32> dIn, dOut; u64 total = 0;
+  if (n) { H10X_HIP(&c, dIn.alloc(hmin<u64>(n, slab) * 30)); H10X_HIP(&c, dOut.alloc(hmin<u64>(n, slab) * 30)); }
+  for (u64 at = 0; at < n; at += slab) {
+    const u64 m = hmin<u64>(slab, n - at); u64 kept = 0;
+    H10X_HIP(&c, hipMemcpyAsync(dIn.p, in + at * 30, m * 120, hipMemcpyHostToDevice, c.stream));
+    H10X_TRY(stageJ_fix(&c, dIn.p, m, dOut.p, &kept, acc));
+    if (kept) H10X_HIP(&c, hipMemcpyAsync(out + total * 30, dOut.p, kept * 120, hipMemcpyDeviceToHost, c.stream));
+    H10X_HIP(&c, hipStreamSynchronize(c.stream));
+    total += kept;
+  }
+  if (nKept) *nKept = total;
+  return 0;
+}
+
 int h10x_crib_genome(h10x_ctx *h, const uint8_t *codes, const uint64_t *seqStart, uint32_t nSeq, int which, uint64_t *nPresent, uint64_t *nAbsent) {
   if (!h) return -1;
   Ctx &c = h->c; H10X_TRY(enter(c));
@@ -848,6 +912,7 @@ int h10x_set_option(h10x_ctx *h, const char *name, int64_t value) {
   if (!strcmp(name, "shard_owner_cut")) { if (value < 0 || value > 1) return h->c.fail("shard_owner_cut must be 0 or 1"); h->c.optOwnerCut = value; return 0; }
   if (!strcmp(name, "shard_delta_lists")) { if (value < -1 || value > 1) return h->c.fail("shard_delta_lists must be -1, 0 or 1"); h->c.optDeltaLists = value; return 0; }
   if (!strcmp(name, "shard_rows_fake_base")) { if (value < 0) return h->c.fail("shard_rows_fake_base must be >= 0"); h->c.optRowsFakeBase = value; return 0; }
+  if (!strcmp(name, "fqb_slab")) { if (value < 0 || value > (1 << 28)) return h->c.fail("fqb_slab must be 0..2^28"); h->c.optFqbSlab = value; return 0; }
   if (!strcmp(name, "neighbour_budget")) { if (value < 0) return h->c.fail("neighbour_budget must be >= 0"); h->c.optNbBudget = value; return 0; }
   return h->c.fail("unknown option %s", name);
 }

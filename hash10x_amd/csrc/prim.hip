@@ -106,6 +106,11 @@ int prim_sort_keys_u64(Ctx *c, PrimTemp &t, const u64 *kin, u64 *kout, size_t n,
   PRIM_TWO_PHASE(c, t, rocprim::radix_sort_keys<SortKeys64Config>(tmp, bytes, kin, kout, n, (unsigned)b0, (unsigned)(b1 > 64 ? 64 : b1), c->stream));
   return 0;
 }
+int prim_sort_keys_u32(Ctx *c, PrimTemp &t, const u32 *kin, u32 *kout, size_t n, int b0, int b1) {
+  if (!n) return 0;
+  PRIM_TWO_PHASE(c, t, rocprim::radix_sort_keys(tmp, bytes, kin, kout, n, (unsigned)b0, (unsigned)(b1 > 32 ? 32 : b1), c->stream));
+  return 0;
+}
 int prim_seg_sort_keys_u64(Ctx *c, PrimTemp &t, const u64 *kin, u64 *kout, u32 n, u32 nSeg, const u32 *begin, const u32 *end, int b0, int b1) {
   if (!n || !nSeg) return 0;
   PRIM_TWO_PHASE(c, t, rocprim::segmented_radix_sort_keys(tmp, bytes, kin, kout, n, nSeg, begin, end, (unsigned)b0, (unsigned)b1, c->stream));

@@ -15,6 +15,7 @@ int prim_inclusive_scan_u32(Ctx *c, PrimTemp &t, const u32 *in, u32 *out, size_t
 // stable LSD radix sorts on key bits [beginBit, endBit)
 int prim_sort_pairs_u64_u32(Ctx *c, PrimTemp &t, const u64 *kin, u64 *kout, const u32 *vin, u32 *vout, size_t n, int beginBit, int endBit);
 int prim_sort_pairs_u32_u32(Ctx *c, PrimTemp &t, const u32 *kin, u32 *kout, const u32 *vin, u32 *vout, size_t n, int beginBit, int endBit);
+int prim_sort_keys_u32(Ctx *c, PrimTemp &t, const u32 *kin, u32 *kout, size_t n, int beginBit, int endBit);
 int prim_sort_keys_u64(Ctx *c, PrimTemp &t, const u64 *kin, u64 *kout, size_t n, int beginBit, int endBit);
 struct Val16 { u64 a; u32 b, c; };                          // a 16-byte payload that rides through a sort (stage_b.hip: a distinct hash with its list's start and end)
 int prim_sort_pairs_u32_v16(Ctx *c, PrimTemp &t, const u32 *kin, u32 *kout, const Val16 *vin, Val16 *vout, size_t n, int beginBit, int endBit);

@@ -17,7 +17,7 @@
 #define ARRAY_MAGIC 8918274                            /* array.h:56 */
 typedef struct { int32_t magic, pad0; uint64_t base; int32_t dim, size, max, pad1; } array_hdr;   /* array.h:41-50 */
 
-enum { N_KNOBS = 21 };
+enum { N_KNOBS = 22 };
 struct h10x_session {
   int k, w, r, B, N, chunk, ct, device;                /* params (hash10x.c:25-33) */
   int timing;                                          /* measurement hook: enable hipEvent timers on every new context */
@@ -31,7 +31,7 @@ struct h10x_session {
   char err[1024];
 };
 static const char *const knobName[N_KNOBS] = {"cluster_stamps", "cluster_lds_budget", "cluster_first_global", "cluster_first_cap",
-                                              "cluster_big_ranks", "cluster_threads0", "cluster_budget0", "shard_row_shift", "shard_rows_fake_base", "stage_a_max_slots", "cluster_narrow_first", "index_no_pack", "shard_delta_lists", "index_priv_table", "cluster_tr_packed", "cluster_tr_est_div", "cluster_tr_class_t", "shard_reply_sort", "shard_owner_cut", "shard_overlap", "index_probed_table"};
+                                              "cluster_big_ranks", "cluster_threads0", "cluster_budget0", "shard_row_shift", "shard_rows_fake_base", "stage_a_max_slots", "cluster_narrow_first", "index_no_pack", "shard_delta_lists", "index_priv_table", "cluster_tr_packed", "cluster_tr_est_div", "cluster_tr_class_t", "shard_reply_sort", "shard_owner_cut", "shard_overlap", "index_probed_table", "fqb_slab"};
 
 static int fail(h10x_session *s, const char *fmt, ...) {
   va_list ap; va_start(ap, fmt); vsnprintf(s->err, sizeof s->err, fmt, ap); va_end(ap);
@@ -1232,6 +1232,163 @@ int h10x_session_sortFQB(h10x_session *s, const char *inPath, const char *outPat
   if (n && fwrite(out, 120, n, g) != n) rc = fail(s, "failed to write %s", outPath);
 done:
   fclose(f); if (g) fclose(g); free(in); free(out);
+  return rc;
+}
+
+/* ---- --codeCensus, --fixFQB, --fixFQBThresh: the barcode step between fq2b and --sortFQB on the packed file (fq2b.c:71-104 and the README's
+   goodcodes pipeline, README.md:44; README.md:57-62 wishes for `fq2b -10xThresh`). The records pass through the device in batches of
+   "fqb_slab" records: the host holds one batch of input and one of output, never the file. ---- */
+static void pack_init(uint8_t *sym) { memset(sym, 0, 256); sym['c'] = sym['C'] = 1; sym['g'] = sym['G'] = 2; sym['t'] = sym['T'] = 3; }   /* a, A, N, anything else: 0 (fq2b.c:27-28) */
+/* the whitelist text as fq2b-amd reads it (read10xWhitelist, fq2b.c:71-94): blank-separated words of 16 characters in line order; never touches the GPU */
+int h10x_host_whitelist_read(const char *path, uint32_t **codes, uint64_t *n, char *err, int errlen) {
+  uint8_t sym[256]; pack_init(sym);
+  *codes = 0; *n = 0;
+  FILE *f = fopen(path, "r");
+  if (!f) { if (err) snprintf(err, (size_t)errlen, "failed to open 10x whitelist file %s\n", path); return -1; }
+  size_t cap = 1 << 16, m = 0; uint32_t *c = (uint32_t *)malloc(cap * 4);
+  char word[64]; int rc = 0;
+  while (c && fscanf(f, "%63s", word) == 1) {
+    if (strlen(word) != 16) { if (err) snprintf(err, (size_t)errlen, "bad barcode line %d in %s: %s", (int)m + 1, path, word); rc = -1; break; }
+    if (m == cap) { cap *= 2; uint32_t *c2 = (uint32_t *)realloc(c, cap * 4); if (!c2) { free(c); c = 0; break; } c = c2; }
+    uint32_t v = 0; for (int i = 0; i < 16; ++i) v = (v << 2) | sym[(unsigned char)word[i]];
+    c[m++] = v;
+  }
+  fclose(f);
+  if (!c) { if (err) snprintf(err, (size_t)errlen, "out of host memory for the whitelist"); return -1; }
+  if (rc) { free(c); return rc; }
+  *codes = c; *n = m;
+  return 0;
+}
+void h10x_host_whitelist_free(uint32_t *codes) { free(codes); }
+int h10x_host_whitelist_write(const char *path, const uint32_t *codes, uint64_t n, char *err, int errlen) {
+  FILE *f = fopen(path, "w");
+  if (!f) { if (err) snprintf(err, (size_t)errlen, "failed to open output file %s", path); return -1; }
+  char line[17]; line[16] = '\n';
+  for (uint64_t i = 0; i < n; ++i) {
+    for (int b = 0; b < 16; ++b) line[15 - b] = "ACGT"[(codes[i] >> (2 * b)) & 3];     /* uSeq (fq2b.c:44-50) */
+    if (fwrite(line, 1, 17, f) != 17) { fclose(f); if (err) snprintf(err, (size_t)errlen, "failed to write %s", path); return -1; }
+  }
+  if (fclose(f)) { if (err) snprintf(err, (size_t)errlen, "failed to write %s", path); return -1; }
+  return 0;
+}
+/* the line a barcode is looked up under: the LAST line that holds it (later lines overwrite earlier ones in the reference's byte table, fq2b.c:89), 0 = absent */
+static int cmp_u64(const void *a, const void *b) { const uint64_t x = *(const uint64_t *)a, y = *(const uint64_t *)b; return x < y ? -1 : x > y; }
+int h10x_host_whitelist_lines(const uint32_t *codes, uint64_t n, const uint32_t *query, uint64_t nq, uint32_t *lines) {
+  uint64_t *k = (uint64_t *)malloc((n ? n : 1) * 8);
+  if (!k) return -1;
+  for (uint64_t i = 0; i < n; ++i) k[i] = (uint64_t)codes[i] << 32 | (uint32_t)(i + 1);
+  qsort(k, n, 8, cmp_u64);
+  for (uint64_t q = 0; q < nq; ++q) {                                                 /* the last entry of the barcode's run = its largest line */
+    const uint64_t top = (uint64_t)query[q] << 32 | 0xFFFFFFFFu;
+    uint64_t lo = 0, hi = n;
+    while (lo < hi) { const uint64_t mid = lo + (hi - lo) / 2; if (k[mid] <= top) lo = mid + 1; else hi = mid; }
+    lines[q] = lo && (uint32_t)(k[lo - 1] >> 32) == query[q] ? (uint32_t)k[lo - 1] : 0;
+  }
+  free(k);
+  return 0;
+}
+
+static uint64_t session_slab(const h10x_session *s) { const int v = h10x_session_get(s, "fqb_slab"); return v > 0 ? (uint64_t)v : (uint64_t)1 << 20; }
+typedef struct { FILE *f; const char *path; uint64_t n; } FqbFile;
+static int fqb_open(h10x_session *s, const char *path, FqbFile *in) {
+  in->path = path; in->n = 0;
+  if (!(in->f = fopen(path, "rb"))) return fail(s, "failed to open fqb file %s", path);
+  fseeko(in->f, 0, SEEK_END); const off_t bytes = ftello(in->f); fseeko(in->f, 0, SEEK_SET);
+  if (bytes % 120) { fclose(in->f); in->f = 0; return fail(s, "%s: size %lld is not a multiple of the 120-byte record", path, (long long)bytes); }
+  in->n = (uint64_t)bytes / 120;
+  if (in->n >= (uint64_t)1 << 32) { fclose(in->f); in->f = 0; return fail(s, "%s: %llu records exceed this build's 2^32 limit", path, (unsigned long long)in->n); }
+  return 0;
+}
+/* one pass over the file: its barcodes into a census, closed at thresh (the good barcodes become the context's whitelist) */
+static int census_file(h10x_session *s, FqbFile *in, int thresh, h10x_census_t *z) {
+  const uint64_t slab = session_slab(s), cap = in->n < slab ? in->n : slab;
+  uint32_t *buf = (uint32_t *)malloc(cap ? cap * 120 : 8);
+  if (!buf) return fail(s, "out of host memory for %llu bytes of records", (unsigned long long)cap * 120);
+  int rc = 0;
+  fseeko(in->f, 0, SEEK_SET);
+  if (h10x_census_begin(s->ctx, in->n)) rc = fail_ctx(s);
+  for (uint64_t at = 0; !rc && at < in->n; at += slab) {
+    const uint64_t m = in->n - at < slab ? in->n - at : slab;
+    if (fread(buf, 120, m, in->f) != m) rc = fail(s, "failed to read %s", in->path);
+    else if (h10x_census_add(s->ctx, buf, m)) rc = fail_ctx(s);
+  }
+  if (!rc && h10x_census_close(s->ctx, thresh, z)) rc = fail_ctx(s);
+  free(buf);
+  return rc;
+}
+/* one pass over the file: every batch corrected to the context's whitelist and appended to outPath */
+static int fix_file(h10x_session *s, FqbFile *in, const char *outPath, h10x_fix_stats *st, uint64_t *written) {
+  struct stat a, b;
+  if (!fstat(fileno(in->f), &a) && !stat(outPath, &b) && a.st_dev == b.st_dev && a.st_ino == b.st_ino) return fail(s, "%s: input and output are the same file", outPath);
+  const uint64_t slab = session_slab(s), cap = in->n < slab ? in->n : slab;
+  uint32_t *buf = (uint32_t *)malloc(cap ? cap * 120 : 8), *out = (uint32_t *)malloc(cap ? cap * 120 : 8);
+  FILE *g = 0; int rc = 0;
+  *written = 0;
+  if (!buf || !out) rc = fail(s, "out of host memory for %llu bytes of records", (unsigned long long)cap * 240);
+  else if (!(g = fopen(outPath, "wb"))) rc = fail(s, "failed to open output file %s", outPath);
+  fseeko(in->f, 0, SEEK_SET);
+  for (uint64_t at = 0; !rc && at < in->n; at += slab) {
+    const uint64_t m = in->n - at < slab ? in->n - at : slab; uint64_t kept = 0;
+    if (fread(buf, 120, m, in->f) != m) rc = fail(s, "failed to read %s", in->path);
+    else if (h10x_fix_fqb(s->ctx, buf, m, out, &kept, st)) rc = fail_ctx(s);
+    else if (kept && fwrite(out, 120, kept, g) != kept) rc = fail(s, "failed to write %s", outPath);
+    else *written += kept;
+  }
+  if (g && fclose(g) && !rc) rc = fail(s, "failed to write %s", outPath);
+  free(buf); free(out);
+  return rc;
+}
+/* the lines fq2b prints after a -10x run (fq2b.c:164, 170-176), from the same C expressions: nan where C prints it */
+static void fix_report(FILE *err, uint64_t written, const h10x_fix_stats *st) {
+  if (!err) return;
+  const long long n = (long long)written, nBad = (long long)st->dropped, nFixed = (long long)st->corrected;
+  fprintf(err, "written %lld read pairs %d + %d bp packed in %d word records\n", n, 151, 151, 30);
+  fprintf(err, "%lld (%.1f%%) not matching barcodes were dropped\n", nBad, 100.0 * nBad / (double)(nBad + n));
+  fprintf(err, "%lld (%.1f%%) of those that matched were error corrected\n", nFixed, 100.0 * nFixed / (double)n);
+  fprintf(err, "by base position:");
+  for (int i = 0; i < 16; ++i) fprintf(err, " %lld", (long long)st->correctedAt[i]);
+  fprintf(err, "\n");
+}
+int h10x_session_codeCensus(h10x_session *s, int thresh, const char *inPath, const char *goodPath, FILE *out) {
+  if (thresh < 1) return fail(s, "barcode threshold %d must be at least 1", thresh);
+  FqbFile in; if (fqb_open(s, inPath, &in)) return -1;
+  h10x_census_t z; int rc = 0; uint32_t *codes = 0;
+  if (!s->ctx && session_init(s)) rc = -1;
+  if (!rc) rc = census_file(s, &in, thresh, &z);
+  if (!rc && !z.nGood) rc = fail(s, "no barcode occurs at least %d times in %s", thresh, inPath);
+  if (!rc && !(codes = (uint32_t *)malloc(z.nGood * 4))) rc = fail(s, "out of host memory for %llu barcodes", (unsigned long long)z.nGood);
+  if (!rc && h10x_census_export(s->ctx, 1, codes, 0, z.nGood)) rc = fail_ctx(s);
+  if (!rc && h10x_host_whitelist_write(goodPath, codes, z.nGood, s->err, (int)sizeof s->err)) rc = -1;
+  if (!rc && out) fprintf(out, "  %llu records, %llu distinct barcodes, %llu good barcodes (at least %d records) holding %llu records\n", (unsigned long long)z.nRecords,
+                          (unsigned long long)z.nDistinct, (unsigned long long)z.nGood, thresh, (unsigned long long)z.nGoodRecords);
+  free(codes); fclose(in.f);
+  return rc;
+}
+int h10x_session_fixFQB(h10x_session *s, const char *goodPath, const char *inPath, const char *outPath, FILE *err) {
+  uint32_t *codes = 0; uint64_t nCodes = 0;
+  if (h10x_host_whitelist_read(goodPath, &codes, &nCodes, s->err, (int)sizeof s->err)) return -1;
+  if (err) fprintf(err, "read %d barcodes from file %s\n", (int)nCodes, goodPath);
+  if (!nCodes) { free(codes); return fail(s, "no barcodes in whitelist file %s", goodPath); }        /* (the reference reads an unallocated table then) */
+  FqbFile in; if (fqb_open(s, inPath, &in)) { free(codes); return -1; }
+  h10x_fix_stats st; memset(&st, 0, sizeof st); uint64_t written = 0; int rc = 0;
+  if (!s->ctx && session_init(s)) rc = -1;
+  if (!rc && h10x_whitelist_set(s->ctx, codes, nCodes)) rc = fail_ctx(s);
+  if (!rc) rc = fix_file(s, &in, outPath, &st, &written);
+  if (!rc) fix_report(err, written, &st);
+  free(codes); fclose(in.f);
+  return rc;
+}
+int h10x_session_fixFQBThresh(h10x_session *s, int thresh, const char *inPath, const char *outPath, FILE *err) {
+  if (thresh < 1) return fail(s, "barcode threshold %d must be at least 1", thresh);
+  FqbFile in; if (fqb_open(s, inPath, &in)) return -1;
+  h10x_census_t z; h10x_fix_stats st; memset(&st, 0, sizeof st); uint64_t written = 0; int rc = 0;
+  if (!s->ctx && session_init(s)) rc = -1;
+  if (!rc) rc = census_file(s, &in, thresh, &z);
+  if (!rc && !z.nGood) rc = fail(s, "no barcode occurs at least %d times in %s", thresh, inPath);
+  if (!rc && err) fprintf(err, "found %d barcodes with at least %d records in %s\n", (int)z.nGood, thresh, inPath);
+  if (!rc) rc = fix_file(s, &in, outPath, &st, &written);
+  if (!rc) fix_report(err, written, &st);
+  fclose(in.f);
   return rc;
 }
 

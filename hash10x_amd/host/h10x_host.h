@@ -76,6 +76,27 @@ int  h10x_session_codeExplore(h10x_session *s, int code, FILE *out, FILE *err);
    on the device: records ordered by their first 4 bytes, stably */
 int  h10x_session_sortFQB(h10x_session *s, const char *inPath, const char *outPath);
 
+/* the barcode step between fq2b and --sortFQB, on the packed file and on the device (additions; include/h10x.h "barcode census"):
+   --codeCensus <thresh> <in.fqb> <goodcodes> writes the barcodes (record word 0) that occur at least thresh times, one 16-letter line
+   each, ascending by packed word — the README's `gzip -dc | perl | sort | uniq -c | awk` (README.md:44) — and one line of counts to out;
+   --fixFQB <goodcodes> <in.fqb> <out.fqb> does to the records what `fq2b -10x <goodcodes>` does to the reads (fq2b.c:71-104, 157):
+   drops those without a whitelist barcode within one substitution, corrects the others to the candidate of the latest whitelist
+   line, and prints fq2b's lines to err; --fixFQBThresh <thresh> <in.fqb> <out.fqb> is both in one (README.md:62's `fq2b -10xThresh`),
+   the whitelist never leaving the device. The file passes through in batches of "fqb_slab" records (h10x_session_set; 0 = 2^20):
+   the host holds one batch. They fail for a size that is no multiple of 120, 2^32 or more records, thresh < 1, and a threshold no
+   barcode reaches (or an empty whitelist: the reference reads an unallocated table then). out / err may be NULL. */
+int  h10x_session_codeCensus(h10x_session *s, int thresh, const char *inPath, const char *goodPath, FILE *out);
+int  h10x_session_fixFQB(h10x_session *s, const char *goodPath, const char *inPath, const char *outPath, FILE *err);
+int  h10x_session_fixFQBThresh(h10x_session *s, int thresh, const char *inPath, const char *outPath, FILE *err);
+/* the whitelist text without a device: the reader of fq2b-amd (blank-separated words of 16 characters; anything but ACGTacgt packs as A;
+   codes in line order, to be freed with h10x_host_whitelist_free; -1 with "bad barcode line %d in %s: %s" or "failed to open 10x
+   whitelist file %s" in err), the writer (one 16-letter line per code), and the line a barcode is looked up under — the LAST line
+   that holds it, 0 = absent — which is what the device's set keeps (h10x_whitelist_set) */
+int  h10x_host_whitelist_read(const char *path, uint32_t **codes, uint64_t *n, char *err, int errlen);
+void h10x_host_whitelist_free(uint32_t *codes);
+int  h10x_host_whitelist_write(const char *path, const uint32_t *codes, uint64_t n, char *err, int errlen);
+int  h10x_host_whitelist_lines(const uint32_t *codes, uint64_t n, const uint32_t *query, uint64_t nq, uint32_t *lines);
+
 /* multi-GPU (include/h10x.h "multi-GPU"): one session per rank, each holding a contiguous barcode range of the sorted file
    (cut with h10x_host_partition / _partition_file; -N is applied by the launcher before cutting). Every command of a
    sharded session is collective: all ranks call it with the same arguments; the text commands print on the rank whose

@@ -9,7 +9,7 @@
  * print "FATAL ERROR: <the reference's message>" and exit(-1) like die() (utils.c:18-29). The dispatch itself is a
  * table of commands, not the reference's if-chain.
  * --interactive reads further commands from stdin, one line each, as the reference does (hash10x.c:1281-1300).
- * Additions: --device <n>, --gpus <n>, --sortFQB; the resource line also carries wall-clock seconds.
+ * Additions: --device <n>, --gpus <n>, --sortFQB, --codeCensus, --fixFQB, --fixFQBThresh; the resource line also carries wall-clock seconds.
  */
 #define _GNU_SOURCE
 #include <stdio.h>
@@ -139,6 +139,9 @@ static void usage(void) {
   fprintf(stderr, "   --device <HIP device ordinal> [0]\n");
   fprintf(stderr, "   --gpus <n> [1]: shard the barcodes of the next --readFQB / --readHash over n GPUs (devices device, device+1, ...)\n");
   fprintf(stderr, "   --sortFQB <fqb from fq2b> <sorted fqb output>: sort records by barcode on the GPU (instead of bsort -k 4 -r 120)\n");
+  fprintf(stderr, "   --codeCensus <thresh> <fqb from fq2b> <goodcodes output>: write the barcodes present at least thresh times, found on the GPU\n");
+  fprintf(stderr, "   --fixFQB <goodcodes> <fqb from fq2b> <fixed fqb output>: drop or correct records by barcode on the GPU (as fq2b -10x <goodcodes>)\n");
+  fprintf(stderr, "   --fixFQBThresh <thresh> <fqb from fq2b> <fixed fqb output>: --codeCensus and --fixFQB in one, without the goodcodes file\n");
   fprintf(stderr, "   --readFQB <sorted fqb input file name>: must have this or readHash\n");
   fprintf(stderr, "   --readHash <hash input file name>\n");
   fprintf(stderr, "   --writeHash <hash output file name>\n");
@@ -255,6 +258,9 @@ static void cmd_hashStats(char **a) { (void)a; const int bad = on_all_ranks(rank
 static int rank_codeStats(h10x_session *s, int r, void *a) { (void)a; return h10x_session_codeStats(s, r == 0 ? outFile : 0); }
 static void cmd_codeStats(char **a) { (void)a; const int bad = on_all_ranks(rank_codeStats, 0); if (bad) die_of(bad); }
 static void cmd_sortFQB(char **a) { if (h10x_session_sortFQB(team.s[0], a[0], a[1])) die_of(1); }
+static void cmd_codeCensus(char **a) { if (h10x_session_codeCensus(team.s[0], atoi(a[0]), a[1], a[2], outFile)) die_of(1); }
+static void cmd_fixFQB(char **a) { if (h10x_session_fixFQB(team.s[0], a[0], a[1], a[2], stderr)) die_of(1); }
+static void cmd_fixFQBThresh(char **a) { if (h10x_session_fixFQBThresh(team.s[0], atoi(a[0]), a[1], a[2], stderr)) die_of(1); }
 static void cmd_output(char **a) {
   if (!strcmp(a[0], "-")) outFile = stdout;
   else if (!(outFile = fopen(a[0], "w"))) { fprintf(stderr, "can't open output file %s\n", a[0]); outFile = stdout; }
@@ -293,6 +299,7 @@ static const Command commands[] = {
   {"--tables", 0, cmd_tables, 0}, {"--verbose", 0, cmd_verbose, 0},
   {"--readFQB", 1, cmd_readFQB, 0}, {"--readHash", 1, cmd_readHash, 0}, {"--writeHash", 1, cmd_writeHash, 0},
   {"--hashDepthRange", 2, cmd_hashDepthRange, 0}, {"--cluster", 2, cmd_cluster, 0}, {"--clusterSplit", 0, cmd_clusterSplit, 0},
+  {"--codeCensus", 3, cmd_codeCensus, 0}, {"--fixFQB", 3, cmd_fixFQB, 0}, {"--fixFQBThresh", 3, cmd_fixFQBThresh, 0},
   {"--sortFQB", 2, cmd_sortFQB, 0}, {"--cribBuild", 2, cmd_cribBuild, 0}, {"--clusterReport", 2, cmd_clusterReport, 0},
   {"--cribSummary", 0, cmd_cribSummary, 0}, {"--hashStats", 0, cmd_hashStats, 0}, {"--codeStats", 0, cmd_codeStats, 0},
   {"--hashInfo", 3, cmd_hashInfo, 0}, {"--hashExplore", 1, cmd_hashExplore, 0}, {"--doubleShared", 2, cmd_doubleShared, 0},

@@ -124,6 +124,34 @@ int  h10x_read_fqb_device(h10x_ctx *ctx, const uint32_t *dev_records, uint64_t n
 int  h10x_sort_fqb(h10x_ctx *ctx, const uint32_t *host_in, uint64_t n_records, uint32_t *host_out);
 int  h10x_sort_fqb_device(h10x_ctx *ctx, const uint32_t *dev_in, uint64_t n_records, uint32_t *dev_out);
 
+/* ---- barcode census and whitelist correction of unsorted .fqb records (csrc/stage_j.hip) ----
+   The barcode step between fq2b and the record sort, on packed records instead of FASTQ text. A barcode is record word 0 as
+   fq2b packs it (first base in the top two bits); whitelist order is the order of that packed value, no byte swap. Records come
+   in batches, so neither the host nor the device ever holds the file: the census keeps 4 bytes per record between batches.
+   h10x_census_begin / _add / _close replace the README's goodcodes pipeline (README.md:44, the wish of README.md:57-62: `gzip -dc | perl | sort | uniq -c |
+   awk` over the FASTQ text) — begin opens a census (nRecordsHint > 0 reserves the key array once instead of growing it), add
+   appends the barcodes of a batch, close(thresh) finds the distinct barcodes with their counts and makes the barcodes that occur
+   at least thresh times the whitelist, in ascending order (line r + 1 = r-th good barcode). thresh < 1 fails. A census without a
+   good barcode closes with nGood = 0 and leaves no whitelist. h10x_census_export copies out the distinct (goodOnly = 0) or good
+   barcodes, ascending, with their counts (NULL = skip; at most cap entries).
+   h10x_whitelist_set replaces read10xWhitelist (fq2b.c:71-94): codes in line order, a repeated code keeps its latest line.
+   h10x_fix_fqb replaces find10xBarcode for a batch (fq2b.c:96-104, 157): per record the candidates are the barcode and its 48
+   one-substitution neighbours that are in the whitelist; none: the record is dropped; otherwise the candidate of the latest line
+   wins and replaces word 0. Kept records go to out in their input order (in / out must not overlap, out holds n records);
+   *nKept = how many. acc (may be NULL) is ADDED to: dropped = nBad, corrected = nFixed, correctedAt[p] = nFixBase[p], p = position
+   of the changed base counted from the first base. The host forms move the records through the device in batches of "fqb_slab"
+   records (h10x_set_option; 0 = default 2^20); results do not depend on it. */
+typedef struct { uint64_t nRecords, nDistinct, nGood, nGoodRecords; } h10x_census_t;
+typedef struct { uint64_t dropped, corrected, correctedAt[16]; } h10x_fix_stats;
+int  h10x_census_begin(h10x_ctx *ctx, uint64_t nRecordsHint);
+int  h10x_census_add(h10x_ctx *ctx, const uint32_t *host_records, uint64_t n_records);
+int  h10x_census_add_device(h10x_ctx *ctx, const uint32_t *dev_records, uint64_t n_records);
+int  h10x_census_close(h10x_ctx *ctx, int64_t thresh, h10x_census_t *out);
+int  h10x_census_export(h10x_ctx *ctx, int goodOnly, uint32_t *codes, uint32_t *counts, uint64_t cap);
+int  h10x_whitelist_set(h10x_ctx *ctx, const uint32_t *host_codes, uint64_t n_codes);
+int  h10x_fix_fqb(h10x_ctx *ctx, const uint32_t *host_in, uint64_t n_records, uint32_t *host_out, uint64_t *nKept, h10x_fix_stats *acc);
+int  h10x_fix_fqb_device(h10x_ctx *ctx, const uint32_t *dev_in, uint64_t n_records, uint32_t *dev_out, uint64_t *nKept, h10x_fix_stats *acc);
+
 /* replaces the state that readHashFile() + fillHashTable() leave behind (hash10x.c:269-315,
    317-347): uploads the tables of a parsed .hash file and rebuilds the hash->barcode lists.
    hashDepth has hashNumber entries, blocks has nBlocks entries (entry 0 unused), clusHash is the
@@ -505,6 +533,7 @@ void *h10x_device_malloc(int device, uint64_t bytes);
 int   h10x_device_mem_info(int device, uint64_t *freeBytes, uint64_t *totalBytes);
 int   h10x_device_free(int device, void *ptr);
 int   h10x_device_upload(int device, void *dst, const void *src, uint64_t bytes);
+int   h10x_device_download(int device, void *dst, const void *src, uint64_t bytes);
 int   h10x_device_synchronize(int device);
 
 /* ---- measurement hooks (not part of the reference surface) ----
@@ -573,7 +602,8 @@ int  h10x_get_counters(h10x_ctx *ctx, h10x_counters *out);
    "shard_owner_cut" (0 default = hash owners' value ranges cut at the quantiles of the canonical-hash density, equal shares; 1 = equal value ranges),
    "shard_row_shift", "shard_rows_fake_base" (sharded list offsets beyond 32 bits on small inputs), "shard_delta_lists" (-1 default:
    the in-range barcode lists travel delta-coded where bytes are dear — more than one rank on the host-staged TCP backend, not over xGMI; 0 never; 1 always),
-   "neighbour_budget" (gathered ClusterHash records per batch of the neighbour census; 0 = default 2^26; small values force batches and hash-index windows). Unknown name: -1. */
+   "neighbour_budget" (gathered ClusterHash records per batch of the neighbour census; 0 = default 2^26; small values force batches and hash-index windows),
+   "fqb_slab" (records per device batch of h10x_census_add / h10x_fix_fqb and of the session's --codeCensus / --fixFQB / --fixFQBThresh; 0 = default 2^20). Unknown name: -1. */
 int  h10x_set_option(h10x_ctx *ctx, const char *name, int64_t value);
 
 #ifdef __cplusplus
