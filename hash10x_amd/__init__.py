@@ -208,6 +208,15 @@ def load_native():
     host.h10x_host_whitelist_free.restype = None; host.h10x_host_whitelist_free.argtypes = [vp]
     host.h10x_host_whitelist_write.argtypes = [cs, vp, cu64, cs, ci]
     host.h10x_host_whitelist_lines.argtypes = [vp, cu64, vp, cu64, vp]
+    # the molecule of every read pair, the records in molecule order (csrc/stage_k.hip)
+    hip.h10x_molecule_map.argtypes = [vp, vp, vp, cu64, vp]
+    hip.h10x_molecule_map_device.argtypes = [vp, vp, vp, cu64, vp]
+    hip.h10x_split_fqb.argtypes = [vp, vp, cu64, vp, vp, cu64]
+    hip.h10x_split_fqb_device.argtypes = [vp, vp, cu64, vp, vp, cu64]
+    host.h10x_session_moleculeMap.argtypes = [vp, cs, vp]
+    host.h10x_session_splitFQB.argtypes = [vp, cs, cs, vp]
+    host.h10x_host_write_molmap.argtypes = [cs, vp, vp, vp, cs, ci]
+    host.h10x_host_write_split_index.argtypes = [cs, vp, ctypes.c_uint32, ctypes.c_uint32, cs, ci]
     # mosh sets (csrc/stage_g.hip, host/mosh_host.c)
     pvp, ci32, cu32 = ctypes.POINTER(vp), ctypes.c_int32, ctypes.c_uint32
     hip.h10x_factors_from_seed.restype = None; hip.h10x_factors_from_seed.argtypes = [ci32, ctypes.POINTER(cu64), ctypes.POINTER(cu64)]
@@ -398,6 +407,42 @@ def partition(records, parts):
     if load_native()[1].h10x_host_partition(r.ctypes.data, r.size // 30, parts, cut):
         raise Hash10xError("partition failed")
     return [int(x) for x in cut]
+
+
+def read_molecule_map(path):
+    """A .mol file of --moleculeMap: (mol, slot, info), as Hash10x.molecule_map() returns them."""
+    with open(path, "rb") as f:
+        data = f.read()
+    if len(data) < 32 or data[:4] != b"10XM":
+        raise Hash10xError("%s is not a molecule map (magic 10XM)" % path)
+    version = int.from_bytes(data[4:8], "little")
+    if version != 1:
+        raise Hash10xError("%s: molecule map version %d, this reader knows 1" % (path, version))
+    info = {"nRecords": int.from_bytes(data[8:16], "little"), "nClustered": int.from_bytes(data[24:32], "little"),
+            "nBlocks": int.from_bytes(data[16:20], "little"), "nMolecules": int.from_bytes(data[20:24], "little")}
+    if len(data) != 32 + 8 * info["nRecords"]:
+        raise Hash10xError("%s: %d bytes, %d records need %d" % (path, len(data), info["nRecords"], 32 + 8 * info["nRecords"]))
+    pairs = np.frombuffer(data, dtype="<u4", offset=32).reshape(-1, 2)
+    return pairs[:, 0].copy(), pairs[:, 1].copy(), info
+
+
+def read_split_index(path):
+    """The .idx file beside a split .fqb: (start, nBlocks, nMolecules); records [start[m], start[m + 1]) are block m's."""
+    with open(path, "rb") as f:
+        data = f.read()
+    if len(data) < 16 or data[:4] != b"10XS":
+        raise Hash10xError("%s is not a split index (magic 10XS)" % path)
+    version = int.from_bytes(data[4:8], "little")
+    if version != 1:
+        raise Hash10xError("%s: split index version %d, this reader knows 1" % (path, version))
+    n_blocks, n_mol = int.from_bytes(data[8:12], "little"), int.from_bytes(data[12:16], "little")
+    if len(data) != 16 + 8 * (n_blocks + n_mol + 1):
+        raise Hash10xError("%s: %d bytes, %d starts need %d" % (path, len(data), n_blocks + n_mol + 1, 16 + 8 * (n_blocks + n_mol + 1)))
+    return np.frombuffer(data, dtype="<u8", offset=16).copy(), n_blocks, n_mol
+
+
+class _MolInfo(ctypes.Structure):
+    _fields_ = [("nRecords", ctypes.c_uint64), ("nClustered", ctypes.c_uint64), ("nBlocks", ctypes.c_uint32), ("nMolecules", ctypes.c_uint32)]
 
 
 class Hash10x:
@@ -850,6 +895,48 @@ class Hash10x:
             self._chk_ctx(self._hip.h10x_fix_fqb(ctx, r.ctypes.data, r.size // 30, buf.ctypes.data, ctypes.byref(kept), st.ctypes.data))
             out = buf[:kept.value * 30].reshape(-1, 30)
         return out, {"dropped": int(st[0]), "corrected": int(st[1]), "correctedAt": [int(v) for v in st[2:]]}
+
+    # ---- the molecule of every read pair (h10x_molecule_map / h10x_split_fqb: hash10x.c:897-920, 979-989 per record) ----
+    def molecule_map(self):
+        """After cluster(), before cluster_split(): (mol, slot, info). Record i of the sorted file the state was read from belongs to
+        block mol[i] of the state cluster_split() would make — a new block (mol >= info["nBlocks"]) for a clustered read pair, its
+        own barcode otherwise — as that block's read number slot[i]. info = {"nRecords", "nClustered", "nBlocks", "nMolecules"}."""
+        ctx = self._ctx()
+        if not ctx:
+            raise Hash10xError("moleculeMap: no hash state loaded: use readFQB or readHash first")
+        z = _MolInfo()
+        self._chk_ctx(self._hip.h10x_molecule_map(ctx, None, None, 0, ctypes.byref(z)))
+        n = int(z.nRecords)
+        mol, slot = np.zeros(max(n, 1), dtype=np.uint32), np.zeros(max(n, 1), dtype=np.uint32)
+        self._chk_ctx(self._hip.h10x_molecule_map(ctx, mol.ctypes.data, slot.ctypes.data, n, ctypes.byref(z)))
+        return mol[:n], slot[:n], {k: int(getattr(z, k)) for k, _ in _MolInfo._fields_}
+
+    def split_fqb(self, records):
+        """The records of the sorted file the state was read from (a host array or DeviceRecords, exactly nRecords of them) in split
+        order: (records_out, start). records_out[start[m]: start[m + 1]] are the read pairs of block m after cluster_split(), a
+        molecule's in slot order; records_out is an (n, 30) uint32 array, or a DeviceRecords for DeviceRecords."""
+        ctx = self._ctx()
+        if not ctx:
+            raise Hash10xError("splitFQB: no hash state loaded: use readFQB or readHash first")
+        z = _MolInfo()
+        self._chk_ctx(self._hip.h10x_molecule_map(ctx, None, None, 0, ctypes.byref(z)))
+        start = np.zeros(int(z.nBlocks) + int(z.nMolecules) + 1, dtype=np.uint64)
+        if isinstance(records, DeviceRecords):
+            out = DeviceRecords(np.zeros(0, dtype=np.uint32), records.device, _words=records.n_records * 30)
+            try:
+                self._chk_ctx(self._hip.h10x_split_fqb_device(ctx, records.ptr, records.n_records, out.ptr, start.ctypes.data, start.size))
+            except Hash10xError:
+                out.free()
+                raise
+            out.n_records = records.n_records
+        else:
+            r = np.ascontiguousarray(records, dtype=np.uint32).reshape(-1)
+            if r.size % 30:
+                raise Hash10xError("records: %d words are no multiple of the 30-word record" % r.size)
+            buf = np.zeros(max(r.size, 30), dtype=np.uint32)
+            self._chk_ctx(self._hip.h10x_split_fqb(ctx, r.ctypes.data, r.size // 30, buf.ctypes.data, start.ctypes.data, start.size))
+            out = buf[:r.size].reshape(-1, 30)
+        return out, start
 
     def export_within(self):
         """hashWithinRange[0 .. hashNumber) as uint8 (fails before --hashDepthRange)."""

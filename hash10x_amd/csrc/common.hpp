@@ -250,6 +250,7 @@ struct Ctx {
   DevBuf<u32> censusCodes, censusCounts, censusGoodCodes, censusGoodCounts; u64 censusDistinct = 0, censusGood = 0; bool censusClosed = false;
   DevBuf<u64> wlSlots; u64 wlMask = 0, wlCodes = 0; bool haveWhitelist = false;
   int64_t optFqbSlab = 0;     // records per device batch of the host forms of the census and the fix (0 = default 2^22); results do not depend on it
+  int64_t optMolGlobal = 0;   // testing knob: 1 = the molecule map keeps first[] of every clustered block in its HBM scratch slice, also where it would fit LDS (stage_k.hip)
   // streaming ingest (h10x_ingest_fqb): the record image grows on the device as the chunks arrive
   DevBuf<u32> ingestBuf; u64 ingestRecords = 0, ingestCap = 0; bool ingestAsync = false;   // ingestAsync: chunks came through h10x_ingest_fqb_async (the closing call then checks the count)
   static constexpr int INGEST_SLOTS = 8; hipEvent_t ingestEv[INGEST_SLOTS] = {};   // h10x_ingest_fqb_async: one event per caller's buffer
@@ -452,6 +453,9 @@ int stageJ_censusExport(Ctx *c, int goodOnly, u32 *codes, u32 *counts, u64 cap);
 int stageJ_whitelistSet(Ctx *c, const u32 *hostCodes, u64 n);
 int stageJ_fix(Ctx *c, const u32 *dIn, u64 n, u32 *dOut, u64 *nKept, h10x_fix_stats *acc);
 u64 stageJ_slab(const Ctx *c);
+int stageK_map(Ctx *c, u32 *dMol, u32 *dSlot, u64 cap, h10x_molmap_info *info);   // device arrays (either may be null)
+int stageK_records(Ctx *c, u64 *nRecords);
+int stageK_split(Ctx *c, const u32 *dIn, u64 n, u32 *dOut, u64 *hostStart, u64 startCap);
 int shard_allreduceU64(Ctx *c, u64 *v, u32 n, int op);
 int shard_gatherBytes(Ctx *c, const void *send, u64 nbytes, void *recv, u64 cap, u64 *counts);
 int shard_exchangeRows(Ctx *c);

@@ -780,6 +780,52 @@ int h10x_fix_fqb(h10x_ctx *h, const uint32_t *in, uint64_t n, uint32_t *out, uin
   return 0;
 }
 
+// ---- the molecule of every read pair and the records in molecule order (stage_k.hip): what --clusterReport counts (hash10x.c:897-920) and --clusterSplit
+// renumbers (hash10x.c:979-989), per record of the file ----
+int h10x_molecule_map_device(h10x_ctx *h, uint32_t *dMol, uint32_t *dSlot, uint64_t cap, h10x_molmap_info *info) {
+  if (!h) return -1;
+  Ctx &c = h->c; H10X_TRY(enter(c));
+  return stageK_map(&c, dMol, dSlot, cap, info);
+}
+int h10x_molecule_map(h10x_ctx *h, uint32_t *mol, uint32_t *slot, uint64_t cap, h10x_molmap_info *info) {
+  if (!h) return -1;
+  Ctx &c = h->c; H10X_TRY(enter(c));
+  if (!mol && !slot) return stageK_map(&c, nullptr, nullptr, 0, info);
+  u64 R = 0;
+  H10X_TRY(stageK_records(&c, &R));
+  if (cap < R) return c.fail("moleculeMap: room for %llu entries, the state holds %llu records", (u64)cap, R);
+  DevBuf<u32> dMol, dSlot;
+  if (mol) H10X_HIP(&c, dMol.alloc(R));
+  if (slot) H10X_HIP(&c, dSlot.alloc(R));
+  H10X_TRY(stageK_map(&c, mol ? dMol.p : nullptr, slot ? dSlot.p : nullptr, R, info));
+  if (mol && R) H10X_HIP(&c, hipMemcpyAsync(mol, dMol.p, R * 4, hipMemcpyDeviceToHost, c.stream));
+  if (slot && R) H10X_HIP(&c, hipMemcpyAsync(slot, dSlot.p, R * 4, hipMemcpyDeviceToHost, c.stream));
+  H10X_HIP(&c, hipStreamSynchronize(c.stream));
+  return 0;
+}
+int h10x_split_fqb_device(h10x_ctx *h, const uint32_t *dIn, uint64_t n, uint32_t *dOut, uint64_t *start, uint64_t startCap) {
+  if (!h) return -1;
+  Ctx &c = h->c; H10X_TRY(enter(c));
+  if (n && (!dIn || !dOut)) return c.fail("h10x_split_fqb_device: null buffer");
+  return stageK_split(&c, dIn, n, dOut, (u64 *)start, startCap);
+}
+int h10x_split_fqb(h10x_ctx *h, const uint32_t *in, uint64_t n, uint32_t *out, uint64_t *start, uint64_t startCap) {
+  if (!h) return -1;
+  Ctx &c = h->c; H10X_TRY(enter(c));
+  if (n && (!in || !out)) return c.fail("h10x_split_fqb: null buffer");
+  u64 R = 0;
+  H10X_TRY(stageK_records(&c, &R));                                                    // the refusals and the size, before anything is uploaded
+  if (n != R) return c.fail("splitFQB: %llu records given, the state was read from %llu", (u64)n, R);
+  if (n) { const uintptr_t a = (uintptr_t)in, b = (uintptr_t)out; if (a < b + n * 120 && b < a + n * 120) return c.fail("splitFQB: the input and output buffers overlap"); }
+  DevBuf<u32> dIn, dOut;
+  H10X_HIP(&c, dIn.alloc(n * 30)); H10X_HIP(&c, dOut.alloc(n * 30));
+  if (n) H10X_HIP(&c, hipMemcpyAsync(dIn.p, in, n * 120, hipMemcpyHostToDevice, c.stream));
+  H10X_TRY(stageK_split(&c, dIn.p, n, dOut.p, (u64 *)start, startCap));
+  if (n) H10X_HIP(&c, hipMemcpyAsync(out, dOut.p, n * 120, hipMemcpyDeviceToHost, c.stream));
+  H10X_HIP(&c, hipStreamSynchronize(c.stream));
+  return 0;
+}
+
 int h10x_crib_genome(h10x_ctx *h, const uint8_t *codes, const uint64_t *seqStart, uint32_t nSeq, int which, uint64_t *nPresent, uint64_t *nAbsent) {
   if (!h) return -1;
   Ctx &c = h->c; H10X_TRY(enter(c));
@@ -912,6 +958,7 @@ int h10x_set_option(h10x_ctx *h, const char *name, int64_t value) {
   if (!strcmp(name, "shard_owner_cut")) { if (value < 0 || value > 1) return h->c.fail("shard_owner_cut must be 0 or 1"); h->c.optOwnerCut = value; return 0; }
   if (!strcmp(name, "shard_delta_lists")) { if (value < -1 || value > 1) return h->c.fail("shard_delta_lists must be -1, 0 or 1"); h->c.optDeltaLists = value; return 0; }
   if (!strcmp(name, "shard_rows_fake_base")) { if (value < 0) return h->c.fail("shard_rows_fake_base must be >= 0"); h->c.optRowsFakeBase = value; return 0; }
+  if (!strcmp(name, "molmap_global")) { if (value < 0 || value > 1) return h->c.fail("molmap_global must be 0 or 1"); h->c.optMolGlobal = value; return 0; }
   if (!strcmp(name, "fqb_slab")) { if (value < 0 || value > (1 << 28)) return h->c.fail("fqb_slab must be 0..2^28"); h->c.optFqbSlab = value; return 0; }
   if (!strcmp(name, "neighbour_budget")) { if (value < 0) return h->c.fail("neighbour_budget must be >= 0"); h->c.optNbBudget = value; return 0; }
   return h->c.fail("unknown option %s", name);

@@ -17,7 +17,7 @@
 #define ARRAY_MAGIC 8918274                            /* array.h:56 */
 typedef struct { int32_t magic, pad0; uint64_t base; int32_t dim, size, max, pad1; } array_hdr;   /* array.h:41-50 */
 
-enum { N_KNOBS = 22 };
+enum { N_KNOBS = 23 };
 struct h10x_session {
   int k, w, r, B, N, chunk, ct, device;                /* params (hash10x.c:25-33) */
   int timing;                                          /* measurement hook: enable hipEvent timers on every new context */
@@ -31,7 +31,7 @@ struct h10x_session {
   char err[1024];
 };
 static const char *const knobName[N_KNOBS] = {"cluster_stamps", "cluster_lds_budget", "cluster_first_global", "cluster_first_cap",
-                                              "cluster_big_ranks", "cluster_threads0", "cluster_budget0", "shard_row_shift", "shard_rows_fake_base", "stage_a_max_slots", "cluster_narrow_first", "index_no_pack", "shard_delta_lists", "index_priv_table", "cluster_tr_packed", "cluster_tr_est_div", "cluster_tr_class_t", "shard_reply_sort", "shard_owner_cut", "shard_overlap", "index_probed_table", "fqb_slab"};
+                                              "cluster_big_ranks", "cluster_threads0", "cluster_budget0", "shard_row_shift", "shard_rows_fake_base", "stage_a_max_slots", "cluster_narrow_first", "index_no_pack", "shard_delta_lists", "index_priv_table", "cluster_tr_packed", "cluster_tr_est_div", "cluster_tr_class_t", "shard_reply_sort", "shard_owner_cut", "shard_overlap", "index_probed_table", "fqb_slab", "molmap_global"};
 
 static int fail(h10x_session *s, const char *fmt, ...) {
   va_list ap; va_start(ap, fmt); vsnprintf(s->err, sizeof s->err, fmt, ap); va_end(ap);
@@ -1232,6 +1232,87 @@ int h10x_session_sortFQB(h10x_session *s, const char *inPath, const char *outPat
   if (n && fwrite(out, 120, n, g) != n) rc = fail(s, "failed to write %s", outPath);
 done:
   fclose(f); if (g) fclose(g); free(in); free(out);
+  return rc;
+}
+
+/* ---- --moleculeMap, --splitFQB: the molecule of every read pair of the sorted file, and the file in molecule order (include/h10x.h "the molecule of every
+   read pair"; what --clusterReport counts and --clusterSplit renumbers, hash10x.c:897-920, 979-989, written per record). The two small formats are written
+   by plain functions over arrays, which never touch the GPU. ---- */
+static int put_err(char *err, int errlen, const char *fmt, const char *path) { if (err) snprintf(err, (size_t)errlen, fmt, path); return -1; }
+int h10x_host_write_molmap(const char *path, const uint32_t *mol, const uint32_t *slot, const h10x_molmap_info *info, char *err, int errlen) {
+  FILE *f = fopen(path, "wb");
+  if (!f) return put_err(err, errlen, "failed to open output file %s", path);
+  unsigned char head[32]; const uint32_t version = 1;
+  memcpy(head, "10XM", 4); memcpy(head + 4, &version, 4); memcpy(head + 8, &info->nRecords, 8); memcpy(head + 16, &info->nBlocks, 4);
+  memcpy(head + 20, &info->nMolecules, 4); memcpy(head + 24, &info->nClustered, 8);
+  int ok = fwrite(head, 1, 32, f) == 32;
+  enum { RUN = 1 << 16 };
+  uint32_t *pair = (uint32_t *)malloc((size_t)RUN * 8);
+  if (!pair) { fclose(f); return put_err(err, errlen, "out of host memory writing %s", path); }
+  for (uint64_t at = 0; ok && at < info->nRecords; at += RUN) {
+    const uint64_t m = info->nRecords - at < RUN ? info->nRecords - at : RUN;
+    for (uint64_t i = 0; i < m; ++i) { pair[2 * i] = mol[at + i]; pair[2 * i + 1] = slot[at + i]; }
+    ok = fwrite(pair, 8, m, f) == m;
+  }
+  free(pair);
+  if (fclose(f)) ok = 0;
+  return ok ? 0 : put_err(err, errlen, "failed to write %s", path);
+}
+int h10x_host_write_split_index(const char *path, const uint64_t *start, uint32_t nBlocks, uint32_t nMolecules, char *err, int errlen) {
+  FILE *f = fopen(path, "wb");
+  if (!f) return put_err(err, errlen, "failed to open output file %s", path);
+  unsigned char head[16]; const uint32_t version = 1; const uint64_t n = (uint64_t)nBlocks + nMolecules + 1;
+  memcpy(head, "10XS", 4); memcpy(head + 4, &version, 4); memcpy(head + 8, &nBlocks, 4); memcpy(head + 12, &nMolecules, 4);
+  int ok = fwrite(head, 1, 16, f) == 16 && fwrite(start, 8, n, f) == n;
+  if (fclose(f)) ok = 0;
+  return ok ? 0 : put_err(err, errlen, "failed to write %s", path);
+}
+static int one_rank(h10x_session *s, const char *name) {
+  if (!s->ctx) return fail(s, "%s: no hash state loaded: use readFQB or readHash first", name);
+  h10x_shard_info_t z; if (h10x_shard_info(s->ctx, &z)) return fail_ctx(s);
+  if (z.nranks > 1) return fail(s, "%s does not run on a sharded session (--gpus > 1)", name);
+  return 0;
+}
+int h10x_session_moleculeMap(h10x_session *s, const char *outPath, FILE *out) {
+  if (one_rank(s, "moleculeMap")) return -1;
+  h10x_molmap_info info; memset(&info, 0, sizeof info);
+  if (h10x_molecule_map(s->ctx, 0, 0, 0, &info)) return fail_ctx(s);                   /* the refusals and R */
+  const size_t n = info.nRecords ? (size_t)info.nRecords : 1;
+  uint32_t *mol = (uint32_t *)malloc(n * 4), *slot = (uint32_t *)malloc(n * 4);
+  int rc = 0;
+  if (!mol || !slot) rc = fail(s, "out of host memory for the map of %llu records", (unsigned long long)info.nRecords);
+  else if (h10x_molecule_map(s->ctx, mol, slot, info.nRecords, &info)) rc = fail_ctx(s);
+  else if (h10x_host_write_molmap(outPath, mol, slot, &info, s->err, (int)sizeof s->err)) rc = -1;
+  else if (out) fprintf(out, "  mapped %llu read pairs: %llu in %u molecules, %llu unclustered, %u barcodes\n", (unsigned long long)info.nRecords,
+                        (unsigned long long)info.nClustered, info.nMolecules, (unsigned long long)(info.nRecords - info.nClustered), info.nBlocks ? info.nBlocks - 1 : 0);
+  free(mol); free(slot);
+  return rc;
+}
+/* the whole image at once, as --sortFQB */
+int h10x_session_splitFQB(h10x_session *s, const char *inPath, const char *outPath, FILE *out) {
+  if (one_rank(s, "splitFQB")) return -1;
+  h10x_molmap_info info; memset(&info, 0, sizeof info);
+  if (h10x_molecule_map(s->ctx, 0, 0, 0, &info)) return fail_ctx(s);
+  FILE *f = fopen(inPath, "rb");
+  if (!f) return fail(s, "failed to open fqb file %s", inPath);
+  fseeko(f, 0, SEEK_END); const off_t bytes = ftello(f); fseeko(f, 0, SEEK_SET);
+  const uint64_t nFile = (uint64_t)bytes / 120, n = info.nRecords, nStart = (uint64_t)info.nBlocks + info.nMolecules + 1;
+  int rc = 0; FILE *g = 0; uint32_t *in = 0, *res = 0; uint64_t *start = 0; char *idxPath = 0;
+  if (bytes % 120) { rc = fail(s, "%s: size %lld is not a multiple of the 120-byte record", inPath, (long long)bytes); goto done; }
+  if (nFile < n) { rc = fail(s, "%s holds %llu records, the state was read from %llu", inPath, (unsigned long long)nFile, (unsigned long long)n); goto done; }
+  in = (uint32_t *)malloc(n ? (size_t)n * 120 : 8); res = (uint32_t *)malloc(n ? (size_t)n * 120 : 8); start = (uint64_t *)malloc((size_t)nStart * 8);
+  idxPath = (char *)malloc(strlen(outPath) + 5);
+  if (!in || !res || !start || !idxPath) { rc = fail(s, "out of host memory for %llu bytes of records", (unsigned long long)n * 120); goto done; }
+  if (n && fread(in, 120, n, f) != n) { rc = fail(s, "failed to read %s", inPath); goto done; }
+  if (h10x_split_fqb(s->ctx, in, n, res, start, nStart)) { rc = fail(s, "%s: %s", inPath, h10x_last_error(s->ctx)); goto done; }
+  if (!(g = fopen(outPath, "wb"))) { rc = fail(s, "failed to open output file %s", outPath); goto done; }
+  if (n && fwrite(res, 120, n, g) != n) { rc = fail(s, "failed to write %s", outPath); goto done; }
+  sprintf(idxPath, "%s.idx", outPath);
+  if (h10x_host_write_split_index(idxPath, start, info.nBlocks, info.nMolecules, s->err, (int)sizeof s->err)) { rc = -1; goto done; }
+  if (out && nFile > n) fprintf(out, "  %llu records beyond the %llu the state was read from are left out\n", (unsigned long long)(nFile - n), (unsigned long long)n);
+done:
+  fclose(f); if (g && fclose(g) && !rc) rc = fail(s, "failed to write %s", outPath);
+  free(in); free(res); free(start); free(idxPath);
   return rc;
 }
 

@@ -97,6 +97,19 @@ void h10x_host_whitelist_free(uint32_t *codes);
 int  h10x_host_whitelist_write(const char *path, const uint32_t *codes, uint64_t n, char *err, int errlen);
 int  h10x_host_whitelist_lines(const uint32_t *codes, uint64_t n, const uint32_t *query, uint64_t nq, uint32_t *lines);
 
+/* the molecule of every read pair (additions; include/h10x.h "the molecule of every read pair"), after --cluster and before --clusterSplit:
+   --moleculeMap <out.mol> writes a 32-byte header (magic "10XM", u32 version 1, u64 nRecords, u32 nBlocks, u32 nMolecules, u64 nClustered) and nRecords
+   pairs {u32 mol, u32 slot} in the order of the sorted file the state was read from, and one line of counts to out;
+   --splitFQB <in.fqb> <out.fqb> writes the records of in.fqb — that file — in split order (the whole image at once, as --sortFQB) and <out.fqb>.idx: magic
+   "10XS", u32 version 1, u32 nBlocks, u32 nMolecules, then nBlocks + nMolecules + 1 u64 starts: the records of post-split block m are [start[m],
+   start[m + 1]). A file with fewer records than the state was read from fails; records beyond them (a -N cut) are left out, with one line to out
+   saying how many. Both fail without a state, on a sharded session and after --clusterSplit. All values little-endian. out may be NULL.
+   h10x_host_write_molmap / _split_index write the two formats from arrays and never touch the GPU (-1 with the message in err). */
+int  h10x_session_moleculeMap(h10x_session *s, const char *outPath, FILE *out);
+int  h10x_session_splitFQB(h10x_session *s, const char *inPath, const char *outPath, FILE *out);
+int  h10x_host_write_molmap(const char *path, const uint32_t *mol, const uint32_t *slot, const h10x_molmap_info *info, char *err, int errlen);
+int  h10x_host_write_split_index(const char *path, const uint64_t *start, uint32_t nBlocks, uint32_t nMolecules, char *err, int errlen);
+
 /* multi-GPU (include/h10x.h "multi-GPU"): one session per rank, each holding a contiguous barcode range of the sorted file
    (cut with h10x_host_partition / _partition_file; -N is applied by the launcher before cutting). Every command of a
    sharded session is collective: all ranks call it with the same arguments; the text commands print on the rank whose

@@ -152,6 +152,29 @@ int  h10x_whitelist_set(h10x_ctx *ctx, const uint32_t *host_codes, uint64_t n_co
 int  h10x_fix_fqb(h10x_ctx *ctx, const uint32_t *host_in, uint64_t n_records, uint32_t *host_out, uint64_t *nKept, h10x_fix_stats *acc);
 int  h10x_fix_fqb_device(h10x_ctx *ctx, const uint32_t *dev_in, uint64_t n_records, uint32_t *dev_out, uint64_t *nKept, h10x_fix_stats *acc);
 
+/* ---- the molecule of every read pair, and the records in molecule order (csrc/stage_k.hip) ----
+   The reference stops at the hash level: --clusterReport counts the reads of a cluster (hash10x.c:897-920) and --clusterSplit renumbers the
+   reads of each new block (hash10x.c:979-989); neither result is written per read. Both calls work on the state after h10x_cluster and
+   before h10x_cluster_split. nCodes = nBlocks (slot 0 unused); record base[c] + r of the sorted file the state was read from (base[c] =
+   sum of nRead over blocks 1 .. c-1, R = base[nCodes] records) is read pair r of block c. A ClusterHash record of block c is clustered with
+   label subCluster when 1 <= subCluster <= nSubCluster[c]; a read's label L is that of its first clustered record in block order.
+   h10x_molecule_map: per record mol = nCodes - 1 + (sub-clusters of the blocks before c) + L, the block number h10x_cluster_split gives
+     the cluster, and slot = the number of clustered reads of the block with the same label whose first clustered record lies earlier (the
+     order of ++new2[clus].nRead, hash10x.c:984-985); an unclustered read has mol = c, slot = r. Arrays of at least R entries (cap says how
+     many there are; either may be NULL, both NULL = info only). info: R, the reads with a molecule, nCodes and M = all sub-clusters.
+   h10x_split_fqb: the records in split order: those of molecule m at start[m] + slot, those left in parent c at start[c] + (unclustered
+     records of c in front), start[0 .. nBlocks + nMolecules] = exclusive sum of the records per post-split block (start[m + 1] - start[m] =
+     nRead of block m after h10x_cluster_split, and its ClusterHash (hash, read r) refers to record start[m] + r). n_records must be R,
+     startCap at least nBlocks + nMolecules + 1, in / out must not overlap. Before anything is written the records are checked against the
+     state: a block whose records do not all carry word 0 of its first record (unless that is 0, the all-A barcode: hash10x.c:212) fails.
+   All four fail without a state, on a sharded context, after h10x_cluster_split (a block with clusterParent != 0), for a clustered block
+   of more than 65536 read pairs (the 16-bit read numbers wrap, hash10x.c:180) and for R >= 2^32. _device: arrays in device memory. */
+typedef struct { uint64_t nRecords, nClustered; uint32_t nBlocks, nMolecules; } h10x_molmap_info;
+int  h10x_molecule_map(h10x_ctx *ctx, uint32_t *mol, uint32_t *slot, uint64_t cap, h10x_molmap_info *info);
+int  h10x_molecule_map_device(h10x_ctx *ctx, uint32_t *dev_mol, uint32_t *dev_slot, uint64_t cap, h10x_molmap_info *info);
+int  h10x_split_fqb(h10x_ctx *ctx, const uint32_t *host_in, uint64_t n_records, uint32_t *host_out, uint64_t *start, uint64_t startCap);
+int  h10x_split_fqb_device(h10x_ctx *ctx, const uint32_t *dev_in, uint64_t n_records, uint32_t *dev_out, uint64_t *start, uint64_t startCap);
+
 /* replaces the state that readHashFile() + fillHashTable() leave behind (hash10x.c:269-315,
    317-347): uploads the tables of a parsed .hash file and rebuilds the hash->barcode lists.
    hashDepth has hashNumber entries, blocks has nBlocks entries (entry 0 unused), clusHash is the
@@ -603,6 +626,7 @@ int  h10x_get_counters(h10x_ctx *ctx, h10x_counters *out);
    "shard_row_shift", "shard_rows_fake_base" (sharded list offsets beyond 32 bits on small inputs), "shard_delta_lists" (-1 default:
    the in-range barcode lists travel delta-coded where bytes are dear — more than one rank on the host-staged TCP backend, not over xGMI; 0 never; 1 always),
    "neighbour_budget" (gathered ClusterHash records per batch of the neighbour census; 0 = default 2^26; small values force batches and hash-index windows),
+   "molmap_global" (1 = the molecule map keeps the first-clustered-position table of every clustered block in device memory, also where it fits LDS: tests of that form),
    "fqb_slab" (records per device batch of h10x_census_add / h10x_fix_fqb and of the session's --codeCensus / --fixFQB / --fixFQBThresh; 0 = default 2^20). Unknown name: -1. */
 int  h10x_set_option(h10x_ctx *ctx, const char *name, int64_t value);
 
