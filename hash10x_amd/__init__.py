@@ -217,6 +217,11 @@ def load_native():
     host.h10x_session_splitFQB.argtypes = [vp, cs, cs, vp]
     host.h10x_host_write_molmap.argtypes = [cs, vp, vp, vp, cs, ci]
     host.h10x_host_write_split_index.argtypes = [cs, vp, ctypes.c_uint32, ctypes.c_uint32, cs, ci]
+    # the share graph (csrc/stage_l.hip)
+    hip.h10x_share_graph_run.argtypes = [vp, ctypes.c_int64, ctypes.c_uint32, ctypes.c_uint32, vp]
+    hip.h10x_share_graph_get.argtypes = [vp, vp, vp, vp, cu64]
+    hip.h10x_share_graph_get_device.argtypes = [vp, vp, vp, vp, cu64]
+    host.h10x_session_shareGraph.argtypes = [vp, ci, cs, vp]
     # mosh sets (csrc/stage_g.hip, host/mosh_host.c)
     pvp, ci32, cu32 = ctypes.POINTER(vp), ctypes.c_int32, ctypes.c_uint32
     hip.h10x_factors_from_seed.restype = None; hip.h10x_factors_from_seed.argtypes = [ci32, ctypes.POINTER(cu64), ctypes.POINTER(cu64)]
@@ -938,12 +943,60 @@ class Hash10x:
             out = buf[:r.size].reshape(-1, 30)
         return out, start
 
+    # ---- the share graph (h10x_share_graph_run / _get): every block's sharing blocks at a threshold, one census ----
+    def share_graph(self, min_share, code_min=1, code_max=0):
+        """The blocks sharing at least min_share good hashes with each block of [code_min, code_max) (code_max = 0: nBlocks), in CSR
+        form: (offsets uint64[code_max - code_min + 1], block uint32[], count uint32[]); the row of block code_min + i is
+        [offsets[i], offsets[i + 1]), ascending in block, count = countShare as code_share gives it. The figures of the run (rows,
+        listEntries, entriesRead, maxCount, batches, windows, codeMin, codeMax, nBlocks) are kept in self.share_graph_info."""
+        ctx = self._ctx()
+        if not ctx:
+            raise Hash10xError("shareGraph: no hash state loaded: use readFQB or readHash first")
+        z = np.zeros(1, dtype=_SHARE_GRAPH_INFO)
+        self._chk_ctx(self._hip.h10x_share_graph_run(ctx, int(min_share), int(code_min), int(code_max), z.ctypes.data))
+        self.share_graph_info = {n: int(z[n][0]) for n in _SHARE_GRAPH_INFO.names}
+        m = self.share_graph_info["rows"]
+        off = np.zeros(self.share_graph_info["codeMax"] - self.share_graph_info["codeMin"] + 1, dtype=np.uint64)
+        blk, cnt = np.zeros(max(m, 1), dtype=np.uint32), np.zeros(max(m, 1), dtype=np.uint32)
+        self._chk_ctx(self._hip.h10x_share_graph_get(ctx, off.ctypes.data, blk.ctypes.data, cnt.ctypes.data, m))
+        return off, blk[:m], cnt[:m]
+
+    def write_share_graph(self, min_share, path, out=None):
+        """--shareGraph <min_share> <path>: the graph of all blocks written range by range (read_share_graph reads it); one line of
+        counts is appended to the file `out`."""
+        self._with_file(out, lambda f: self._host.h10x_session_shareGraph(self._s, int(min_share), os.fsencode(path), f))
+
     def export_within(self):
         """hashWithinRange[0 .. hashNumber) as uint8 (fails before --hashDepthRange)."""
         z = self.sizes()
         w = np.zeros(max(z["hashNumber"], 1), dtype=np.uint8)
         self._chk_ctx(self._hip.h10x_export_slice(self._ctx(), 7, 0, z["hashNumber"], w.ctypes.data))
         return w[:z["hashNumber"]]
+
+
+_SHARE_GRAPH_INFO = np.dtype([("rows", "<u8"), ("listEntries", "<u8"), ("entriesRead", "<u8"), ("maxCount", "<u4"), ("batches", "<u4"), ("windows", "<u4"),
+                              ("codeMin", "<u4"), ("codeMax", "<u4"), ("nBlocks", "<u4")])
+
+
+def read_share_graph(path):
+    """A --shareGraph file (magic "10XG", u32 version 1, u32 nBlocks, u32 minShare, u64 rows, nBlocks + 1 u64 offsets, rows pairs
+    {u32 block, u32 count}, little-endian; needs no device): ({"version", "nBlocks", "minShare", "rows"}, offsets, block, count). The row
+    of block c is [offsets[c], offsets[c + 1]). Raises Hash10xError for a file that is not one or does not hold together."""
+    with open(path, "rb") as f:
+        data = f.read()
+    if len(data) < 24 or data[:4] != b"10XG":
+        raise Hash10xError("%s: not a share graph file (magic 10XG)" % path)
+    version, n_blocks, min_share = (int(v) for v in np.frombuffer(data, dtype="<u4", count=3, offset=4))
+    rows = int(np.frombuffer(data, dtype="<u8", count=1, offset=16)[0])
+    if version != 1:
+        raise Hash10xError("%s: share graph version %d, this reader knows 1" % (path, version))
+    if len(data) != 24 + 8 * (n_blocks + 1) + 8 * rows:
+        raise Hash10xError("%s: %d bytes, %d blocks and %d rows need %d" % (path, len(data), n_blocks, rows, 24 + 8 * (n_blocks + 1) + 8 * rows))
+    off = np.frombuffer(data, dtype="<u8", count=n_blocks + 1, offset=24).copy()
+    if off[0] != 0 or int(off[-1]) != rows or np.any(off[1:] < off[:-1]):
+        raise Hash10xError("%s: the offsets do not ascend from 0 to the %d rows" % (path, rows))
+    pairs = np.frombuffer(data, dtype="<u4", count=2 * rows, offset=24 + 8 * (n_blocks + 1)).reshape(-1, 2)
+    return {"version": version, "nBlocks": n_blocks, "minShare": min_share, "rows": rows}, off, pairs[:, 0].copy(), pairs[:, 1].copy()
 
 
 # ---- mosh sets: the reference's moshutils (moshset.c, moshutils.c) on the GPU — csrc/stage_g.hip, host/mosh_host.c -------------------

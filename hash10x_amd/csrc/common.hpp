@@ -251,6 +251,9 @@ struct Ctx {
   DevBuf<u64> wlSlots; u64 wlMask = 0, wlCodes = 0; bool haveWhitelist = false;
   int64_t optFqbSlab = 0;     // records per device batch of the host forms of the census and the fix (0 = default 2^22); results do not depend on it
   int64_t optMolGlobal = 0;   // testing knob: 1 = the molecule map keeps first[] of every clustered block in its HBM scratch slice, also where it would fit LDS (stage_k.hip)
+  // the share graph of the last h10x_share_graph_run (stage_l.hip), kept until the next run, a new depth range, --clusterSplit or a new state:
+  // rows (block, count) of blocks [sgCodeMin, sgCodeMax) back to back, sgOffsets[sgCodeMax - sgCodeMin + 1]
+  DevBuf<u32> sgBlock, sgCount; DevBuf<u64> sgOffsets; u64 sgRows = 0; u32 sgCodeMin = 0, sgCodeMax = 0; bool haveShareGraph = false;
   // streaming ingest (h10x_ingest_fqb): the record image grows on the device as the chunks arrive
   DevBuf<u32> ingestBuf; u64 ingestRecords = 0, ingestCap = 0; bool ingestAsync = false;   // ingestAsync: chunks came through h10x_ingest_fqb_async (the closing call then checks the count)
   static constexpr int INGEST_SLOTS = 8; hipEvent_t ingestEv[INGEST_SLOTS] = {};   // h10x_ingest_fqb_async: one event per caller's buffer
@@ -446,6 +449,9 @@ int stageF_neighbourHist(Ctx *c, const u32 *xs, u32 nq, const u64 *offsets, u32 
 int stageF_codeShare(Ctx *c, const u32 *codes, u32 nq, u64 *offsets, u32 *barcode, u32 *count, u32 *firstRank, u32 *firstHash, u64 cap);
 int stageF_codeExplore(Ctx *c, int code, int threshold, u32 *out /* 8: h10x_code_explore_rep */);
 int stageF_codeCrib(Ctx *c, const u32 *codes, u32 n, u32 *out);
+int stageL_run(Ctx *c, int64_t minShare, u32 codeMin, u32 codeMax, h10x_share_graph_info *info);
+int stageL_get(Ctx *c, u64 *offsets, u32 *block, u32 *count, u64 cap, int toDevice);
+void stageL_release(Ctx *c);
 int stageJ_censusBegin(Ctx *c, u64 hint);
 int stageJ_censusAdd(Ctx *c, const u32 *dRec, u64 n);
 int stageJ_censusClose(Ctx *c, int64_t thresh, h10x_census_t *out);

@@ -230,6 +230,7 @@ const char *h10x_last_error(const h10x_ctx *h) { return h ? h->c.err.c_str() : "
 
 static void reset_state(Ctx &c) {
   c.haveState = false; c.haveRange = false; c.haveGood = false; c.rangeMin = c.rangeMax = 0; c.depthBound = 0xFFFFFFFFu; c.rangeHiMax = 0;
+  stageL_release(&c);
   c.within.release(); c.goodPos.release(); c.nGood.release(); c.goodEntries.release(); c.goodRow.release();
   // the tables of the state being replaced go back to the block cache NOW, not when their successors are swapped in: the second --readFQB of a
   // context then finds every block of the first one parked and allocates nothing (kept until the swap, rows[] and clusHash had no twin in the
@@ -399,6 +400,7 @@ int h10x_shard_agree(h10x_ctx *h, int ok, int *allOk) {
 int h10x_depth_range(h10x_ctx *h, int32_t lo, int32_t hi) {
   if (!h) return -1;
   H10X_TRY(enter(h->c));
+  stageL_release(&h->c);                                      // a kept share graph is of the lists this call replaces
   return stageC_depthRange(&h->c, lo, hi);
 }
 
@@ -411,6 +413,7 @@ int h10x_cluster(h10x_ctx *h, int32_t codeMin, int32_t codeMax, int32_t threshol
 int h10x_cluster_split(h10x_ctx *h) {
   if (!h) return -1;
   H10X_TRY(enter(h->c));
+  stageL_release(&h->c);                                      // (and of the blocks this call renumbers)
   return stageC_split(&h->c);
 }
 
@@ -661,6 +664,17 @@ int h10x_code_explore(h10x_ctx *h, int32_t code, int32_t threshold, h10x_code_ex
 }
 int h10x_code_crib_counts(h10x_ctx *h, const uint32_t *codes, uint32_t n, uint32_t *out) {
   if (!h || (n && (!codes || !out))) return -1; H10X_TRY(enter(h->c)); return stageF_codeCrib(&h->c, codes, n, out);
+}
+
+// ---- the share graph (stage_l.hip) ----
+int h10x_share_graph_run(h10x_ctx *h, int64_t minShare, uint32_t codeMin, uint32_t codeMax, h10x_share_graph_info *info) {
+  if (!h || !info) return -1; H10X_TRY(enter(h->c)); return stageL_run(&h->c, minShare, codeMin, codeMax, info);
+}
+int h10x_share_graph_get(h10x_ctx *h, uint64_t *offsets, uint32_t *block, uint32_t *count, uint64_t cap) {
+  if (!h) return -1; H10X_TRY(enter(h->c)); return stageL_get(&h->c, (u64 *)offsets, block, count, cap, 0);
+}
+int h10x_share_graph_get_device(h10x_ctx *h, uint64_t *devOffsets, uint32_t *devBlock, uint32_t *devCount, uint64_t cap) {
+  if (!h) return -1; H10X_TRY(enter(h->c)); return stageL_get(&h->c, (u64 *)devOffsets, devBlock, devCount, cap, 1);
 }
 
 int h10x_timing_enable(h10x_ctx *h, int on) { if (!h) return -1; h->c.timing = on != 0; return 0; }

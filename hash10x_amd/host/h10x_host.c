@@ -28,6 +28,7 @@ struct h10x_session {
   /* Array bookkeeping of the reference for the two arrays that are dumped raw into .hash */
   int depthDim, depthMax, blocksDim, blocksMax;
   uint32_t *depthTail; int depthTailFrom;              /* entries [hashNumber, dim) as read from a file (normally zero) */
+  int sgBlocks;                                        /* --shareGraph: blocks per range of its walk (0 = 8192) */
   char err[1024];
 };
 static const char *const knobName[N_KNOBS] = {"cluster_stamps", "cluster_lds_budget", "cluster_first_global", "cluster_first_cap",
@@ -63,8 +64,8 @@ const char *h10x_session_error(const h10x_session *s) { return s->err; }
 h10x_ctx *h10x_session_ctx(h10x_session *s) { return s->ctx; }
 
 static int *param_slot(h10x_session *s, const char *n) {
-  static const char *const names[] = {"k", "w", "r", "B", "N", "c", "ct", "device", "timing", 0};
-  int *const slots[] = {&s->k, &s->w, &s->r, &s->B, &s->N, &s->chunk, &s->ct, &s->device, &s->timing};
+  static const char *const names[] = {"k", "w", "r", "B", "N", "c", "ct", "device", "timing", "share_graph_blocks", 0};
+  int *const slots[] = {&s->k, &s->w, &s->r, &s->B, &s->N, &s->chunk, &s->ct, &s->device, &s->timing, &s->sgBlocks};
   for (int i = 0; names[i]; ++i) if (!strcmp(n, names[i])) return slots[i];
   for (int i = 0; i < N_KNOBS; ++i) if (!strcmp(n, knobName[i])) return &s->knob[i];
   return 0;
@@ -1752,5 +1753,47 @@ int h10x_session_codeExplore(h10x_session *s, int code, FILE *out, FILE *err) {
             (int)rows[i].rank, nb_text(s, &nb, rows[i].hash, t));
 done:
   free(bc); free(cnt); free(fr); free(fh); free(rows); free(hist); free(sel); free(crib); nb_close(&nb);
+  return rc;
+}
+
+/* ---- --shareGraph <minShare> <out.sg>: the graph of all blocks (h10x_share_graph_run) written range by range, so that neither the host nor the
+   device ever holds all rows: the header and the offsets are left blank first and filled in at the end. ---- */
+int h10x_session_shareGraph(h10x_session *s, int minShare, const char *outPath, FILE *out) {
+  if (!s->ctx) return fail(s, "!! you must set hashDepthRange before shareGraph");    /* nothing loaded: no range either */
+  h10x_shard_info_t z; if (h10x_shard_info(s->ctx, &z)) return fail_ctx(s);
+  if (z.nranks > 1) return fail(s, "shareGraph does not run on a sharded session (--gpus > 1)");
+  h10x_share_graph_info info;
+  if (h10x_share_graph_run(s->ctx, minShare, 1, 1, &info)) return fail_ctx(s);          /* the refusals, before the file is touched */
+  const uint32_t nBlocks = info.nBlocks, step = s->sgBlocks > 0 ? (uint32_t)s->sgBlocks : 8192u;
+  int rc = 0; FILE *f = 0; uint64_t *offsets = 0, *part = 0; uint32_t *blk = 0, *cnt = 0, *pair = 0; uint64_t cap = 0;
+  uint64_t rows = 0, listEntries = 0; uint32_t maxCount = 0;
+  const uint32_t version = 1, T = (uint32_t)minShare; unsigned char head[24];
+  offsets = (uint64_t *)calloc((size_t)nBlocks + 1, 8); part = (uint64_t *)malloc(((size_t)step + 1) * 8);
+  if (!offsets || !part) { rc = fail(s, "out of host memory for the offsets of %u blocks", nBlocks); goto done; }
+  if (!(f = fopen(outPath, "wb"))) { rc = fail(s, "failed to open output file %s", outPath); goto done; }
+  memset(head, 0, sizeof head);
+  if (fwrite(head, 1, 24, f) != 24 || fwrite(offsets, 8, (size_t)nBlocks + 1, f) != (size_t)nBlocks + 1) { rc = fail(s, "failed to write %s", outPath); goto done; }
+  for (uint32_t c0 = 0; c0 < nBlocks; c0 += step) {               /* (block 0 is unused: its row is empty) */
+    const uint32_t c1 = nBlocks - c0 < step ? nBlocks : c0 + step;
+    if (h10x_share_graph_run(s->ctx, minShare, c0, c1, &info)) { rc = fail_ctx(s); goto done; }
+    if (info.rows > cap) {
+      cap = info.rows + info.rows / 2;
+      free(blk); free(cnt); free(pair);
+      blk = (uint32_t *)malloc((size_t)cap * 4); cnt = (uint32_t *)malloc((size_t)cap * 4); pair = (uint32_t *)malloc((size_t)cap * 8);
+      if (!blk || !cnt || !pair) { rc = fail(s, "out of host memory for %llu rows", (unsigned long long)cap); goto done; }
+    }
+    if (h10x_share_graph_get(s->ctx, part, blk, cnt, info.rows)) { rc = fail_ctx(s); goto done; }
+    for (uint32_t q = 0; q <= c1 - c0; ++q) offsets[c0 + q] = rows + part[q];
+    for (uint64_t i = 0; i < info.rows; ++i) { pair[2 * i] = blk[i]; pair[2 * i + 1] = cnt[i]; }
+    if (info.rows && fwrite(pair, 8, (size_t)info.rows, f) != (size_t)info.rows) { rc = fail(s, "failed to write %s", outPath); goto done; }
+    rows += info.rows; listEntries += info.listEntries; if (info.maxCount > maxCount) maxCount = info.maxCount;
+  }
+  memcpy(head, "10XG", 4); memcpy(head + 4, &version, 4); memcpy(head + 8, &nBlocks, 4); memcpy(head + 12, &T, 4); memcpy(head + 16, &rows, 8);
+  if (fseeko(f, 0, SEEK_SET) || fwrite(head, 1, 24, f) != 24 || fwrite(offsets, 8, (size_t)nBlocks + 1, f) != (size_t)nBlocks + 1) { rc = fail(s, "failed to write %s", outPath); goto done; }
+  if (out) fprintf(out, "  share graph at minShare %d: %u blocks, %llu rows, %llu list entries, max count %u\n", minShare, nBlocks,
+                   (unsigned long long)rows, (unsigned long long)listEntries, maxCount);
+done:
+  if (f && fclose(f) && !rc) rc = fail(s, "failed to write %s", outPath);
+  free(offsets); free(part); free(blk); free(cnt); free(pair);
   return rc;
 }

@@ -110,6 +110,14 @@ int  h10x_session_splitFQB(h10x_session *s, const char *inPath, const char *outP
 int  h10x_host_write_molmap(const char *path, const uint32_t *mol, const uint32_t *slot, const h10x_molmap_info *info, char *err, int errlen);
 int  h10x_host_write_split_index(const char *path, const uint64_t *start, uint32_t nBlocks, uint32_t nMolecules, char *err, int errlen);
 
+/* --shareGraph <minShare> <out.sg> (addition; include/h10x.h "the share graph"): for every block the blocks that share at least minShare of its
+   good hashes, with the counts. The file, little-endian: magic "10XG", u32 version 1, u32 nBlocks, u32 minShare, u64 rows, nBlocks + 1 u64 offsets,
+   then rows pairs {u32 block, u32 count}: the row of block c is pairs [offsets[c], offsets[c + 1]), ascending in block. The blocks are walked in
+   ranges of "share_graph_blocks" (h10x_session_set; 0 = 8192) and the file is written range by range, so neither the host nor the device holds all
+   rows; the result does not depend on it. One line of counts to out (may be NULL). Fails with "!! ..." (the command then does nothing) before
+   --hashDepthRange, after --clusterSplit until a new range is set, and for minShare < 1; single-GPU sessions only. */
+int  h10x_session_shareGraph(h10x_session *s, int minShare, const char *outPath, FILE *out);
+
 /* multi-GPU (include/h10x.h "multi-GPU"): one session per rank, each holding a contiguous barcode range of the sorted file
    (cut with h10x_host_partition / _partition_file; -N is applied by the launcher before cutting). Every command of a
    sharded session is collective: all ranks call it with the same arguments; the text commands print on the rank whose

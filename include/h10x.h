@@ -395,6 +395,36 @@ int  h10x_code_share(h10x_ctx *ctx, const uint32_t *codes, uint32_t nq, uint64_t
 int  h10x_code_explore(h10x_ctx *ctx, int32_t code, int32_t threshold, h10x_code_explore_rep *rep);
 int  h10x_code_crib_counts(h10x_ctx *ctx, const uint32_t *codes, uint32_t n, uint32_t *out);
 
+/* ---- the share graph (csrc/stage_l.hip): all pairs of blocks that share at least minShare good hashes ----
+   The barcode census above for every block at once, thresholded on the device. For a block c, countShare_c[d] is the `count` column of
+   h10x_code_share: the entries d != c in the barcode lists of c's good hashes, repeats as the lists hold them. It is a DIRECTED count: a block
+   of more than 65535 records has no good hashes (hash10x.c:748), so its own row is empty, yet it appears in the rows of others. The graph at
+   minShare = T >= 1 over blocks [codeMin, codeMax) is, per block c of the range, the row {(d, countShare_c[d]) : countShare_c[d] >= T}
+   ascending in d, in CSR form: offsets[codeMax - codeMin + 1], and block[] / count[] with offsets[last] entries. At T = 1 these are the
+   rows of h10x_code_share for the same codes. codeMax = 0 means nBlocks (as --cluster 1 0); codeMin >= codeMax is an empty graph (one
+   offset, 0). The blocks are the current ones: after --clusterSplit and a new range they are the molecules.
+   h10x_share_graph_run computes the graph with ONE census — per block and per list a size pass, keys (c - codeMin') << bits | d without a
+     rank (32-bit where they fit), every list's place from a scan instead of a reservation, a sort, and a run pass that keeps only runs of
+     length >= T — and keeps the rows in device memory of the context. Batches are cut by list entries against "neighbour_budget", a block
+     above it runs alone in windows of barcode index; both are counted in h10x_neighbour_stats too. The result does not depend on the
+     batching, and two calls give the same bytes. info: rows = offsets[last]; listEntries = the list entries d != c gathered and sorted
+     (the sum of all counts at T = 1); entriesRead = list entries read, the blocks' own included; maxCount = the largest count of a row (0 without rows); batches, windows of this call; the range
+     as it was taken, and nBlocks.
+   h10x_share_graph_get / _get_device copy the kept graph out: the offsets and the first min(cap, rows) rows (any array may be NULL), to
+     host or to device memory. The kept graph is released by the next run (also a failed one), h10x_depth_range, h10x_cluster_split, a new
+     state and h10x_destroy; get without one fails.
+   h10x_share_graph_run fails without a state, on a sharded context, before --hashDepthRange and after --clusterSplit until a new range is
+   set ("!! you must set hashDepthRange before shareGraph"), for minShare < 1 ("!! shareGraph minShare ... must be >= 1") and for
+   codeMax > nBlocks ("!! shareGraph codeMax ... beyond nBlocks ..."). */
+typedef struct {
+  uint64_t rows, listEntries, entriesRead;
+  uint32_t maxCount, batches, windows;
+  uint32_t codeMin, codeMax, nBlocks;
+} h10x_share_graph_info;
+int  h10x_share_graph_run(h10x_ctx *ctx, int64_t minShare, uint32_t codeMin, uint32_t codeMax, h10x_share_graph_info *info);
+int  h10x_share_graph_get(h10x_ctx *ctx, uint64_t *offsets, uint32_t *block, uint32_t *count, uint64_t cap);
+int  h10x_share_graph_get_device(h10x_ctx *ctx, uint64_t *dev_offsets, uint32_t *dev_block, uint32_t *dev_count, uint64_t cap);
+
 /* ---- mosh sets (csrc/stage_g.hip): the Moshset object of the reference's moshutils (moshset.h, moshset.c, moshutils.c) ----
    A second opaque handle beside the context. A set is the probe table index[2^B] (moshsetIndexFind, moshset.c:45-61) and, per index
    1 .. max in order of first appearance, value (the hash), depth (saturating at 65535) and info (low two bits = copy class 0, 1, 2, M).
