@@ -222,6 +222,13 @@ def load_native():
     hip.h10x_share_graph_get.argtypes = [vp, vp, vp, vp, cu64]
     hip.h10x_share_graph_get_device.argtypes = [vp, vp, vp, vp, cu64]
     host.h10x_session_shareGraph.argtypes = [vp, ci, cs, vp]
+    # the components of the share graph (csrc/stage_m.hip)
+    hip.h10x_share_components_begin.argtypes = [vp, ctypes.c_int64]
+    hip.h10x_share_components_add.argtypes = [vp, ctypes.c_uint32, ctypes.c_uint32]
+    hip.h10x_share_components_finish.argtypes = [vp, vp]
+    hip.h10x_share_components_get.argtypes = [vp, vp, vp, vp, vp, vp, cu64, cu64]
+    host.h10x_session_shareComponents.argtypes = [vp, ci, cs, vp]
+    host.h10x_session_shareComponentsRun.argtypes = [vp, ci, vp]
     # mosh sets (csrc/stage_g.hip, host/mosh_host.c)
     pvp, ci32, cu32 = ctypes.POINTER(vp), ctypes.c_int32, ctypes.c_uint32
     hip.h10x_factors_from_seed.restype = None; hip.h10x_factors_from_seed.argtypes = [ci32, ctypes.POINTER(cu64), ctypes.POINTER(cu64)]
@@ -966,6 +973,32 @@ class Hash10x:
         counts is appended to the file `out`."""
         self._with_file(out, lambda f: self._host.h10x_session_shareGraph(self._s, int(min_share), os.fsencode(path), f))
 
+    # ---- the components of the share graph (h10x_share_components_*): each range's rows are hooked into a label array on the device ----
+    def share_components(self, min_share):
+        """The connected components of the share graph at min_share over all blocks (every row entry (c, d) an undirected edge), walked
+        in ranges of the option "share_graph_blocks": (comp uint32[nBlocks], root uint32[nBlocks], rootOf uint32[nComponents + 1],
+        blocks uint32[nComponents + 1], records uint64[nComponents + 1]). root[c] = the smallest block of c's component, the components
+        of blocks 1 .. are numbered 1 .. nComponents by ascending root, comp[c] = that number (comp[0] = 0), and per component its root,
+        member count and sum of nHash (entry 0 all zero). The figures of the run (nBlocks, minShare, rows, listEntries, nComponents,
+        largest, singletons, batches, windows, hookRounds) are kept in self.share_components_info."""
+        if not self._ctx():
+            raise Hash10xError("shareComponents: no hash state loaded: use readFQB or readHash first")
+        z = np.zeros(1, dtype=_SHARE_COMPONENTS_INFO)
+        min_share = max(-2 ** 31, min(int(min_share), 2 ** 31 - 1))
+        self._chk(self._host.h10x_session_shareComponentsRun(self._s, min_share, z.ctypes.data))
+        self.share_components_info = {n: int(z[n][0]) for n in _SHARE_COMPONENTS_INFO.names}
+        nb, nc = self.share_components_info["nBlocks"], self.share_components_info["nComponents"] + 1
+        comp, root = np.zeros(nb, dtype=np.uint32), np.zeros(nb, dtype=np.uint32)
+        root_of, blocks, records = np.zeros(nc, dtype=np.uint32), np.zeros(nc, dtype=np.uint32), np.zeros(nc, dtype=np.uint64)
+        self._chk_ctx(self._hip.h10x_share_components_get(self._ctx(), comp.ctypes.data, root.ctypes.data, root_of.ctypes.data, blocks.ctypes.data,
+                                                          records.ctypes.data, nb, nc))
+        return comp, root, root_of, blocks, records
+
+    def write_share_components(self, min_share, path, out=None):
+        """--shareComponents <min_share> <path>: the components of all blocks written as a .sc file (read_share_components reads it);
+        one line of counts is appended to the file `out`."""
+        self._with_file(out, lambda f: self._host.h10x_session_shareComponents(self._s, int(min_share), os.fsencode(path), f))
+
     def export_within(self):
         """hashWithinRange[0 .. hashNumber) as uint8 (fails before --hashDepthRange)."""
         z = self.sizes()
@@ -997,6 +1030,40 @@ def read_share_graph(path):
         raise Hash10xError("%s: the offsets do not ascend from 0 to the %d rows" % (path, rows))
     pairs = np.frombuffer(data, dtype="<u4", count=2 * rows, offset=24 + 8 * (n_blocks + 1)).reshape(-1, 2)
     return {"version": version, "nBlocks": n_blocks, "minShare": min_share, "rows": rows}, off, pairs[:, 0].copy(), pairs[:, 1].copy()
+
+
+_SHARE_COMPONENTS_INFO = np.dtype([("rows", "<u8"), ("listEntries", "<u8"), ("nBlocks", "<u4"), ("minShare", "<u4"), ("nComponents", "<u4"), ("largest", "<u4"),
+                                   ("singletons", "<u4"), ("batches", "<u4"), ("windows", "<u4"), ("hookRounds", "<u4")])
+_SC_ENTRY = np.dtype([("root", "<u4"), ("blocks", "<u4"), ("records", "<u8")])
+
+
+def read_share_components(path):
+    """A --shareComponents file (magic "10XC", u32 version 1, u32 nBlocks, u32 minShare, u32 nComponents, u32 largest, u64 rows,
+    comp[nBlocks] as u32, nComponents + 1 entries {u32 root, u32 blocks, u64 records}, little-endian; needs no device):
+    ({"version", "nBlocks", "minShare", "nComponents", "largest", "rows"}, comp, rootOf, blocks, records). Raises Hash10xError for a file
+    that is not one or does not hold together: lengths, comp < nComponents + 1, the member counts summing to nBlocks - 1, rootOf ascending."""
+    with open(path, "rb") as f:
+        data = f.read()
+    if len(data) < 32 or data[:4] != b"10XC":
+        raise Hash10xError("%s: not a share components file (magic 10XC)" % path)
+    version, n_blocks, min_share, n_comp, largest = (int(v) for v in np.frombuffer(data, dtype="<u4", count=5, offset=4))
+    rows = int(np.frombuffer(data, dtype="<u8", count=1, offset=24)[0])
+    if version != 1:
+        raise Hash10xError("%s: share components version %d, this reader knows 1" % (path, version))
+    need = 32 + 4 * n_blocks + 16 * (n_comp + 1)
+    if len(data) != need:
+        raise Hash10xError("%s: %d bytes, %d blocks and %d components need %d" % (path, len(data), n_blocks, n_comp, need))
+    comp = np.frombuffer(data, dtype="<u4", count=n_blocks, offset=32).copy()
+    ent = np.frombuffer(data, dtype=_SC_ENTRY, count=n_comp + 1, offset=32 + 4 * n_blocks)
+    root_of, blocks, records = ent["root"].copy(), ent["blocks"].copy(), ent["records"].copy()
+    if n_blocks and int(comp.max()) >= n_comp + 1:
+        raise Hash10xError("%s: a block's component is beyond the %d components" % (path, n_comp))
+    if int(blocks.sum(dtype=np.uint64)) != max(n_blocks - 1, 0) or blocks[0] != 0:
+        raise Hash10xError("%s: the components' member counts do not sum to the %d blocks" % (path, max(n_blocks - 1, 0)))
+    if root_of[0] != 0 or np.any(root_of[1:] <= root_of[:-1]) or (n_comp and int(root_of[-1]) >= n_blocks):
+        raise Hash10xError("%s: the components' roots do not ascend within the %d blocks" % (path, n_blocks))
+    return ({"version": version, "nBlocks": n_blocks, "minShare": min_share, "nComponents": n_comp, "largest": largest, "rows": rows},
+            comp, root_of, blocks, records)
 
 
 # ---- mosh sets: the reference's moshutils (moshset.c, moshutils.c) on the GPU — csrc/stage_g.hip, host/mosh_host.c -------------------

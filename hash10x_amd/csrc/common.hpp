@@ -254,6 +254,11 @@ struct Ctx {
   // the share graph of the last h10x_share_graph_run (stage_l.hip), kept until the next run, a new depth range, --clusterSplit or a new state:
   // rows (block, count) of blocks [sgCodeMin, sgCodeMax) back to back, sgOffsets[sgCodeMax - sgCodeMin + 1]
   DevBuf<u32> sgBlock, sgCount; DevBuf<u64> sgOffsets; u64 sgRows = 0; u32 sgCodeMin = 0, sgCodeMax = 0; bool haveShareGraph = false;
+  // the components of the share graph (stage_m.hip). Between h10x_share_components_begin and _finish: scParent[scBlocks], the union-find forest the ranges' rows
+  // are hooked into. After _finish, kept until the next begin, a new depth range, --clusterSplit or a new state: scComp / scRoot [scBlocks] and, per component
+  // 0 .. scComps, its root, member count and record sum
+  DevBuf<u32> scParent, scComp, scRoot, scRootOf, scMembers; DevBuf<u64> scRecords; u32 scBlocks = 0, scComps = 0; int64_t scMinShare = 0;
+  bool scOpen = false, haveShareComp = false; h10x_share_components_info scInfo{};
   // streaming ingest (h10x_ingest_fqb): the record image grows on the device as the chunks arrive
   DevBuf<u32> ingestBuf; u64 ingestRecords = 0, ingestCap = 0; bool ingestAsync = false;   // ingestAsync: chunks came through h10x_ingest_fqb_async (the closing call then checks the count)
   static constexpr int INGEST_SLOTS = 8; hipEvent_t ingestEv[INGEST_SLOTS] = {};   // h10x_ingest_fqb_async: one event per caller's buffer
@@ -452,6 +457,11 @@ int stageF_codeCrib(Ctx *c, const u32 *codes, u32 n, u32 *out);
 int stageL_run(Ctx *c, int64_t minShare, u32 codeMin, u32 codeMax, h10x_share_graph_info *info);
 int stageL_get(Ctx *c, u64 *offsets, u32 *block, u32 *count, u64 cap, int toDevice);
 void stageL_release(Ctx *c);
+int stageM_begin(Ctx *c, int64_t minShare);
+int stageM_add(Ctx *c, u32 codeMin, u32 codeMax);
+int stageM_finish(Ctx *c, h10x_share_components_info *info);
+int stageM_get(Ctx *c, u32 *comp, u32 *root, u32 *rootOf, u32 *nMember, u64 *records, u64 capBlocks, u64 capComps);
+void stageM_release(Ctx *c);
 int stageJ_censusBegin(Ctx *c, u64 hint);
 int stageJ_censusAdd(Ctx *c, const u32 *dRec, u64 n);
 int stageJ_censusClose(Ctx *c, int64_t thresh, h10x_census_t *out);

@@ -1797,3 +1797,56 @@ done:
   free(offsets); free(part); free(blk); free(cnt); free(pair);
   return rc;
 }
+
+/* ---- --shareComponents <minShare> <out.sc>: the connected components of the share graph over all blocks (h10x_share_components_*). The blocks are walked
+   in the ranges of --shareGraph; each range's rows are folded into the device's label array where the census made them, and only the labels come back. ---- */
+int h10x_session_shareComponentsRun(h10x_session *s, int minShare, h10x_share_components_info *info) {
+  if (!s->ctx) return fail(s, "!! you must set hashDepthRange before shareComponents");   /* nothing loaded: no range either */
+  h10x_shard_info_t z; if (h10x_shard_info(s->ctx, &z)) return fail_ctx(s);
+  if (z.nranks > 1) return fail(s, "shareComponents does not run on a sharded session (--gpus > 1)");
+  if (h10x_share_components_begin(s->ctx, minShare)) return fail_ctx(s);                /* the refusals */
+  h10x_sizes zs; if (h10x_get_sizes(s->ctx, &zs)) return fail_ctx(s);
+  const uint32_t nBlocks = zs.nBlocks, step = s->sgBlocks > 0 ? (uint32_t)s->sgBlocks : 8192u;
+  for (uint32_t c0 = 0; c0 < nBlocks; c0 += step) {
+    const uint32_t c1 = nBlocks - c0 < step ? nBlocks : c0 + step;
+    if (h10x_share_components_add(s->ctx, c0, c1)) return fail_ctx(s);
+  }
+  if (h10x_share_components_finish(s->ctx, info)) return fail_ctx(s);
+  return 0;
+}
+
+int h10x_host_write_share_components(const char *path, const h10x_share_components_info *info, const uint32_t *comp, const uint32_t *rootOf,
+                                     const uint32_t *blocks, const uint64_t *records, char *err, int errlen) {
+  FILE *f = fopen(path, "wb");
+  if (!f) { snprintf(err, (size_t)errlen, "failed to open output file %s", path); return -1; }
+  const uint32_t version = 1; unsigned char head[32]; int ok = 1;
+  memcpy(head, "10XC", 4); memcpy(head + 4, &version, 4); memcpy(head + 8, &info->nBlocks, 4); memcpy(head + 12, &info->minShare, 4);
+  memcpy(head + 16, &info->nComponents, 4); memcpy(head + 20, &info->largest, 4); memcpy(head + 24, &info->rows, 8);
+  ok = fwrite(head, 1, 32, f) == 32;
+  if (ok && info->nBlocks) ok = fwrite(comp, 4, info->nBlocks, f) == info->nBlocks;
+  for (uint32_t k = 0; ok && k <= info->nComponents; ++k) {
+    unsigned char e[16];
+    memcpy(e, rootOf + k, 4); memcpy(e + 4, blocks + k, 4); memcpy(e + 8, records + k, 8);
+    ok = fwrite(e, 1, 16, f) == 16;
+  }
+  if (fclose(f)) ok = 0;
+  if (!ok) { snprintf(err, (size_t)errlen, "failed to write %s", path); return -1; }
+  return 0;
+}
+
+int h10x_session_shareComponents(h10x_session *s, int minShare, const char *outPath, FILE *out) {
+  h10x_share_components_info info;
+  if (h10x_session_shareComponentsRun(s, minShare, &info)) return -1;
+  const size_t nb = info.nBlocks, nc = (size_t)info.nComponents + 1;
+  int rc = 0;
+  uint32_t *comp = (uint32_t *)malloc((nb ? nb : 1) * 4), *rootOf = (uint32_t *)malloc(nc * 4), *blocks = (uint32_t *)malloc(nc * 4);
+  uint64_t *records = (uint64_t *)malloc(nc * 8);
+  if (!comp || !rootOf || !blocks || !records) { rc = fail(s, "out of host memory for the components of %u blocks", info.nBlocks); goto done; }
+  if (h10x_share_components_get(s->ctx, comp, 0, rootOf, blocks, records, nb, nc)) { rc = fail_ctx(s); goto done; }
+  if (h10x_host_write_share_components(outPath, &info, comp, rootOf, blocks, records, s->err, (int)sizeof s->err)) { rc = -1; goto done; }
+  if (out) fprintf(out, "  share components at minShare %d: %d blocks, %llu rows, %u components, largest %u blocks, %u singletons\n", minShare, (int)info.nBlocks,
+                   (unsigned long long)info.rows, info.nComponents, info.largest, info.singletons);
+done:
+  free(comp); free(rootOf); free(blocks); free(records);
+  return rc;
+}

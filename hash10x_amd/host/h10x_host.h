@@ -118,6 +118,20 @@ int  h10x_host_write_split_index(const char *path, const uint64_t *start, uint32
    --hashDepthRange, after --clusterSplit until a new range is set, and for minShare < 1; single-GPU sessions only. */
 int  h10x_session_shareGraph(h10x_session *s, int minShare, const char *outPath, FILE *out);
 
+/* --shareComponents <minShare> <out.sc> (addition; include/h10x.h "the components of the share graph"): the connected components of the share graph at
+   minShare over all blocks — which blocks (after --clusterSplit: molecules) hang together through shared good hashes. The file, little-endian: magic
+   "10XC", u32 version 1, u32 nBlocks, u32 minShare, u32 nComponents, u32 largest, u64 rows, then comp[nBlocks] as u32, then nComponents + 1 entries
+   {u32 root, u32 blocks, u64 records} (entry 0 all zero). The blocks are walked in ranges of "share_graph_blocks" as --shareGraph walks them; each
+   range's rows are folded into the labels on the device and never leave it; the result does not depend on the ranges. One line of counts to out (may
+   be NULL). Fails with "!! ..." (the command then does nothing, no file is written) before --hashDepthRange, after --clusterSplit until a new range is
+   set, and for minShare < 1; single-GPU sessions only.
+   h10x_session_shareComponentsRun is the walk alone: the result stays in the context for h10x_share_components_get.
+   h10x_host_write_share_components writes the file from host arrays (no device). */
+int  h10x_session_shareComponents(h10x_session *s, int minShare, const char *outPath, FILE *out);
+int  h10x_session_shareComponentsRun(h10x_session *s, int minShare, h10x_share_components_info *info);
+int  h10x_host_write_share_components(const char *path, const h10x_share_components_info *info, const uint32_t *comp, const uint32_t *rootOf,
+                                      const uint32_t *blocks, const uint64_t *records, char *err, int errlen);
+
 /* multi-GPU (include/h10x.h "multi-GPU"): one session per rank, each holding a contiguous barcode range of the sorted file
    (cut with h10x_host_partition / _partition_file; -N is applied by the launcher before cutting). Every command of a
    sharded session is collective: all ranks call it with the same arguments; the text commands print on the rank whose

@@ -425,6 +425,44 @@ int  h10x_share_graph_run(h10x_ctx *ctx, int64_t minShare, uint32_t codeMin, uin
 int  h10x_share_graph_get(h10x_ctx *ctx, uint64_t *offsets, uint32_t *block, uint32_t *count, uint64_t cap);
 int  h10x_share_graph_get_device(h10x_ctx *ctx, uint64_t *dev_offsets, uint32_t *dev_block, uint32_t *dev_count, uint64_t cap);
 
+/* ---- the components of the share graph (csrc/stage_m.hip): which blocks hang together through shared good hashes ----
+   State: as for the share graph, an unsharded context with a --hashDepthRange in force.
+   Graph: the share graph above at minShare = T >= 1 over ALL blocks. Every row entry (c, d) is an undirected edge {c, d}. A block of more
+   than 65535 records has an empty row of its own, yet it stands in the rows of others: such entries join it all the same.
+   Per block and per component:
+     root[c]   = the smallest block number in c's connected component; root[0] = 0.
+     The components of blocks 1 .. nBlocks-1 are numbered 1 .. nComponents in ascending order of their root.
+     comp[c]   = that number; comp[0] = 0.
+     For each component k: blocks[k] = its member count (u32), records[k] = the sum of nHash over its members (u64), rootOf[k] = its root.
+     Entry 0 of the three is all zero. A block without edges is a component of one; empty blocks count.
+   The result depends on none of "neighbour_budget", the ranges the blocks are added in, the order in which atomics land, or the run: two
+   calls give the same bytes.
+   h10x_share_components_begin starts a run: parent[nBlocks], one label per block, is set up on the device as the identity.
+   h10x_share_components_add(ctx, codeMin, codeMax) runs the census of h10x_share_graph_run over blocks [codeMin, codeMax) (codeMax = 0:
+     nBlocks) and folds that range's rows into parent[] where they were made: a hook kernel, one thread per row, joins the two ends by
+     lock-free union by smaller root; a check kernel counts the rows whose ends still differ, and the hook runs again while there are any
+     (bounded; running out of rounds is an error). The caller adds ranges that cover blocks 1 .. nBlocks-1, each block once, in any order. The
+     census uses the share graph's result arrays: a share graph kept from h10x_share_graph_run is dropped by a components run.
+   h10x_share_components_finish computes the five arrays and keeps them in device memory of the context. info: nBlocks, minShare, rows =
+     the rows of all ranges, listEntries as in h10x_share_graph_info, nComponents, largest = the largest member count, singletons = the
+     components of one block, batches and windows of the censuses, hookRounds = hook launches over all ranges (one per range that has rows,
+     unless a check asked for more).
+   h10x_share_components_get copies the first min(capBlocks, nBlocks) entries of comp / root and the first min(capComps, nComponents + 1) of
+     rootOf / blocks / records to host memory; any array may be NULL. With all NULL it returns 0 when a result is kept, non-zero otherwise.
+   The kept result (and a run in progress) is released by the next begin (also a failed one), h10x_depth_range, h10x_cluster_split, a new
+   state and h10x_destroy. begin fails without a state, on a sharded context, before --hashDepthRange and after --clusterSplit until a new
+   range is set ("!! you must set hashDepthRange before shareComponents") and for minShare < 1 ("!! shareComponents minShare ... must be
+   >= 1"); add and finish fail without a begin. */
+typedef struct {
+  uint64_t rows, listEntries;
+  uint32_t nBlocks, minShare, nComponents, largest, singletons, batches, windows, hookRounds;
+} h10x_share_components_info;
+int  h10x_share_components_begin(h10x_ctx *ctx, int64_t minShare);
+int  h10x_share_components_add(h10x_ctx *ctx, uint32_t codeMin, uint32_t codeMax);
+int  h10x_share_components_finish(h10x_ctx *ctx, h10x_share_components_info *info);
+int  h10x_share_components_get(h10x_ctx *ctx, uint32_t *comp, uint32_t *root, uint32_t *rootOf, uint32_t *blocks, uint64_t *records,
+                               uint64_t capBlocks, uint64_t capComps);
+
 /* ---- mosh sets (csrc/stage_g.hip): the Moshset object of the reference's moshutils (moshset.h, moshset.c, moshutils.c) ----
    A second opaque handle beside the context. A set is the probe table index[2^B] (moshsetIndexFind, moshset.c:45-61) and, per index
    1 .. max in order of first appearance, value (the hash), depth (saturating at 65535) and info (low two bits = copy class 0, 1, 2, M).
