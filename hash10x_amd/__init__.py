@@ -229,6 +229,14 @@ def load_native():
     hip.h10x_share_components_get.argtypes = [vp, vp, vp, vp, vp, vp, cu64, cu64]
     host.h10x_session_shareComponents.argtypes = [vp, ci, cs, vp]
     host.h10x_session_shareComponentsRun.argtypes = [vp, ci, vp]
+    # the per-hash linkage groups (csrc/stage_n.hip)
+    hip.h10x_hash_copies_run.argtypes = [vp, ctypes.c_int64, vp]
+    hip.h10x_hash_copies_get.argtypes = [vp, vp, cu64, cu64]
+    hip.h10x_hash_copies_get_device.argtypes = [vp, vp, cu64, cu64]
+    hip.h10x_hash_copies_tally.argtypes = [vp, vp]
+    hip.h10x_crib_export.argtypes = [vp, vp, vp, vp, vp]
+    host.h10x_session_hashCopies.argtypes = [vp, ci, cs, vp]
+    host.h10x_session_hashCopiesRun.argtypes = [vp, ci, vp]
     # mosh sets (csrc/stage_g.hip, host/mosh_host.c)
     pvp, ci32, cu32 = ctypes.POINTER(vp), ctypes.c_int32, ctypes.c_uint32
     hip.h10x_factors_from_seed.restype = None; hip.h10x_factors_from_seed.argtypes = [ci32, ctypes.POINTER(cu64), ctypes.POINTER(cu64)]
@@ -999,6 +1007,45 @@ class Hash10x:
         one line of counts is appended to the file `out`."""
         self._with_file(out, lambda f: self._host.h10x_session_shareComponents(self._s, int(min_share), os.fsencode(path), f))
 
+    # ---- the per-hash linkage groups (h10x_hash_copies_*): one wave per in-range hash reads the share graph restricted to its own blocks ----
+    def hash_copies(self, min_share):
+        """For every hash index the linkage groups of the blocks that hold it, at min_share: a (hashNumber, 4) uint16 array of
+        (distinct, groups, largest, second) — the distinct blocks of the hash's barcode list, the connected components of the share
+        graph at min_share restricted to them (either direction joins), the member counts of the largest and the second largest
+        component (0 with one group). Hashes outside the depth range, and index 0, hold zeros. The figures of the run (hashNumber,
+        minShare, inRange, rows, listEntries, deepest, oneGroup, split, batches, windows) are kept in self.hash_copies_info."""
+        if not self._ctx():
+            raise Hash10xError("hashCopies: no hash state loaded: use readFQB or readHash first")
+        z = np.zeros(1, dtype=_HASH_COPIES_INFO)
+        min_share = max(-2 ** 31, min(int(min_share), 2 ** 31 - 1))
+        self._chk(self._host.h10x_session_hashCopiesRun(self._s, min_share, z.ctypes.data))
+        self.hash_copies_info = {n: int(z[n][0]) for n in _HASH_COPIES_INFO.names if n != "reserved"}
+        n = self.hash_copies_info["hashNumber"]
+        out = np.zeros((max(n, 1), 4), dtype=np.uint16)
+        self._chk_ctx(self._hip.h10x_hash_copies_get(self._ctx(), out.ctypes.data, 0, n))
+        return out[:n]
+
+    def hash_copies_tally(self):
+        """Of the kept hash_copies result, per crib type (err, htA, htB, hom, mul; all under err when no crib was built): a (5, 3)
+        uint64 array of the in-range hashes, those with groups == 1 and those with second >= 2."""
+        if not self._ctx():
+            raise Hash10xError("hashCopies: no hash state loaded: use readFQB or readHash first")
+        counts = np.zeros((5, 3), dtype=np.uint64)
+        self._chk_ctx(self._hip.h10x_hash_copies_tally(self._ctx(), counts.ctypes.data))
+        return counts
+
+    def export_crib_type(self):
+        """cribType[0 .. hashNumber) as uint8 (0 err, 1 htA, 2 htB, 3 hom, 4 mul; fails before --cribBuild): the classes hash_copies_tally counts by."""
+        z = self.sizes()
+        t = np.zeros(max(z["hashNumber"], 1), dtype=np.uint8)
+        self._chk_ctx(self._hip.h10x_crib_export(self._ctx(), None, None, t.ctypes.data, None))
+        return t[:z["hashNumber"]]
+
+    def write_hash_copies(self, min_share, path, out=None):
+        """--hashCopies <min_share> <path>: the table written as a .hc file (read_hash_copies reads it); one line of counts, and with a
+        crib the five HASH_COPIES lines, are appended to the file `out`."""
+        self._with_file(out, lambda f: self._host.h10x_session_hashCopies(self._s, int(min_share), os.fsencode(path), f))
+
     def export_within(self):
         """hashWithinRange[0 .. hashNumber) as uint8 (fails before --hashDepthRange)."""
         z = self.sizes()
@@ -1064,6 +1111,29 @@ def read_share_components(path):
         raise Hash10xError("%s: the components' roots do not ascend within the %d blocks" % (path, n_blocks))
     return ({"version": version, "nBlocks": n_blocks, "minShare": min_share, "nComponents": n_comp, "largest": largest, "rows": rows},
             comp, root_of, blocks, records)
+
+
+_HASH_COPIES_INFO = np.dtype([("inRange", "<u8"), ("rows", "<u8"), ("listEntries", "<u8"), ("oneGroup", "<u8"), ("split", "<u8"), ("hashNumber", "<u4"),
+                              ("minShare", "<u4"), ("deepest", "<u4"), ("batches", "<u4"), ("windows", "<u4"), ("reserved", "<u4")])
+
+
+def read_hash_copies(path):
+    """A --hashCopies file (magic "10XK", u32 version 1, u32 hashNumber, u32 minShare, u64 inRange, u64 rows, hashNumber records
+    {u16 distinct, u16 groups, u16 largest, u16 second}, little-endian; needs no device): ({"version", "hashNumber", "minShare",
+    "inRange", "rows"}, a (hashNumber, 4) uint16 array). Raises Hash10xError for a file that is not one or whose length is not what its
+    header says."""
+    with open(path, "rb") as f:
+        data = f.read()
+    if len(data) < 32 or data[:4] != b"10XK":
+        raise Hash10xError("%s: not a hash copies file (magic 10XK)" % path)
+    version, n_hash, min_share = (int(v) for v in np.frombuffer(data, dtype="<u4", count=3, offset=4))
+    in_range, rows = (int(v) for v in np.frombuffer(data, dtype="<u8", count=2, offset=16))
+    if version != 1:
+        raise Hash10xError("%s: hash copies version %d, this reader knows 1" % (path, version))
+    if len(data) != 32 + 8 * n_hash:
+        raise Hash10xError("%s: %d bytes, %d hashes need %d" % (path, len(data), n_hash, 32 + 8 * n_hash))
+    table = np.frombuffer(data, dtype="<u2", count=4 * n_hash, offset=32).reshape(-1, 4).copy()
+    return {"version": version, "hashNumber": n_hash, "minShare": min_share, "inRange": in_range, "rows": rows}, table
 
 
 # ---- mosh sets: the reference's moshutils (moshset.c, moshutils.c) on the GPU — csrc/stage_g.hip, host/mosh_host.c -------------------

@@ -259,6 +259,9 @@ struct Ctx {
   // 0 .. scComps, its root, member count and record sum
   DevBuf<u32> scParent, scComp, scRoot, scRootOf, scMembers; DevBuf<u64> scRecords; u32 scBlocks = 0, scComps = 0; int64_t scMinShare = 0;
   bool scOpen = false, haveShareComp = false; h10x_share_components_info scInfo{};
+  // the per-hash linkage groups of the last h10x_hash_copies_run (stage_n.hip), kept until the next run, a new depth range, --clusterSplit or a new state:
+  // hcOut = hcHashes records {u16 distinct, groups, largest, second}; hcTally[3 * t + k] = the counts per crib type t, [15] = the deepest in-range list
+  DevBuf<u32> hcOut; u32 hcHashes = 0; bool haveHashCopies = false; u64 hcTally[16] = {}; h10x_hash_copies_info hcInfo{};
   // streaming ingest (h10x_ingest_fqb): the record image grows on the device as the chunks arrive
   DevBuf<u32> ingestBuf; u64 ingestRecords = 0, ingestCap = 0; bool ingestAsync = false;   // ingestAsync: chunks came through h10x_ingest_fqb_async (the closing call then checks the count)
   static constexpr int INGEST_SLOTS = 8; hipEvent_t ingestEv[INGEST_SLOTS] = {};   // h10x_ingest_fqb_async: one event per caller's buffer
@@ -462,6 +465,10 @@ int stageM_add(Ctx *c, u32 codeMin, u32 codeMax);
 int stageM_finish(Ctx *c, h10x_share_components_info *info);
 int stageM_get(Ctx *c, u32 *comp, u32 *root, u32 *rootOf, u32 *nMember, u64 *records, u64 capBlocks, u64 capComps);
 void stageM_release(Ctx *c);
+int stageN_run(Ctx *c, int64_t minShare, h10x_hash_copies_info *info);
+int stageN_get(Ctx *c, uint16_t *out, u64 first, u64 count, int toDevice);
+int stageN_tally(Ctx *c, u64 *counts15);
+void stageN_release(Ctx *c);
 int stageJ_censusBegin(Ctx *c, u64 hint);
 int stageJ_censusAdd(Ctx *c, const u32 *dRec, u64 n);
 int stageJ_censusClose(Ctx *c, int64_t thresh, h10x_census_t *out);

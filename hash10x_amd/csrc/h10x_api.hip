@@ -230,7 +230,7 @@ const char *h10x_last_error(const h10x_ctx *h) { return h ? h->c.err.c_str() : "
 
 static void reset_state(Ctx &c) {
   c.haveState = false; c.haveRange = false; c.haveGood = false; c.rangeMin = c.rangeMax = 0; c.depthBound = 0xFFFFFFFFu; c.rangeHiMax = 0;
-  stageL_release(&c); stageM_release(&c);
+  stageL_release(&c); stageM_release(&c); stageN_release(&c);
   c.within.release(); c.goodPos.release(); c.nGood.release(); c.goodEntries.release(); c.goodRow.release();
   // the tables of the state being replaced go back to the block cache NOW, not when their successors are swapped in: the second --readFQB of a
   // context then finds every block of the first one parked and allocates nothing (kept until the swap, rows[] and clusHash had no twin in the
@@ -400,7 +400,7 @@ int h10x_shard_agree(h10x_ctx *h, int ok, int *allOk) {
 int h10x_depth_range(h10x_ctx *h, int32_t lo, int32_t hi) {
   if (!h) return -1;
   H10X_TRY(enter(h->c));
-  stageL_release(&h->c); stageM_release(&h->c);               // a kept share graph, and kept components, are of the lists this call replaces
+  stageL_release(&h->c); stageM_release(&h->c); stageN_release(&h->c);   // a kept share graph, kept components and kept hash copies are of the lists this call replaces
   return stageC_depthRange(&h->c, lo, hi);
 }
 
@@ -413,7 +413,7 @@ int h10x_cluster(h10x_ctx *h, int32_t codeMin, int32_t codeMax, int32_t threshol
 int h10x_cluster_split(h10x_ctx *h) {
   if (!h) return -1;
   H10X_TRY(enter(h->c));
-  stageL_release(&h->c); stageM_release(&h->c);               // (and of the blocks this call renumbers)
+  stageL_release(&h->c); stageM_release(&h->c); stageN_release(&h->c);   // (and of the blocks this call renumbers)
   return stageC_split(&h->c);
 }
 
@@ -687,6 +687,14 @@ int h10x_share_components_get(h10x_ctx *h, uint32_t *comp, uint32_t *root, uint3
                               uint64_t capComps) {
   if (!h) return -1; H10X_TRY(enter(h->c)); return stageM_get(&h->c, comp, root, rootOf, blocks, (u64 *)records, capBlocks, capComps);
 }
+
+// ---- the per-hash linkage groups (stage_n.hip) ----
+int h10x_hash_copies_run(h10x_ctx *h, int64_t minShare, h10x_hash_copies_info *info) { if (!h || !info) return -1; H10X_TRY(enter(h->c)); return stageN_run(&h->c, minShare, info); }
+int h10x_hash_copies_get(h10x_ctx *h, uint16_t *out, uint64_t first, uint64_t count) { if (!h) return -1; H10X_TRY(enter(h->c)); return stageN_get(&h->c, out, first, count, 0); }
+int h10x_hash_copies_get_device(h10x_ctx *h, uint16_t *devOut, uint64_t first, uint64_t count) {
+  if (!h) return -1; H10X_TRY(enter(h->c)); return stageN_get(&h->c, devOut, first, count, 1);
+}
+int h10x_hash_copies_tally(h10x_ctx *h, uint64_t counts[5][3]) { if (!h || !counts) return -1; H10X_TRY(enter(h->c)); return stageN_tally(&h->c, (u64 *)&counts[0][0]); }
 
 int h10x_timing_enable(h10x_ctx *h, int on) { if (!h) return -1; h->c.timing = on != 0; return 0; }
 int h10x_timing_count(const h10x_ctx *) { return T_COUNT; }

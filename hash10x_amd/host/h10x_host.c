@@ -1850,3 +1850,58 @@ done:
   free(comp); free(rootOf); free(blocks); free(records);
   return rc;
 }
+
+/* ---- --hashCopies <minShare> <out.hc>: per in-range hash the linkage groups of its own blocks (h10x_hash_copies_*). The table stays on the device;
+   the file is written in slabs of 2^22 hashes, so the host never holds it. ---- */
+int h10x_session_hashCopiesRun(h10x_session *s, int minShare, h10x_hash_copies_info *info) {
+  if (!s->ctx) return fail(s, "!! you must set hashDepthRange before hashCopies");      /* nothing loaded: no range either */
+  h10x_shard_info_t z; if (h10x_shard_info(s->ctx, &z)) return fail_ctx(s);
+  if (z.nranks > 1) return fail(s, "hashCopies does not run on a sharded session (--gpus > 1)");
+  if (h10x_hash_copies_run(s->ctx, minShare, info)) return fail_ctx(s);
+  return 0;
+}
+
+int h10x_host_write_hash_copies(const char *path, const h10x_hash_copies_info *info, h10x_hash_copies_slab_fn slab, void *user, uint64_t slabHashes,
+                                char *err, int errlen) {
+  if (!slabHashes) slabHashes = (uint64_t)1 << 22;
+  const uint64_t n = info->hashNumber, cap = n < slabHashes ? (n ? n : 1) : slabHashes;
+  uint16_t *buf = (uint16_t *)malloc((size_t)cap * 8);
+  if (!buf) { snprintf(err, (size_t)errlen, "out of host memory for a slab of %llu hashes", (unsigned long long)cap); return -1; }
+  FILE *f = fopen(path, "wb");
+  if (!f) { free(buf); snprintf(err, (size_t)errlen, "failed to open output file %s", path); return -1; }
+  const uint32_t version = 1; unsigned char head[32]; int ok = 1, rc = 0;
+  memcpy(head, "10XK", 4); memcpy(head + 4, &version, 4); memcpy(head + 8, &info->hashNumber, 4); memcpy(head + 12, &info->minShare, 4);
+  memcpy(head + 16, &info->inRange, 8); memcpy(head + 24, &info->rows, 8);
+  ok = fwrite(head, 1, 32, f) == 32;
+  for (uint64_t first = 0; ok && !rc && first < n; first += cap) {
+    const uint64_t count = n - first < cap ? n - first : cap;
+    if (slab(user, buf, first, count)) { rc = -2; break; }          /* the callback's own error stands */
+    ok = fwrite(buf, 8, (size_t)count, f) == (size_t)count;
+  }
+  if (fclose(f)) ok = 0;
+  free(buf);
+  if (!rc && !ok) { snprintf(err, (size_t)errlen, "failed to write %s", path); rc = -1; }
+  return rc;
+}
+
+static int hc_slab_from_ctx(void *user, uint16_t *out, uint64_t first, uint64_t count) { return h10x_hash_copies_get((h10x_ctx *)user, out, first, count); }
+
+int h10x_session_hashCopies(h10x_session *s, int minShare, const char *outPath, FILE *out) {
+  h10x_hash_copies_info info;
+  if (h10x_session_hashCopiesRun(s, minShare, &info)) return -1;
+  const int w = h10x_host_write_hash_copies(outPath, &info, hc_slab_from_ctx, s->ctx, 0, s->err, (int)sizeof s->err);
+  if (w == -2) return fail_ctx(s);
+  if (w) return -1;
+  if (!out) return 0;
+  fprintf(out, "  hash copies at minShare %d: %llu hashes in range, %llu rows, %llu in one group, %llu split, deepest list %u\n", minShare,
+          (unsigned long long)info.inRange, (unsigned long long)info.rows, (unsigned long long)info.oneGroup, (unsigned long long)info.split, info.deepest);
+  uint32_t histDim = 0;
+  if (h10x_crib_sizes(s->ctx, &histDim, 0) == 0) {                  /* with a crib: how the tallies fall on its types */
+    uint64_t counts[5][3];
+    if (h10x_hash_copies_tally(s->ctx, counts)) return fail_ctx(s);
+    for (int t = 0; t < 5; ++t)
+      fprintf(out, "HASH_COPIES  %s n %llu one %llu split %llu\n", cribTypeName[t], (unsigned long long)counts[t][0], (unsigned long long)counts[t][1],
+              (unsigned long long)counts[t][2]);
+  }
+  return 0;
+}

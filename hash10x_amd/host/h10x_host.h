@@ -132,6 +132,22 @@ int  h10x_session_shareComponentsRun(h10x_session *s, int minShare, h10x_share_c
 int  h10x_host_write_share_components(const char *path, const h10x_share_components_info *info, const uint32_t *comp, const uint32_t *rootOf,
                                       const uint32_t *blocks, const uint64_t *records, char *err, int errlen);
 
+/* --hashCopies <minShare> <out.hc> (addition; include/h10x.h "the per-hash linkage groups"): for every hash in the depth range the linkage groups of the
+   blocks that hold it — one group for a hash at one locus, two that do not link for a hash at two. The file, little-endian: magic "10XK", u32 version 1,
+   u32 hashNumber, u32 minShare, u64 inRange, u64 rows, then hashNumber records {u16 distinct, u16 groups, u16 largest, u16 second} (zeros outside the
+   range and at index 0), written in slabs of 2^22 hashes. One line of counts to out (may be NULL) and, with a crib, five lines
+   "HASH_COPIES  <err|htA|htB|hom|mul> n <in range> one <groups == 1> split <second >= 2>". Fails with "!! ..." (the command then does nothing, no file
+   is written) before --hashDepthRange, after --clusterSplit until a new range is set, for minShare < 1 and when an in-range hash is deeper than 4096;
+   single-GPU sessions only.
+   h10x_session_hashCopiesRun is the run alone: the result stays in the context for h10x_hash_copies_get.
+   h10x_host_write_hash_copies writes the file from a callback that fills records [first, first + count) (no device); slabHashes = 0: 2^22. It returns
+   -2 when the callback failed (err untouched), -1 with err set for its own failures. */
+typedef int (*h10x_hash_copies_slab_fn)(void *user, uint16_t *out, uint64_t first, uint64_t count);
+int  h10x_session_hashCopies(h10x_session *s, int minShare, const char *outPath, FILE *out);
+int  h10x_session_hashCopiesRun(h10x_session *s, int minShare, h10x_hash_copies_info *info);
+int  h10x_host_write_hash_copies(const char *path, const h10x_hash_copies_info *info, h10x_hash_copies_slab_fn slab, void *user, uint64_t slabHashes,
+                                 char *err, int errlen);
+
 /* multi-GPU (include/h10x.h "multi-GPU"): one session per rank, each holding a contiguous barcode range of the sorted file
    (cut with h10x_host_partition / _partition_file; -N is applied by the launcher before cutting). Every command of a
    sharded session is collective: all ranks call it with the same arguments; the text commands print on the rank whose

@@ -463,6 +463,44 @@ int  h10x_share_components_finish(h10x_ctx *ctx, h10x_share_components_info *inf
 int  h10x_share_components_get(h10x_ctx *ctx, uint32_t *comp, uint32_t *root, uint32_t *rootOf, uint32_t *blocks, uint64_t *records,
                                uint64_t capBlocks, uint64_t capComps);
 
+/* ---- the per-hash linkage groups (csrc/stage_n.hip): at how many places of the genome does a hash sit ----
+   State: as for the share graph, an unsharded context with a --hashDepthRange in force. T = minShare >= 1.
+   For a hash index x >= 1 with hashWithinRange[x] set:
+     L(x) = its barcode list: one entry per ClusterHash record of x, ascending, a block as often as it holds x.
+     D(x) = the distinct blocks of L(x), m = |D(x)|.
+     Graph on D(x): a and b (a != b) are joined when countShare_a[b] >= T or countShare_b[a] >= T, countShare as the share graph above
+     defines it. x itself counts: every pair of D(x) shares at least x. Either direction joins, as for the components: a block of more
+     than 65535 records has an empty row of its own and is joined through the rows of the others.
+     distinct = m, groups = the connected components of that graph, largest = the member count of the largest component, second = that of
+     the second largest (0 with one group). Four u16 values per hash; hashes outside the range, and index 0, get four zeros.
+   So at T = 1 a hash whose blocks are not all above 65535 records has groups = 1 and largest = m; at T = 2^31 - 1 groups = m, largest = 1
+   and second = 1 if m > 1; groups does not fall as T rises. A hash at one locus tends to one group, a hash at two loci to two that do not
+   link: thresholds on second / largest are the caller's.
+   The result depends on none of "neighbour_budget", the order in which atomics land, or the run: two calls give the same bytes.
+   A list of more than 4096 entries in range is refused for the whole call ("!! hashCopies needs every hash in range to have depth <= 4096
+   (deepest N)"): a wave's working set then has a fixed bound in LDS and u16 holds every figure.
+   h10x_hash_copies_run runs the census of h10x_share_graph_run over all blocks at T (the rows stay on the device and are dropped at the
+     end; a share graph or components kept from an earlier call are dropped too), then one wave per in-range hash: the list deduped into LDS,
+     each member's row streamed and looked up there, the hits hooked by union by smaller label in LDS until a pass hooks nothing (bounded;
+     running out of passes is an error), the members per root counted. info: hashNumber, minShare, inRange = the hashes x >= 1 in range,
+     rows / listEntries / batches / windows of the census, deepest = the longest in-range list, oneGroup = hashes with groups = 1, split =
+     hashes with second >= 2.
+   h10x_hash_copies_get copies records [first, first + count) (4 x u16 each) to host memory, _get_device to device memory. out = NULL asks
+     whether a result is kept: 0 if so.
+   h10x_hash_copies_tally: counts[t][0 .. 2] = in-range hashes, those with groups = 1, those with second >= 2, per crib type t (err, htA, htB,
+     hom, mul; everything under 0 when no crib was built at the time of the run).
+   The kept result is released by the next run (also a refused one), h10x_depth_range, h10x_cluster_split, a new state and h10x_destroy.
+   The run fails without a state, on a sharded context, before --hashDepthRange and after --clusterSplit until a new range is set ("!! you
+   must set hashDepthRange before hashCopies"), for minShare < 1 ("!! hashCopies minShare ... must be >= 1") and above the depth cap. */
+typedef struct {
+  uint64_t inRange, rows, listEntries, oneGroup, split;
+  uint32_t hashNumber, minShare, deepest, batches, windows, reserved;
+} h10x_hash_copies_info;
+int  h10x_hash_copies_run(h10x_ctx *ctx, int64_t minShare, h10x_hash_copies_info *info);
+int  h10x_hash_copies_get(h10x_ctx *ctx, uint16_t *out, uint64_t first, uint64_t count);
+int  h10x_hash_copies_get_device(h10x_ctx *ctx, uint16_t *dev_out, uint64_t first, uint64_t count);
+int  h10x_hash_copies_tally(h10x_ctx *ctx, uint64_t counts[5][3]);
+
 /* ---- mosh sets (csrc/stage_g.hip): the Moshset object of the reference's moshutils (moshset.h, moshset.c, moshutils.c) ----
    A second opaque handle beside the context. A set is the probe table index[2^B] (moshsetIndexFind, moshset.c:45-61) and, per index
    1 .. max in order of first appearance, value (the hash), depth (saturating at 65535) and info (low two bits = copy class 0, 1, 2, M).
