@@ -457,6 +457,32 @@ int stageF_neighbourHist(Ctx *c, const u32 *xs, u32 nq, const u64 *offsets, u32 
 int stageF_codeShare(Ctx *c, const u32 *codes, u32 nq, u64 *offsets, u32 *barcode, u32 *count, u32 *firstRank, u32 *firstHash, u64 cap);
 int stageF_codeExplore(Ctx *c, int code, int threshold, u32 *out /* 8: h10x_code_explore_rep */);
 int stageF_codeCrib(Ctx *c, const u32 *codes, u32 n, u32 *out);
+// the census family (stage_f / stage_l / stage_m / stage_n): what its drivers share
+int ce_check(Ctx *c, const char *cmd, int64_t minShare = 1);   // the refusals: no state, a sharded context, no good lists, minShare < 1 (stage_f.hip)
+inline int keyBits(u64 v) { int b = 1; while (b < 64 && (v >> b)) ++b; return b; }   // bits that hold 0 .. v (at least one)
+// The batch cutter. Queries [0, nq) with size[q] records each over the index range [0, top), in order: as many whole queries to a batch as fit
+// the budget; a query above the budget runs alone in windows of index, halved until their records fit (a window of one index always runs).
+// sizeIn(q, lo, hi, &records): the records of query q in [lo, hi). run(q0, n, lo, hi, full, records): one batch; full = false marks a window
+template <typename SizeIn, typename Run>
+int cut_windows(u32 q, u32 lo, u32 hi, u64 records, u64 budget, SizeIn &sizeIn, Run &run) {
+  if (!records) return 0;
+  if (records <= budget || hi - lo <= 1) return run(q, 1, lo, hi, false, records);
+  const u32 mid = lo + (hi - lo) / 2;
+  u64 left = 0; H10X_TRY(sizeIn(q, lo, mid, &left));
+  H10X_TRY(cut_windows(q, lo, mid, left, budget, sizeIn, run));
+  return cut_windows(q, mid, hi, records - left, budget, sizeIn, run);
+}
+template <typename SizeIn, typename Run>
+int cut_batches(const u64 *size, u32 nq, u32 top, u64 budget, SizeIn sizeIn, Run run) {
+  for (u32 q0 = 0; q0 < nq;) {
+    if (size[q0] > budget) { H10X_TRY(cut_windows(q0, 0, top, size[q0], budget, sizeIn, run)); ++q0; continue; }
+    u32 q1 = q0; u64 sum = 0;
+    while (q1 < nq && size[q1] <= budget && sum + size[q1] <= budget) sum += size[q1++];
+    H10X_TRY(run(q0, q1 - q0, 0, top, true, sum));
+    q0 = q1;
+  }
+  return 0;
+}
 int stageL_run(Ctx *c, int64_t minShare, u32 codeMin, u32 codeMax, h10x_share_graph_info *info);
 int stageL_get(Ctx *c, u64 *offsets, u32 *block, u32 *count, u64 cap, int toDevice);
 void stageL_release(Ctx *c);
@@ -469,6 +495,7 @@ int stageN_run(Ctx *c, int64_t minShare, h10x_hash_copies_info *info);
 int stageN_get(Ctx *c, uint16_t *out, u64 first, u64 count, int toDevice);
 int stageN_tally(Ctx *c, u64 *counts15);
 void stageN_release(Ctx *c);
+inline void release_share_results(Ctx *c) { stageL_release(c); stageM_release(c); stageN_release(c); }   // the kept graph, components and hash copies
 int stageJ_censusBegin(Ctx *c, u64 hint);
 int stageJ_censusAdd(Ctx *c, const u32 *dRec, u64 n);
 int stageJ_censusClose(Ctx *c, int64_t thresh, h10x_census_t *out);

@@ -230,7 +230,7 @@ const char *h10x_last_error(const h10x_ctx *h) { return h ? h->c.err.c_str() : "
 
 static void reset_state(Ctx &c) {
   c.haveState = false; c.haveRange = false; c.haveGood = false; c.rangeMin = c.rangeMax = 0; c.depthBound = 0xFFFFFFFFu; c.rangeHiMax = 0;
-  stageL_release(&c); stageM_release(&c); stageN_release(&c);
+  release_share_results(&c);
   c.within.release(); c.goodPos.release(); c.nGood.release(); c.goodEntries.release(); c.goodRow.release();
   // the tables of the state being replaced go back to the block cache NOW, not when their successors are swapped in: the second --readFQB of a
   // context then finds every block of the first one parked and allocates nothing (kept until the swap, rows[] and clusHash had no twin in the
@@ -400,7 +400,7 @@ int h10x_shard_agree(h10x_ctx *h, int ok, int *allOk) {
 int h10x_depth_range(h10x_ctx *h, int32_t lo, int32_t hi) {
   if (!h) return -1;
   H10X_TRY(enter(h->c));
-  stageL_release(&h->c); stageM_release(&h->c); stageN_release(&h->c);   // a kept share graph, kept components and kept hash copies are of the lists this call replaces
+  release_share_results(&h->c);   // a kept share graph, kept components and kept hash copies are of the lists this call replaces
   return stageC_depthRange(&h->c, lo, hi);
 }
 
@@ -413,7 +413,7 @@ int h10x_cluster(h10x_ctx *h, int32_t codeMin, int32_t codeMax, int32_t threshol
 int h10x_cluster_split(h10x_ctx *h) {
   if (!h) return -1;
   H10X_TRY(enter(h->c));
-  stageL_release(&h->c); stageM_release(&h->c); stageN_release(&h->c);   // (and of the blocks this call renumbers)
+  release_share_results(&h->c);   // (and of the blocks this call renumbers)
   return stageC_split(&h->c);
 }
 

@@ -23,6 +23,7 @@
 // msMax / msTot and ce_replay_kernel replays the order-dependent part in one workgroup.
 #include "common.hpp"
 #include "prim.hpp"
+#include "wave.hpp"
 
 namespace h10x {
 
@@ -31,19 +32,6 @@ enum { KIND_HASH = 0, KIND_CODE = 1 };                       // census of a hash
 static constexpr u64 NB_DEFAULT_BUDGET = 1ull << 26;       // gathered records per batch: 2 x 8 bytes each for the sort = 1 GiB
 static constexpr int CE_RANK_BITS = 16;                      // good ranks of a block (nHash <= 65535: goodHashesBuild, hash10x.c:748)
 
-static int nbBits(u64 v) { int b = 1; while (b < 64 && (v >> b)) ++b; return b; }
-
-// entries [a, b) of the barcode list at `row` (ascending barcode) with barcode in [lo, hi); full = the window covers every barcode
-__device__ __forceinline__ void ce_window(const u32 *__restrict__ rows, u64 row, u32 len, u32 lo, u32 hi, bool full, u64 &a, u64 &b) {
-  a = row; b = row + len;
-  if (full) return;
-  u64 l = a, r = b;
-  while (l < r) { const u64 m = (l + r) >> 1; if (rows[m] < lo) l = m + 1; else r = m; }
-  const u64 s = l; r = b;
-  while (l < r) { const u64 m = (l + r) >> 1; if (rows[m] < hi) l = m + 1; else r = m; }
-  a = s; b = l;
-}
-
 // barcode census, one wave per query: list entries of its good ranks in the window (size), and its rank count (the gather's units)
 __global__ void ce_size_kernel(const u32 *__restrict__ codes, u32 nq, const u32 *__restrict__ nGood, const u64 *__restrict__ blockOff,
                                const u64 *__restrict__ goodRow, const u32 *__restrict__ rows, u32 rowShift, u32 lo, u32 hi, int full,
@@ -51,13 +39,7 @@ __global__ void ce_size_kernel(const u32 *__restrict__ codes, u32 nq, const u32 
   const u32 lane = threadIdx.x & (WAVE - 1);
   const u32 q = (blockIdx.x * blockDim.x + threadIdx.x) / WAVE;
   if (q >= nq) return;
-  const u32 code = codes[q], n = nGood[code]; const u64 o = blockOff[code];
-  u64 s = 0;
-  for (u32 i = lane; i < n; i += WAVE) {
-    const u64 d = goodRow[o + i]; u64 a, b;
-    ce_window(rows, (u64)(u32)d << rowShift, (u32)(d >> 32), lo, hi, full != 0, a, b); s += b - a;
-  }
-  for (int k = 32; k; k >>= 1) s += __shfl_xor(s, k);
+  u32 n; const u64 s = good_list_entries(codes[q], nGood, blockOff, goodRow, rows, rowShift, lo, hi, full != 0, n);
   if (lane == 0) { size[q] = s; qUnits[q] = n; }
 }
 
@@ -71,11 +53,8 @@ __global__ __launch_bounds__(256) void ce_gather_kernel(const u32 *__restrict__ 
   const u64 units = unitBase[nq];
   const u64 w0 = ((u64)blockIdx.x * blockDim.x + threadIdx.x) / WAVE, wStride = ((u64)gridDim.x * blockDim.x) / WAVE;
   for (u64 u = w0; u < units; u += wStride) {
-    u32 l = 0, r = nq;                                        // the query: last q with unitBase[q] <= u
-    while (r - l > 1) { const u32 m = (l + r) >> 1; if (unitBase[m] <= u) l = m; else r = m; }
-    const u32 q = l, code = codes[q], rank = (u32)(u - unitBase[q]);
-    const u64 d = goodRow[blockOff[code] + rank];
-    u64 a, b; ce_window(rows, (u64)(u32)d << rowShift, (u32)(d >> 32), lo, hi, full != 0, a, b);
+    const u32 q = last_le(unitBase, nq, u), code = codes[q], rank = (u32)(u - unitBase[q]);
+    u64 a, b; list_window(rows, goodRow[blockOff[code] + rank], rowShift, lo, hi, full != 0, a, b);
     const u64 tag = ((u64)q << sbits) | rank;
     u64 cnt = 0;
     for (u64 e = a; e < b; e += WAVE) {                       // wave-uniform trip counts
@@ -90,10 +69,8 @@ __global__ __launch_bounds__(256) void ce_gather_kernel(const u32 *__restrict__ 
       const u64 j = e + lane;
       u32 cj = 0; bool keep = false;
       if (j < b) { cj = rows[j]; keep = cj != code; }
-      const u64 m = __ballot(keep);
-      const u64 p = p0 + __popcll(m & ((1ull << lane) - 1));
+      const u64 p = wave_place(keep, p0);
       if (keep && p < cap) keys[p] = tag | ((u64)cj << CE_RANK_BITS);   // (p < cap always: cap = entries in the window)
-      p0 += __popcll(m);
     }
   }
 }
@@ -120,7 +97,7 @@ __global__ void nb_size_kernel(const u32 *__restrict__ xs, u32 nq, const u32 *__
   const u32 x = xs[q], d = depth[x]; const u64 rs = rowStart[x];
   u64 s = 0;
   for (u32 i = lane; i < d; i += WAVE) { u64 a, b; nb_window(ch, blockOff, rows[rs + i], lo, hi, full != 0, a, b); s += b - a; }
-  for (int k = 32; k; k >>= 1) s += __shfl_xor(s, k);
+  s = wave_sum(s);
   if (lane == 0) { size[q] = s; qDepth[q] = d; }
 }
 
@@ -134,9 +111,7 @@ __global__ __launch_bounds__(256) void nb_gather_kernel(const u32 *__restrict__ 
   const u64 units = unitBase[nq];
   const u64 w0 = ((u64)blockIdx.x * blockDim.x + threadIdx.x) / WAVE, wStride = ((u64)gridDim.x * blockDim.x) / WAVE;
   for (u64 u = w0; u < units; u += wStride) {
-    u32 l = 0, r = nq;                                        // the query: last q with unitBase[q] <= u
-    while (r - l > 1) { const u32 m = (l + r) >> 1; if (unitBase[m] <= u) l = m; else r = m; }
-    const u32 q = l, x = xs[q];
+    const u32 q = last_le(unitBase, nq, u), x = xs[q];
     const u32 blk = rows[rowStart[x] + (u - unitBase[q])];
     u64 a, b; nb_window(ch, blockOff, blk, lo, hi, full != 0, a, b);
     const u64 slot = (u64)q << hbits;
@@ -157,10 +132,8 @@ __global__ __launch_bounds__(256) void nb_gather_kernel(const u32 *__restrict__ 
       const u64 j = e + lane;
       u32 h = 0; bool keep = false;
       if (j < b) { h = ch[j].hash; keep = h != x && within[h]; }
-      const u64 m = __ballot(keep);
-      const u64 p = p0 + __popcll(m & ((1ull << lane) - 1));
+      const u64 p = wave_place(keep, p0);
       if (keep && p < cap) keys[p] = slot | h;               // p < cap always (cap = records in the window); the test keeps a miscount in bounds
-      p0 += __popcll(m);
     }
   }
 }
@@ -329,7 +302,7 @@ struct Census {
   PrimTemp pt;
 
   u32 top() const { return kind == KIND_CODE ? c->nBlocks : c->hashNumber; }   // the window that covers everything: [0, top)
-  int idBits() const { return kind == KIND_CODE ? nbBits(c->nBlocks) + CE_RANK_BITS : nbBits(c->hashNumber); }   // key bits below the slot
+  int idBits() const { return kind == KIND_CODE ? keyBits(c->nBlocks) + CE_RANK_BITS : keyBits(c->hashNumber); }   // key bits below the slot
 
   int sizes(const u32 *dX, u32 nq, u32 lo, u32 hi, bool full, u64 *hSize, u32 *hDepth) {
     DevBuf<u64> s; DevBuf<u32> d; hipStream_t st = c->stream;
@@ -347,9 +320,10 @@ struct Census {
     return 0;
   }
 
-  // queries [q0, q0 + nq) of the call in the window [lo, hi); total = records gathered
+  // queries [q0, q0 + nq) of the call in the window [lo, hi); total = records gathered. !full: one window of a query above the budget
   int batch(u32 q0, u32 nq, u32 lo, u32 hi, bool full, u64 total) {
     hipStream_t st = c->stream;
+    if (!full) c->nbStats[3] += 1;
     c->nbStats[2] += 1;
     if (!total) return 0;
     std::vector<u64> ub(nq + 1); ub[0] = 0;
@@ -359,7 +333,7 @@ struct Census {
     if (keys.n < total) { H10X_HIP(c, keys.alloc(total)); H10X_HIP(c, keys2.alloc(total)); }
     if (!nKept.p) H10X_HIP(c, nKept.alloc(1));
     H10X_HIP(c, hipMemsetAsync(nKept.p, 0, 8, st));
-    const int hbits = idBits(), lowBits = kind == KIND_CODE ? CE_RANK_BITS : 0, endBit = hbits + nbBits(nq - 1);
+    const int hbits = idBits(), lowBits = kind == KIND_CODE ? CE_RANK_BITS : 0, endBit = hbits + keyBits(nq - 1);
     const unsigned g = (unsigned)hmin<u64>(divUp(ub[nq], 4), 65536);
     if (kind == KIND_CODE)
       ce_gather_kernel<<<g, 256, 0, st>>>(dXs + q0, nq, unitBase.p, c->blockOff.p, c->goodRow.p, c->rows.p, (u32)c->rowShift,
@@ -414,25 +388,10 @@ struct Census {
     return 0;
   }
 
-  // one query above the budget: windows of hash (barcode) index, halved until their records fit (a window of one index always runs)
-  int windowed(u32 q, u32 lo, u32 hi, u64 records) {
-    if (!records) return 0;
-    if (records <= budget || hi - lo <= 1) { c->nbStats[3] += 1; return batch(q, 1, lo, hi, false, records); }
-    const u32 mid = lo + (hi - lo) / 2;
-    u64 left = 0; H10X_TRY(sizes(dXs + q, 1, lo, mid, false, &left, nullptr));
-    H10X_TRY(windowed(q, lo, mid, left));
-    return windowed(q, mid, hi, records - left);
-  }
-
   int run(u32 nq) {
-    for (u32 q0 = 0; q0 < nq;) {
-      if (size[q0] > budget) { H10X_TRY(windowed(q0, 0, top(), size[q0])); ++q0; continue; }
-      u32 q1 = q0; u64 sum = 0;
-      while (q1 < nq && size[q1] <= budget && sum + size[q1] <= budget) sum += size[q1++];
-      H10X_TRY(batch(q0, q1 - q0, 0, top(), true, sum));
-      q0 = q1;
-    }
-    return 0;
+    return cut_batches(size.data(), nq, top(), budget,
+                       [&](u32 q, u32 lo, u32 hi, u64 *records) { return sizes(dXs + q, 1, lo, hi, false, records, nullptr); },
+                       [&](u32 q0, u32 n, u32 lo, u32 hi, bool full, u64 total) { return batch(q0, n, lo, hi, full, total); });
   }
 };
 
@@ -453,14 +412,17 @@ int nb_begin(Ctx *c, Census &k, DevBuf<u32> &dX, const u32 *xs, u32 nq) {
   return k.sizes(dX.p, nq, 0, k.top(), true, k.size.data(), k.depth.data());
 }
 
-// the barcode census and --codeExplore: one GPU holding the whole data set, good lists that belong to the current blocks
-int ce_check(Ctx *c, const char *cmd) {
+}  // namespace
+
+// the barcode census and what is built on it (--codeExplore, --shareGraph, --shareComponents, --hashCopies): one GPU holding the whole
+// data set, good lists that belong to the current blocks, and for the share commands a threshold of at least 1
+int ce_check(Ctx *c, const char *cmd, int64_t minShare) {
   if (!c->haveState) return c->fail("no hash state loaded: use readFQB or readHash first");
   if (c->sharded) return c->fail("%s: not available on a sharded context (one rank holds only its own barcodes)", cmd);
   if (!c->haveGood) return c->fail("!! you must set hashDepthRange before %s", cmd);    // hash10x.c:1230 (after --clusterSplit too: the lists are of the old blocks)
+  if (minShare < 1) return c->fail("!! %s minShare %lld must be >= 1", cmd, (long long)minShare);
   return 0;
 }
-}  // namespace
 
 int stageF_codeShare(Ctx *c, const u32 *codes, u32 nq, u64 *offsets, u32 *barcode, u32 *count, u32 *firstRank, u32 *firstHash, u64 cap) {
   H10X_TRY(ce_check(c, "codeShare"));

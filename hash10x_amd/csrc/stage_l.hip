@@ -16,23 +16,11 @@
 // against "neighbour_budget"; a block above it runs alone in windows of barcode index (whole runs each: the lists ascend), as in stage_f.hip.
 #include "common.hpp"
 #include "prim.hpp"
+#include "wave.hpp"
 
 namespace h10x {
 
 static constexpr u64 SG_DEFAULT_BUDGET = 1ull << 26;       // list entries per batch (stage_f.hip's NB_DEFAULT_BUDGET)
-
-static int sgBits(u64 v) { int b = 1; while (b < 64 && (v >> b)) ++b; return b; }
-
-// entries [a, b) of the barcode list at `row` (ascending barcode) with barcode in [lo, hi); full = the window covers every barcode
-__device__ __forceinline__ void sg_window(const u32 *__restrict__ rows, u64 row, u32 len, u32 lo, u32 hi, bool full, u64 &a, u64 &b) {
-  a = row; b = row + len;
-  if (full) return;
-  u64 l = a, r = b;
-  while (l < r) { const u64 m = (l + r) >> 1; if (rows[m] < lo) l = m + 1; else r = m; }
-  const u64 s = l; r = b;
-  while (l < r) { const u64 m = (l + r) >> 1; if (rows[m] < hi) l = m + 1; else r = m; }
-  a = s; b = l;
-}
 
 // one wave per block c0 + q: size[q] = entries of its good hashes' lists in the window (the block's own included)
 __global__ void sg_size_kernel(u32 c0, u32 nq, const u32 *__restrict__ nGood, const u64 *__restrict__ blockOff, const u64 *__restrict__ goodRow,
@@ -40,13 +28,7 @@ __global__ void sg_size_kernel(u32 c0, u32 nq, const u32 *__restrict__ nGood, co
   const u32 lane = threadIdx.x & (WAVE - 1);
   const u32 q = (blockIdx.x * blockDim.x + threadIdx.x) / WAVE;
   if (q >= nq) return;
-  const u32 code = c0 + q, n = nGood[code]; const u64 o = blockOff[code];
-  u64 s = 0;
-  for (u32 i = lane; i < n; i += WAVE) {
-    const u64 d = goodRow[o + i]; u64 a, b;
-    sg_window(rows, (u64)(u32)d << rowShift, (u32)(d >> 32), lo, hi, full != 0, a, b); s += b - a;
-  }
-  for (int k = 32; k; k >>= 1) s += __shfl_xor(s, k);
+  u32 n; const u64 s = good_list_entries(c0 + q, nGood, blockOff, goodRow, rows, rowShift, lo, hi, full != 0, n);
   if (lane == 0) size[q] = s;
 }
 
@@ -60,13 +42,9 @@ __global__ void sg_list_kernel(u32 c0, u32 nq, const u64 *__restrict__ unitBase,
   const u32 code = c0 + q; const u64 o = blockOff[code], u0 = unitBase[q] - unitBase[0];
   const u32 n = (u32)(unitBase[q + 1] - unitBase[q]);
   for (u32 i = lane; i < n; i += WAVE) {
-    const u64 d = goodRow[o + i]; u64 a, b;
-    sg_window(rows, (u64)(u32)d << rowShift, (u32)(d >> 32), lo, hi, full != 0, a, b);
-    u64 l = a, r = b;                                       // the list's own entries of `code`: [s, l)
-    while (l < r) { const u64 m = (l + r) >> 1; if (rows[m] < code) l = m + 1; else r = m; }
-    const u64 s = l; r = b;
-    while (l < r) { const u64 m = (l + r) >> 1; if (rows[m] <= code) l = m + 1; else r = m; }
-    listCnt[u0 + i] = (u32)((b - a) - (l - s));
+    u64 a, b; list_window(rows, goodRow[o + i], rowShift, lo, hi, full != 0, a, b);
+    const u64 s = lower_bound(rows, a, b, code), e = upper_bound(rows, s, b, code);   // the list's own entries of `code`: [s, e)
+    listCnt[u0 + i] = (u32)((b - a) - (e - s));
   }
 }
 
@@ -79,21 +57,16 @@ __global__ __launch_bounds__(256) void sg_gather_kernel(u32 c0, u32 nq, const u6
   const u64 base = unitBase[0], units = unitBase[nq] - base;
   const u64 w0 = ((u64)blockIdx.x * blockDim.x + threadIdx.x) / WAVE, wStride = ((u64)gridDim.x * blockDim.x) / WAVE;
   for (u64 u = w0; u < units; u += wStride) {
-    u32 l = 0, r = nq;                                        // the block: last q with unitBase[q] - base <= u
-    while (r - l > 1) { const u32 m = (l + r) >> 1; if (unitBase[m] - base <= u) l = m; else r = m; }
-    const u32 q = l, code = c0 + q, rank = (u32)(u - (unitBase[q] - base));
-    const u64 d = goodRow[blockOff[code] + rank];
-    u64 a, b; sg_window(rows, (u64)(u32)d << rowShift, (u32)(d >> 32), lo, hi, full != 0, a, b);
+    const u32 q = last_le(unitBase, nq, base + u), code = c0 + q, rank = (u32)(u - (unitBase[q] - base));   // (unitBase[0] = base)
+    u64 a, b; list_window(rows, goodRow[blockOff[code] + rank], rowShift, lo, hi, full != 0, a, b);
     const K tag = (K)q << cbits;
     u64 p0 = listPos[u];
     for (u64 e = a; e < b; e += WAVE) {                       // wave-uniform trip counts around the ballot
       const u64 j = e + lane;
       u32 cj = 0; bool keep = false;
       if (j < b) { cj = rows[j]; keep = cj != code; }
-      const u64 m = __ballot(keep);
-      const u64 p = p0 + __popcll(m & ((1ull << lane) - 1));
+      const u64 p = wave_place(keep, p0);
       if (keep && p < cap) keys[p] = tag | (K)cj;
-      p0 += __popcll(m);
     }
   }
 }
@@ -129,7 +102,6 @@ __global__ __launch_bounds__(256) void sg_emit_kernel(const K *__restrict__ keys
                                                       u32 *__restrict__ maxCount) {
   __shared__ u32 sMax[256 / WAVE];
   const u64 stride = (u64)gridDim.x * blockDim.x;
-  const u32 lane = threadIdx.x & (WAVE - 1);
   u32 mx = 0;
   for (u64 i0 = (u64)blockIdx.x * blockDim.x; i0 < n; i0 += stride) {
     const u64 i = i0 + threadIdx.x;
@@ -139,24 +111,16 @@ __global__ __launch_bounds__(256) void sg_emit_kernel(const K *__restrict__ keys
       mx = mx > c ? mx : c;
     }
   }
-  for (int k = 32; k; k >>= 1) { const u32 o = (u32)__shfl_xor((int)mx, k); mx = mx > o ? mx : o; }
-  if (lane == 0) sMax[threadIdx.x / WAVE] = mx;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    for (u32 w = 1; w < blockDim.x / WAVE; ++w) mx = mx > sMax[w] ? mx : sMax[w];
-    if (mx) atomicMax(maxCount, mx);
-  }
+  mx = wg_max(mx, sMax);
+  if (threadIdx.x == 0 && mx) atomicMax(maxCount, mx);
 }
 
 // rowCnt[q] += rows of the batch with slot q (oSlot ascends). A windowed block comes here once per window, one launch after the other
 __global__ void sg_rowcount_kernel(const u32 *__restrict__ oSlot, u64 runs, u32 nq, u32 *__restrict__ rowCnt) {
   const u32 q = blockIdx.x * blockDim.x + threadIdx.x;
   if (q >= nq) return;
-  u64 l = 0, r = runs;
-  while (l < r) { const u64 m = (l + r) >> 1; if (oSlot[m] < q) l = m + 1; else r = m; }
-  const u64 s = l; r = runs;
-  while (l < r) { const u64 m = (l + r) >> 1; if (oSlot[m] <= q) l = m + 1; else r = m; }
-  rowCnt[q] += (u32)(l - s);
+  const u64 s = lower_bound(oSlot, (u64)0, runs, q);
+  rowCnt[q] += (u32)(upper_bound(oSlot, s, runs, q) - s);
 }
 
 // ---------------------------------------------------------------------------------------------------------- driver
@@ -226,6 +190,7 @@ struct ShareGraph {
   // blocks [c0, c0 + nq) in the window [lo, hi); total = list entries gathered
   int batch(u32 c0, u32 nq, u32 lo, u32 hi, bool full, u64 total) {
     hipStream_t st = c->stream;
+    if (!full) { c->nbStats[3] += 1; ++windows; }             // one window of a block above the budget
     c->nbStats[2] += 1; ++batches;
     if (!total) return 0;
     if (total >= 0xFFFFFFFFull) return c->fail("shareGraph: %llu list entries in one batch, beyond 2^32 (block %u alone)", (u64)total, c0);
@@ -241,19 +206,9 @@ struct ShareGraph {
     if (n > total) return c->fail("shareGraph: %llu keys of %llu list entries", n, (u64)total);
     c->nbStats[0] += total; c->nbStats[1] += n; entries += total; nKeys += n;
     if (!n) return 0;
-    const int cbits = sgBits(c->nBlocks), endBit = cbits + sgBits(nq - 1);
+    const int cbits = keyBits(c->nBlocks), endBit = cbits + keyBits(nq - 1);
     if (endBit <= 32) return sortAndEmit<u32>(keys32, keys32s, c0, nq, lo, hi, full, cbits, endBit, units, n);
     return sortAndEmit<u64>(keys64, keys64s, c0, nq, lo, hi, full, cbits, endBit, units, n);
-  }
-
-  // one block above the budget: windows of barcode index, halved until their entries fit (a window of one index always runs)
-  int windowed(u32 code, u32 lo, u32 hi, u64 records) {
-    if (!records) return 0;
-    if (records <= budget || hi - lo <= 1) { c->nbStats[3] += 1; ++windows; return batch(code, 1, lo, hi, false, records); }
-    const u32 mid = lo + (hi - lo) / 2;
-    u64 left = 0; H10X_TRY(sizes(code, 1, lo, mid, false, &left));
-    H10X_TRY(windowed(code, lo, mid, left));
-    return windowed(code, mid, hi, records - left);
   }
 
   int run() {
@@ -269,13 +224,9 @@ struct ShareGraph {
     H10X_HIP(c, rowCnt.alloc((size_t)nB + 1)); H10X_HIP(c, hipMemsetAsync(rowCnt.p, 0, ((size_t)nB + 1) * 4, st));
     H10X_HIP(c, maxCount.alloc(1)); H10X_HIP(c, hipMemsetAsync(maxCount.p, 0, 4, st));
     H10X_HIP(c, hipStreamSynchronize(st));
-    for (u32 q0 = 0; q0 < nB;) {
-      if (size[q0] > budget) { H10X_TRY(windowed(codeMin + q0, 0, c->nBlocks, size[q0])); ++q0; continue; }
-      u32 q1 = q0; u64 sum = 0;
-      while (q1 < nB && size[q1] <= budget && sum + size[q1] <= budget) sum += size[q1++];
-      H10X_TRY(batch(codeMin + q0, q1 - q0, 0, c->nBlocks, true, sum));
-      q0 = q1;
-    }
+    H10X_TRY(cut_batches(size.data(), nB, c->nBlocks, budget,
+                         [&](u32 q, u32 lo, u32 hi, u64 *records) { return sizes(codeMin + q, 1, lo, hi, false, records); },
+                         [&](u32 q0, u32 n, u32 lo, u32 hi, bool full, u64 total) { return batch(codeMin + q0, n, lo, hi, full, total); }));
     H10X_HIP(c, c->sgOffsets.alloc((size_t)nB + 1));
     return prim_exclusive_scan_u32_u64(c, pt, rowCnt.p, c->sgOffsets.p, (size_t)nB + 1);
   }
@@ -289,10 +240,7 @@ void stageL_release(Ctx *c) {
 
 int stageL_run(Ctx *c, int64_t minShare, u32 codeMin, u32 codeMax, h10x_share_graph_info *info) {
   stageL_release(c);
-  if (!c->haveState) return c->fail("no hash state loaded: use readFQB or readHash first");
-  if (c->sharded) return c->fail("shareGraph: not available on a sharded context (one rank holds only its own barcodes)");
-  if (!c->haveGood) return c->fail("!! you must set hashDepthRange before shareGraph");      // (after --clusterSplit too: the lists are of the old blocks)
-  if (minShare < 1) return c->fail("!! shareGraph minShare %lld must be >= 1", (long long)minShare);
+  H10X_TRY(ce_check(c, "shareGraph", minShare));
   if (codeMax > c->nBlocks) return c->fail("!! shareGraph codeMax %u beyond nBlocks %u", codeMax, c->nBlocks);
   if (!codeMax) codeMax = c->nBlocks;                         // as --cluster 1 0
   if (codeMin > codeMax) codeMin = codeMax;                   // an empty graph

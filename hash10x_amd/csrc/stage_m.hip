@@ -2,68 +2,41 @@
 //
 // Every row entry (c, d) of the share graph (stage_l.hip) is an undirected edge {c, d}. The rows of a block range are born on the device and stay
 // there: a label per block, parent[nBlocks], lives in the context, and each range's rows are folded into it as soon as the census has made them.
-//   hook     one thread per row of the range (the source block by binary search in the range's offsets): lock-free union by smaller root. Find
-//            both roots; atomicMin the larger root's parent towards the smaller. If the word no longer held the larger root itself, another
-//            thread hooked it first: go on with (what it held, the smaller root). parent[x] <= x at all times, so a find strictly descends,
-//            and the larger end of a retry strictly descends: every loop is bounded by nBlocks, nothing waits for another wave.
+//   hook     one thread per row of the range (the source block by binary search in the range's offsets): lock-free union by smaller root
+//            (unionfind.hpp: every loop is bounded by nBlocks, nothing waits for another wave).
 //   check    the same rows: how many still have ends with different roots. While that is non-zero the hook runs again over the range (sets
 //            only merge: a satisfied range stays satisfied, whatever later ranges do). Bounded rounds; running out of them is an error.
 //   finish   root[c] by a find per block; the roots c >= 1 flagged, scanned, numbered in ascending order; comp[c] = number(root[c]) + 1; member
 //            counts and record sums by integer atomics (exact, order-free); the largest component and the singletons with one atomic per
-//            workgroup (sg_emit_kernel's form).
+//            workgroup.
 // parent[] is rewritten by other CUs and XCDs while hook runs, so inside these kernels every read of it is a relaxed agent-scope atomic load (it
 // bypasses the CU's L1, which no other CU's store refreshes) and every write an agent-scope atomic. Between kernels the launch boundary orders.
 #include "common.hpp"
 #include "prim.hpp"
+#include "unionfind.hpp"
+#include "wave.hpp"
 
 namespace h10x {
 
 static constexpr u32 SM_MAX_ROUNDS = 64;                     // hook rounds per range (one is the rule: the hook leaves nothing undone by itself)
 static constexpr unsigned SM_GRID = 2048;                    // workgroups of the kernels that end in one atomic each
 
-__device__ __forceinline__ u32 sm_load(const u32 *p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-
-// the root of x: at most nB steps down (parent[v] <= v; a value out of range would be a corrupted array: the walk stops at it).
-// On the way every visited word is lowered to its grandparent (atomicMin: stays inside the set, keeps parent[v] <= v).
-__device__ __forceinline__ u32 sm_find(u32 *parent, u32 x, u32 nB) {
-  for (u32 step = 0; step < nB; ++step) {
-    const u32 p = sm_load(parent + x);
-    if (p >= x) return x;
-    const u32 g = sm_load(parent + p);
-    if (g < p) __hip_atomic_fetch_min(parent + x, g, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    x = p;
-  }
-  return x;
-}
-
-// source block of row i: the last q with offsets[q] <= i (offsets[0] = 0, offsets[nq] = rows)
-__device__ __forceinline__ u32 sm_source(const u64 *__restrict__ offsets, u32 nq, u64 i) {
-  u32 l = 0, r = nq;
-  while (r - l > 1) { const u32 m = (l + r) >> 1; if (offsets[m] <= i) l = m; else r = m; }
-  return l;
-}
+typedef UfDevice<__HIP_MEMORY_SCOPE_AGENT> SmWords;          // parent[]: global memory, rewritten by every CU
 
 __global__ void sm_init_kernel(u32 *__restrict__ parent, u32 nB) {
   const u32 c = blockIdx.x * blockDim.x + threadIdx.x;
   if (c < nB) parent[c] = c;
 }
 
-// one thread per row: union of the row's block (c0 + its slot) and its entry. Block 0 holds no records and stands in no list; an entry outside
-// [1, nB) is skipped, never followed
+// one thread per row: union of the row's block (c0 + its slot: the last q with offsets[q] <= i; offsets[0] = 0, offsets[nq] = rows) and its
+// entry. Block 0 holds no records and stands in no list; an entry outside [1, nB) is skipped, never followed
 __global__ __launch_bounds__(256) void sm_hook_kernel(const u64 *__restrict__ offsets, const u32 *__restrict__ block, u64 rows, u32 c0, u32 nq,
                                                       u32 *parent, u32 nB) {
   const u64 stride = (u64)gridDim.x * blockDim.x;
   for (u64 i = (u64)blockIdx.x * blockDim.x + threadIdx.x; i < rows; i += stride) {
-    u32 a = c0 + sm_source(offsets, nq, i), b = block[i];
+    const u32 a = c0 + last_le(offsets, nq, i), b = block[i];
     if (!a || !b || a >= nB || b >= nB) continue;
-    for (u32 t = 0; t < nB; ++t) {                            // max(a, b) descends with every retry
-      a = sm_find(parent, a, nB); b = sm_find(parent, b, nB);
-      if (a == b) break;
-      const u32 hi = a > b ? a : b, lo = a > b ? b : a;
-      const u32 old = __hip_atomic_fetch_min(parent + hi, lo, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      if (old == hi) break;                                   // hi was a root, and hangs below lo now
-      a = old; b = lo;                                        // hi had been hooked to old < hi meanwhile: old and lo are still to be joined
-    }
+    uf_union<SmWords>(parent, a, b, nB);
   }
 }
 
@@ -72,22 +45,16 @@ __global__ __launch_bounds__(256) void sm_check_kernel(const u64 *__restrict__ o
                                                        u32 *parent, u32 nB, u32 *__restrict__ open) {
   __shared__ u32 sOpen[256 / WAVE];
   const u64 stride = (u64)gridDim.x * blockDim.x;
-  const u32 lane = threadIdx.x & (WAVE - 1);
   u32 n = 0;
   for (u64 i0 = (u64)blockIdx.x * blockDim.x; i0 < rows; i0 += stride) {
     const u64 i = i0 + threadIdx.x;
     if (i < rows) {
-      const u32 a = c0 + sm_source(offsets, nq, i), b = block[i];
-      if (a && b && a < nB && b < nB && sm_find(parent, a, nB) != sm_find(parent, b, nB)) ++n;
+      const u32 a = c0 + last_le(offsets, nq, i), b = block[i];
+      if (a && b && a < nB && b < nB && uf_find<SmWords>(parent, a, nB) != uf_find<SmWords>(parent, b, nB)) ++n;
     }
   }
-  for (int k = 32; k; k >>= 1) n += (u32)__shfl_xor((int)n, k);
-  if (lane == 0) sOpen[threadIdx.x / WAVE] = n;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    for (u32 w = 1; w < blockDim.x / WAVE; ++w) n += sOpen[w];
-    if (n) atomicAdd(open, n);
-  }
+  n = wg_sum(n, sOpen);
+  if (threadIdx.x == 0 && n) atomicAdd(open, n);
 }
 
 // root[c] for every block, and flag[c] = 1 for the roots c >= 1 (flag[nB] = 0: the scan's last entry is the number of components)
@@ -95,7 +62,7 @@ __global__ void sm_root_kernel(u32 *parent, u32 nB, u32 *__restrict__ root, u32 
   const u32 c = blockIdx.x * blockDim.x + threadIdx.x;
   if (c > nB) return;
   if (c == nB) { flag[c] = 0; return; }
-  const u32 r = sm_find(parent, c, nB);
+  const u32 r = uf_find<SmWords>(parent, c, nB);
   root[c] = r; flag[c] = (c >= 1 && r == c) ? 1u : 0u;
 }
 
@@ -122,9 +89,8 @@ __global__ __launch_bounds__(256) void sm_label_kernel(const u32 *__restrict__ r
     const u32 kl = (u32)__shfl((int)k, lead);
     const bool mine = k == kl;
     const u64 m = __ballot(mine);
-    unsigned long long sum = mine ? nh : 0;
-    for (int o = 32; o; o >>= 1) sum += __shfl_xor(sum, o);
-    if (lane == (u32)lead) { atomicAdd(nMember + kl, (u32)__popcll(m)); if (sum) atomicAdd(records + kl, sum); }
+    const u64 sum = wave_sum((u64)(mine ? nh : 0));
+    if (lane == (u32)lead) { atomicAdd(nMember + kl, (u32)__popcll(m)); if (sum) atomicAdd(records + kl, (unsigned long long)sum); }
     todo &= ~m;
   }
 }
@@ -139,6 +105,7 @@ __global__ __launch_bounds__(256) void sm_summary_kernel(const u32 *__restrict__
     const u32 m = nMember[k];
     mx = mx > m ? mx : m; one += m == 1;
   }
+  // two values through one butterfly and one barrier: wave.hpp's folds take one value each and would make two of both
   for (int k = 32; k; k >>= 1) { const u32 o = (u32)__shfl_xor((int)mx, k); mx = mx > o ? mx : o; one += (u32)__shfl_xor((int)one, k); }
   if (lane == 0) { sMax[threadIdx.x / WAVE] = mx; sOne[threadIdx.x / WAVE] = one; }
   __syncthreads();
@@ -157,10 +124,7 @@ void stageM_release(Ctx *c) {
 
 int stageM_begin(Ctx *c, int64_t minShare) {
   stageM_release(c);
-  if (!c->haveState) return c->fail("no hash state loaded: use readFQB or readHash first");
-  if (c->sharded) return c->fail("shareComponents: not available on a sharded context (one rank holds only its own barcodes)");
-  if (!c->haveGood) return c->fail("!! you must set hashDepthRange before shareComponents");   // (after --clusterSplit too: the lists are of the old blocks)
-  if (minShare < 1) return c->fail("!! shareComponents minShare %lld must be >= 1", (long long)minShare);
+  H10X_TRY(ce_check(c, "shareComponents", minShare));
   const u32 nB = c->nBlocks;
   H10X_HIP(c, c->scParent.alloc(nB));
   if (nB) sm_init_kernel<<<divUp(nB, 256), 256, 0, c->stream>>>(c->scParent.p, nB);

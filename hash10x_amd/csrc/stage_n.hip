@@ -8,20 +8,21 @@
 //            compact writes their indices back to back;
 //   groups   ONE WAVE per in-range hash, nothing in it waits for another wave. The list is deduped into LDS (D) with the labels beside it
 //            (lab[i] = i). For each member a the wave streams a's row in coalesced 64-wide steps; each entry is looked up in D by binary search
-//            in LDS; a hit is an edge and is hooked with sm_hook_kernel's union by smaller label, on LDS words: find both roots, atomicMin
-//            the larger root's label towards the smaller, and if the word no longer held the larger root, go on with (what it held, the
-//            smaller root). lab[i] <= i always, so every loop is bounded by m. After a pass the labels are flattened and the roots counted:
+//            in LDS; a hit is an edge and is hooked with the union by smaller label of unionfind.hpp, on LDS words (lab[i] <= i always,
+//            so every loop is bounded by m). After a pass the labels are flattened and the roots counted:
 //            the passes end when a pass hooked nothing or one root is left (sets only merge); running out of m passes is an error word.
 //            Then the members per root are counted in LDS (D's words, no longer wanted), groups / largest / second reduced across the
 //            wave, and the 8 bytes written by one store.
 //   tally    per crib type the in-range hashes, those in one group, those with second >= 2, and the deepest list: one atomic per workgroup
-//            and counter (sg_emit_kernel's form).
+//            and counter.
 // This reads 4 B per list entry and 4 B per row entry of every member, contiguously. The other form, a look-up of each of the m^2 pairs in
 // the rows in global memory, would make m^2 log2(row) dependent 4-byte reads per hash and was not built.
 // The lanes of a wave run in lockstep and its LDS operations complete in order, so inside a wave a fence for the compiler is all the
 // synchronisation there is; labels that other lanes rewrite are read with atomic loads.
 #include "common.hpp"
 #include "prim.hpp"
+#include "unionfind.hpp"
+#include "wave.hpp"
 
 namespace h10x {
 
@@ -33,53 +34,21 @@ __device__ __forceinline__ void hc_sync() {
   __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront"); __builtin_amdgcn_wave_barrier(); __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
 __device__ __forceinline__ u32 hc_load(const u32 *p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT); }
-
-// the root of i: at most m steps down (lab[v] <= v); every visited word is lowered to its grandparent on the way
-__device__ __forceinline__ u32 hc_find(u32 *lab, u32 i, u32 m) {
-  for (u32 step = 0; step < m; ++step) {
-    const u32 p = hc_load(lab + i);
-    if (p >= i) return i;
-    const u32 g = hc_load(lab + p);
-    if (g < p) atomicMin(lab + i, g);
-    i = p;
-  }
-  return i;
-}
-
-// union of the sets of a and b (indices into D); true if their roots differed. max(a, b) descends with every retry
-__device__ __forceinline__ bool hc_union(u32 *lab, u32 a, u32 b, u32 m) {
-  bool did = false;
-  for (u32 t = 0; t < m; ++t) {
-    a = hc_find(lab, a, m); b = hc_find(lab, b, m);
-    if (a == b) break;
-    did = true;
-    const u32 hi = a > b ? a : b, lo = a > b ? b : a;
-    const u32 old = atomicMin(lab + hi, lo);
-    if (old == hi) break;                                     // hi was a root, and hangs below lo now
-    a = old; b = lo;                                          // hi had been hooked to old < hi meanwhile: old and lo are still to be joined
-  }
-  return did;
-}
+typedef UfDevice<__HIP_MEMORY_SCOPE_WAVEFRONT> HcWords;      // lab[]: LDS words of one wave (indices into D)
 
 // flag[x] = 1 for the in-range hashes x >= 1 (flag[U1] = 0: the scan's last entry is their number); *deepest = the longest of their lists
 __global__ __launch_bounds__(256) void hc_flag_kernel(const u8 *__restrict__ within, const u32 *__restrict__ hashDepth, u32 U1, u32 *__restrict__ flag,
                                                       u32 *__restrict__ deepest) {
   __shared__ u32 sMax[256 / WAVE];
   const u64 stride = (u64)gridDim.x * blockDim.x;
-  const u32 lane = threadIdx.x & (WAVE - 1);
   u32 mx = 0;
   for (u64 x = (u64)blockIdx.x * blockDim.x + threadIdx.x; x <= U1; x += stride) {
     u32 f = 0;
     if (x >= 1 && x < U1 && within[x]) { f = 1; const u32 d = hashDepth[x]; mx = mx > d ? mx : d; }
     flag[x] = f;
   }
-  for (int k = 32; k; k >>= 1) { const u32 o = (u32)__shfl_xor((int)mx, k); mx = mx > o ? mx : o; }
-  if (lane == 0) sMax[threadIdx.x / WAVE] = mx;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    for (u32 w = 1; w < blockDim.x / WAVE; ++w) mx = mx > sMax[w] ? mx : sMax[w];
-    if (mx) atomicMax(deepest, mx);
-  }
+  mx = wg_max(mx, sMax);
+  if (threadIdx.x == 0 && mx) atomicMax(deepest, mx);
 }
 
 __global__ void hc_compact_kernel(const u32 *__restrict__ flag, const u32 *__restrict__ pos, u32 U1, u32 nx, u32 *__restrict__ xs) {
@@ -95,7 +64,6 @@ __global__ __launch_bounds__(256) void hc_groups_kernel(const u32 *__restrict__ 
   extern __shared__ u32 hcLds[];
   const u32 lane = threadIdx.x & (WAVE - 1), wave = threadIdx.x / WAVE, wpw = blockDim.x / WAVE;
   u32 *D = hcLds + (size_t)wave * 2 * cap, *lab = D + cap;
-  const u64 below = (1ull << lane) - 1;
   for (u64 w = (u64)blockIdx.x * wpw + wave; w < nx; w += (u64)gridDim.x * wpw) {   // wave-uniform throughout
     const u32 x = xs[w];
     const u32 depth = hashDepth[x], len = depth < cap ? depth : cap;                // (depth <= cap: the driver sized cap from the deepest list)
@@ -105,10 +73,8 @@ __global__ __launch_bounds__(256) void hc_groups_kernel(const u32 *__restrict__ 
       const u32 j = j0 + lane;
       u32 v = 0; bool keep = false;
       if (j < len) { v = rows[rs + j]; keep = j == 0 || rows[rs + j - 1] != v; }
-      const u64 mask = __ballot(keep);
-      const u32 p = m + (u32)__popcll(mask & below);
+      const u32 p = wave_place(keep, m);
       if (keep) { D[p] = v; lab[p] = p; }                     // p < len <= cap
-      m += (u32)__popcll(mask);
     }
     hc_sync();
     if (m > 1) {
@@ -123,9 +89,8 @@ __global__ __launch_bounds__(256) void hc_groups_kernel(const u32 *__restrict__ 
             const u64 j = r + lane;
             if (j < r1) {
               const u32 b = block[j];
-              u32 l = 0, h = m;                               // first index with D[index] >= b
-              while (l < h) { const u32 mid = (l + h) >> 1; if (D[mid] < b) l = mid + 1; else h = mid; }
-              if (l < m && l != ia && D[l] == b) changed |= hc_union(lab, ia, l, m);
+              const u32 l = lower_bound(D, 0u, m, b);
+              if (l < m && l != ia && D[l] == b) changed |= uf_union<HcWords>(lab, ia, l, m);
             }
           }
         }
@@ -134,7 +99,7 @@ __global__ __launch_bounds__(256) void hc_groups_kernel(const u32 *__restrict__ 
         for (u32 i0 = 0; i0 < m; i0 += WAVE) {                // flatten, count the roots
           const u32 i = i0 + lane;
           bool isRoot = false;
-          if (i < m) { const u32 r = hc_find(lab, i, m); isRoot = r == i; if (!isRoot) atomicMin(lab + i, r); }
+          if (i < m) { const u32 r = uf_find<HcWords>(lab, i, m); isRoot = r == i; if (!isRoot) atomicMin(lab + i, r); }
           roots += (u32)__popcll(__ballot(isRoot));
         }
         hc_sync();
@@ -187,7 +152,7 @@ __global__ __launch_bounds__(256) void hc_tally_kernel(const u32 *__restrict__ x
       n[3 * k] += (u32)__popcll(__ballot(t == k)); n[3 * k + 1] += (u32)__popcll(__ballot(t == k && one)); n[3 * k + 2] += (u32)__popcll(__ballot(t == k && split));
     }
   }
-  for (int k = 32; k; k >>= 1) { const u32 o = (u32)__shfl_xor((int)mx, k); mx = mx > o ? mx : o; }
+  mx = wave_max(mx);
   if (lane == 0) {
 #pragma unroll
     for (int k = 0; k < 15; ++k) sCnt[wave][k] = n[k];
@@ -209,11 +174,8 @@ void stageN_release(Ctx *c) {
 }
 
 int stageN_run(Ctx *c, int64_t minShare, h10x_hash_copies_info *info) {
-  stageN_release(c); stageM_release(c); stageL_release(c);    // the census below uses the share graph's arrays
-  if (!c->haveState) return c->fail("no hash state loaded: use readFQB or readHash first");
-  if (c->sharded) return c->fail("hashCopies: not available on a sharded context (one rank holds only its own barcodes)");
-  if (!c->haveGood) return c->fail("!! you must set hashDepthRange before hashCopies");   // (after --clusterSplit too: the lists are of the old blocks)
-  if (minShare < 1) return c->fail("!! hashCopies minShare %lld must be >= 1", (long long)minShare);
+  release_share_results(c);                                   // the census below uses the share graph's arrays
+  H10X_TRY(ce_check(c, "hashCopies", minShare));
   hipStream_t st = c->stream;
   const u32 U1 = c->hashNumber;
   PrimTemp pt; DevBuf<u32> flag, pos, small;

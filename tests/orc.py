@@ -520,3 +520,61 @@ def slice_digest(h, step=1 << 25):
     table(3, 0, z["nBlocks"], zero_ptr=True); put(bytes(32 * (blocks_dim - z["nBlocks"])))
     table(4, 0, z["nClusHash"])
     return sha.hexdigest(), size
+
+
+# ---------------------------------------------------------------- shared by the census tests (neighbours, codeExplore, shareGraph, shareComponents, hashCopies)
+GEN_MOLECULES = (8000, 30, 600000, 0.003, 7, 4.0, 150, 5000)   # gen_fqb's arguments for the generated set of the shareComponents and hashCopies tests
+
+
+def hx():
+    import hash10x_amd
+    return hash10x_amd
+
+
+def set_budget(h, n):
+    """h10x_set_option(ctx, "neighbour_budget", n) on the live context"""
+    assert h._hip.h10x_set_option(h._ctx(), b"neighbour_budget", n) == 0
+
+
+def molecules(recs, crib=None):
+    """the generated set clustered and split: one block per molecule (crib: the haplotype files' stem, for --cribBuild)"""
+    h = hx().Hash10x(B=21)
+    h.read_fqb(recs)
+    if crib:
+        h.crib_build(crib + ".A.fa", crib + ".B.fa")
+    h.depth_range(2, 40)
+    h.cluster(1, 0, 3)
+    h.cluster_split()
+    return h
+
+
+def hash_image(blocks, B=20):
+    """the bytes of a .hash file, version 2 (hash10x.c:244-267): blocks[i] = the hash indices of the records of block i + 1 (may be empty);
+    the depth of a hash index is the number of records that hold it"""
+    blocks = [np.asarray(b, dtype=np.int64) for b in blocks]
+    n_blocks, n_index = len(blocks) + 1, int(max(b.max() for b in blocks if len(b))) + 1
+    depth = np.bincount(np.concatenate(blocks), minlength=n_index).astype("<u4")
+    table = np.zeros(n_blocks, dtype=BLOCK)
+    records = []
+    for i, b in enumerate(blocks, start=1):
+        table[i] = (1, len(b), 0, 0, 0, 0.0)
+        rec = np.zeros(len(b), dtype=CLUSHASH)
+        rec["hash"] = b
+        records.append(rec.tobytes())
+
+    def array_header(n, size):
+        return np.array([(8918274, 0, 0, n, size, n, 0)], dtype="<i4,<i4,<u8,<i4,<i4,<i4,<i4").tobytes()
+
+    u16, u32 = (lambda v: int(v).to_bytes(2, "little")), (lambda v: int(v).to_bytes(4, "little"))
+    head = b"10XH" + u32(2) + u16(8) + u16(32) + u32(B) + bytes(4 << B) + u32(n_index) + (np.arange(n_index, dtype="<u8") * 31).tobytes()
+    return b"".join([head, array_header(n_index, 4), depth.tobytes(), array_header(n_blocks, 32), table.tobytes()] + records)
+
+
+def load_image(tmp_path, blocks, lo=2, hi=100):
+    p = tmp_path / "state.hash"
+    p.write_bytes(hash_image(blocks))
+    h = hx().Hash10x(B=20)
+    h.read_hash(str(p))
+    h.depth_range(lo, hi)                                      # a hash counts when lo .. hi - 1 records hold it
+    assert h.export_blocks()["nHash"].tolist() == [0] + [len(b) for b in blocks]
+    return h

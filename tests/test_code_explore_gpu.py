@@ -14,9 +14,7 @@ pytestmark = pytest.mark.gpu
 EXE = os.path.join(orc.REPO, "bin", "hash10x-amd")
 
 
-def _hx():
-    import hash10x_amd
-    return hash10x_amd
+_hx, _budget = orc.hx, orc.set_budget
 
 
 # ------------------------------------------------------------------------------------ NumPy restatement
@@ -144,10 +142,6 @@ def explore(st, code, thr):
 
 
 # ------------------------------------------------------------------------------------ the census
-def _budget(h, n):
-    assert h._hip.h10x_set_option(h._ctx(), b"neighbour_budget", n) == 0
-
-
 def _check_share(h, st, codes):
     got = h.code_share(codes)
     for code, r in zip(codes, got):

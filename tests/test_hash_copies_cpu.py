@@ -13,7 +13,7 @@ import orc
 
 EXE = os.path.join(orc.REPO, "bin", "hash10x-amd")
 TOP = 2 ** 31 - 1
-GEN = (8000, 30, 600000, 0.003, 7, 4.0, 150, 5000)             # the generated set of test_share_components_cpu.py
+GEN = orc.GEN_MOLECULES                                         # the generated set of test_share_components_cpu.py
 
 
 def test_model_by_hand():

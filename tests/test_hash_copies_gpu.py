@@ -15,16 +15,9 @@ pytestmark = pytest.mark.gpu
 
 EXE = os.path.join(orc.REPO, "bin", "hash10x-amd")
 TOP = 2 ** 31 - 1
-GEN = (8000, 30, 600000, 0.003, 7, 4.0, 150, 5000)             # the generated set of test_share_components_cpu.py
 
 
-def _hx():
-    import hash10x_amd
-    return hash10x_amd
-
-
-def _budget(h, n):
-    assert h._hip.h10x_set_option(h._ctx(), b"neighbour_budget", n) == 0
+_hx, _budget, _molecules, _load_image, GEN = orc.hx, orc.set_budget, orc.molecules, orc.load_image, orc.GEN_MOLECULES
 
 
 def _same(got, exp, what):
@@ -53,17 +46,6 @@ def _check_info(h, cm, table, t):
 def gen_recs(tmp_path_factory):
     d = str(tmp_path_factory.mktemp("hc"))
     return d, orc.gen_fqb(os.path.join(d, "x.fqb"), *GEN, fa=os.path.join(d, "x"))   # (the two haplotypes beside it, for --cribBuild)
-
-
-def _molecules(recs, crib=None):
-    h = _hx().Hash10x(B=21)
-    h.read_fqb(recs)
-    if crib:
-        h.crib_build(crib + ".A.fa", crib + ".B.fa")
-    h.depth_range(2, 40)
-    h.cluster(1, 0, 3)
-    h.cluster_split()
-    return h
 
 
 @pytest.fixture(scope="module")
@@ -115,38 +97,6 @@ def test_unsplit_small():
 
 
 # ------------------------------------------------------------------------------------ hand-made states
-def _hash_image(blocks, B=20):
-    """the bytes of a .hash file, version 2 (hash10x.c:244-267): blocks[i] = the hash indices of the records of block i + 1 (may be empty);
-    the depth of a hash index is the number of records that hold it"""
-    blocks = [np.asarray(b, dtype=np.int64) for b in blocks]
-    n_blocks, n_index = len(blocks) + 1, int(max(b.max() for b in blocks if len(b))) + 1
-    depth = np.bincount(np.concatenate(blocks), minlength=n_index).astype("<u4")
-    table = np.zeros(n_blocks, dtype=orc.BLOCK)
-    records = []
-    for i, b in enumerate(blocks, start=1):
-        table[i] = (1, len(b), 0, 0, 0, 0.0)
-        rec = np.zeros(len(b), dtype=orc.CLUSHASH)
-        rec["hash"] = b
-        records.append(rec.tobytes())
-
-    def array_header(n, size):
-        return np.array([(8918274, 0, 0, n, size, n, 0)], dtype="<i4,<i4,<u8,<i4,<i4,<i4,<i4").tobytes()
-
-    u16, u32 = (lambda v: int(v).to_bytes(2, "little")), (lambda v: int(v).to_bytes(4, "little"))
-    head = b"10XH" + u32(2) + u16(8) + u16(32) + u32(B) + bytes(4 << B) + u32(n_index) + (np.arange(n_index, dtype="<u8") * 31).tobytes()
-    return b"".join([head, array_header(n_index, 4), depth.tobytes(), array_header(n_blocks, 32), table.tobytes()] + records)
-
-
-def _load_image(tmp_path, blocks, lo=2, hi=100):
-    p = tmp_path / "state.hash"
-    p.write_bytes(_hash_image(blocks))
-    h = _hx().Hash10x(B=20)
-    h.read_hash(str(p))
-    h.depth_range(lo, hi)                                      # a hash counts when lo .. hi - 1 records hold it
-    assert h.export_blocks()["nHash"].tolist() == [0] + [len(b) for b in blocks]
-    return h
-
-
 def _model_of(blocks, lo=2, hi=100):
     hashes = np.concatenate([np.asarray(b, dtype=np.int64) for b in blocks])
     depth = np.bincount(hashes)
@@ -387,7 +337,7 @@ def test_cli_depth_cap(tmp_path):
     """the depth cap from the command line: the message on the output, no file, exit status 0; the state read anew (ranges add up) with the
     range cut below the deep hash runs"""
     blocks = [[1, 2], [1, 2]] + [[1]] * 4095
-    (tmp_path / "deep.hash").write_bytes(_hash_image(blocks))
+    (tmp_path / "deep.hash").write_bytes(orc.hash_image(blocks))
     p = subprocess.run([EXE, "-B", "20", "--readHash", "deep.hash", "--hashDepthRange", "2", "5000", "--hashCopies", "1", "deep.hc",
                         "--readHash", "deep.hash", "--hashDepthRange", "2", "4097", "--hashCopies", "1", "cut.hc"], cwd=tmp_path, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=300)
     assert p.returncode == 0, p.stderr.decode()

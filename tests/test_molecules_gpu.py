@@ -98,7 +98,8 @@ def test_golden_through_read_hash(workdir, name, fqb):
 # ------------------------------------------------------------------------------------------ 3: hand-built states
 def hash_bytes(blocks, B=20):
     """a .hash v2 image (hash10x.c:244-267) from [(nRead, nSubCluster, clusterParent, [(read, subCluster), ...]), ...] for blocks 1 ..:
-    the record at position p of a block holds hash index p + 1, so hashDepth[h] = the blocks with at least h records"""
+    the record at position p of a block holds hash index p + 1, so hashDepth[h] = the blocks with at least h records.
+    (Not orc.hash_image: that one takes the hash indices of each block; this one sets each record's read and label and the block's header fields.)"""
     n_blocks = len(blocks) + 1
     longest = max([len(b[3]) for b in blocks] + [0])
     hash_number = longest + 1

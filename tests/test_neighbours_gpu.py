@@ -14,9 +14,7 @@ pytestmark = pytest.mark.gpu
 EXE = os.path.join(orc.REPO, "bin", "hash10x-amd")
 
 
-def _hx():
-    import hash10x_amd
-    return hash10x_amd
+_hx, _budget = orc.hx, orc.set_budget
 
 
 # ------------------------------------------------------------------------------------ NumPy restatement of the census
@@ -71,11 +69,6 @@ def _check(h, cs, qs):
         assert int(mk[i]) == exp, "max of %d" % x
         eh_hist = np.bincount(ec, minlength=int(cs.depth[x]) + 1) if len(ec) else np.zeros(int(cs.depth[x]) + 1, np.int64)
         assert np.array_equal(hists[i], eh_hist), "histogram of %d" % x
-
-
-def _budget(h, n):
-    """h10x_set_option(ctx, "neighbour_budget", n) on the live context"""
-    assert h._hip.h10x_set_option(h._ctx(), b"neighbour_budget", n) == 0
 
 
 def _both_budgets(h, cs, qs):

@@ -57,7 +57,7 @@ def test_model_on_generated_set_through_reference(tmp_path):
     if not orc.have_ref():
         pytest.fail("reference binary missing: build() makes oracle/_ref")
     d = str(tmp_path)
-    orc.gen_fqb(os.path.join(d, "x.fqb"), 8000, 30, 600000, 0.003, 7, 4.0, 150, 5000)
+    orc.gen_fqb(os.path.join(d, "x.fqb"), *orc.GEN_MOLECULES)
     r = orc.run_ref(["-B", 21, "-ct", 3, "--readFQB", "x.fqb", "--hashDepthRange", 2, 40, "--cluster", 1, 0, "--clusterSplit", "--writeHash", "x.hash"], d)
     assert r.returncode == 0, r.stderr[-400:]
     hf = orc.HashFile(open(os.path.join(d, "x.hash"), "rb").read())

@@ -18,13 +18,7 @@ NAMES = ("comp", "root", "rootOf", "blocks", "records")
 TOP = 2 ** 31 - 1
 
 
-def _hx():
-    import hash10x_amd
-    return hash10x_amd
-
-
-def _budget(h, n):
-    assert h._hip.h10x_set_option(h._ctx(), b"neighbour_budget", n) == 0
+_hx, _budget, _molecules, _load_image, GEN = orc.hx, orc.set_budget, orc.molecules, orc.load_image, orc.GEN_MOLECULES
 
 
 def _same(got, exp, what):
@@ -50,22 +44,10 @@ def _check_info(h, res, rows, t):
 
 
 # ------------------------------------------------------------------------------------ the inputs, loaded once, with their models
-GEN = (8000, 30, 600000, 0.003, 7, 4.0, 150, 5000)
-
-
 @pytest.fixture(scope="module")
 def gen_recs(tmp_path_factory):
     d = str(tmp_path_factory.mktemp("sc"))
     return d, orc.gen_fqb(os.path.join(d, "x.fqb"), *GEN)
-
-
-def _molecules(recs):
-    h = _hx().Hash10x(B=21)
-    h.read_fqb(recs)
-    h.depth_range(2, 40)
-    h.cluster(1, 0, 3)
-    h.cluster_split()
-    return h
 
 
 @pytest.fixture(scope="module")
@@ -138,38 +120,6 @@ def test_unsplit_small(small):
 
 
 # ------------------------------------------------------------------------------------ hand-made states
-def _hash_image(blocks, B=20):
-    """the bytes of a .hash file, version 2 (hash10x.c:244-267): blocks[i] = the hash indices of the records of block i + 1 (may be empty);
-    the depth of a hash index is the number of records that hold it"""
-    blocks = [np.asarray(b, dtype=np.int64) for b in blocks]
-    n_blocks, n_index = len(blocks) + 1, int(max(b.max() for b in blocks if len(b))) + 1
-    depth = np.bincount(np.concatenate(blocks), minlength=n_index).astype("<u4")
-    table = np.zeros(n_blocks, dtype=orc.BLOCK)
-    records = []
-    for i, b in enumerate(blocks, start=1):
-        table[i] = (1, len(b), 0, 0, 0, 0.0)
-        rec = np.zeros(len(b), dtype=orc.CLUSHASH)
-        rec["hash"] = b
-        records.append(rec.tobytes())
-
-    def array_header(n, size):
-        return np.array([(8918274, 0, 0, n, size, n, 0)], dtype="<i4,<i4,<u8,<i4,<i4,<i4,<i4").tobytes()
-
-    u16, u32 = (lambda v: int(v).to_bytes(2, "little")), (lambda v: int(v).to_bytes(4, "little"))
-    head = b"10XH" + u32(2) + u16(8) + u16(32) + u32(B) + bytes(4 << B) + u32(n_index) + (np.arange(n_index, dtype="<u8") * 31).tobytes()
-    return b"".join([head, array_header(n_index, 4), depth.tobytes(), array_header(n_blocks, 32), table.tobytes()] + records)
-
-
-def _load_image(tmp_path, blocks):
-    p = tmp_path / "state.hash"
-    p.write_bytes(_hash_image(blocks))
-    h = _hx().Hash10x(B=20)
-    h.read_hash(str(p))
-    h.depth_range(2, 100)                                      # a hash counts when 2 .. 99 records hold it
-    assert h.export_blocks()["nHash"].tolist() == [0] + [len(b) for b in blocks]
-    return h
-
-
 def test_chain(tmp_path):
     """300 blocks in a chain; link i - (i + 1) is two private hashes for even i, one for odd i. Block numbers are a fixed permutation of the
     chain positions: neighbours lie in different ranges, and the smaller root is often the far end. At 4 blocks a range, components meet

@@ -17,13 +17,7 @@ EXE = os.path.join(orc.REPO, "bin", "hash10x-amd")
 THRESHOLDS = (1, 50, 200, 2 ** 31 - 1)
 
 
-def _hx():
-    import hash10x_amd
-    return hash10x_amd
-
-
-def _budget(h, n):
-    assert h._hip.h10x_set_option(h._ctx(), b"neighbour_budget", n) == 0
+_hx, _budget = orc.hx, orc.set_budget
 
 
 def _same(got, exp, what):
@@ -143,28 +137,6 @@ def test_after_cluster_split(generated):
 
 
 # ------------------------------------------------------------------------------------ a hand-made state
-def _state_bytes(blocks, B=20):
-    """a .hash v2 image (hash10x.c:244-267) from the hash indices of blocks 1 ..; hashDepth[x] = the records of x"""
-    n_blocks = len(blocks) + 1
-    hash_number = max(int(np.max(b)) for b in blocks if len(b)) + 1
-    depth = np.zeros(hash_number, dtype="<u4")
-    blk = np.zeros(n_blocks, dtype=orc.BLOCK)
-    parts = []
-    for i, hs in enumerate(blocks, start=1):
-        hs = np.asarray(hs, dtype=np.int64)
-        blk[i] = (1, len(hs), 0, 0, 0, 0.0)
-        ch = np.zeros(len(hs), dtype=orc.CLUSHASH)
-        ch["hash"] = hs
-        np.add.at(depth, hs, 1)
-        parts.append(ch.tobytes())
-    hdr = np.zeros(1, dtype="<i4,<i4,<u8,<i4,<i4,<i4,<i4")
-    out = [b"10XH", (2).to_bytes(4, "little"), (8).to_bytes(2, "little"), (32).to_bytes(2, "little"), B.to_bytes(4, "little"),
-           bytes(4 << B), hash_number.to_bytes(4, "little"), (np.arange(hash_number, dtype="<u8") * 31).tobytes()]
-    hdr[0] = (8918274, 0, 0, hash_number, 4, hash_number, 0); out += [hdr.tobytes(), depth.tobytes()]
-    hdr[0] = (8918274, 0, 0, n_blocks, 32, n_blocks, 0); out += [hdr.tobytes(), blk.tobytes()]
-    return b"".join(out + parts)
-
-
 def test_hand_made_state(tmp_path):
     """Block 1 holds hash 1 twice: its lists are walked twice, and every list holds block 1 twice. Block 3 has 65540 records: no good
     hashes of its own (hash10x.c:748), so its row is empty, yet it stands in the rows of blocks 1 and 2. Hashes 1 and 2 have 4 records
@@ -172,7 +144,7 @@ def test_hand_made_state(tmp_path):
     filler = np.arange(10, 10 + 65538)
     blocks = [[1, 1, 2, 3], [1, 2, 2, 4], np.concatenate([[1, 2], filler])]
     p = tmp_path / "state.hash"
-    p.write_bytes(_state_bytes(blocks))
+    p.write_bytes(orc.hash_image(blocks))
     h = _hx().Hash10x(B=20)
     h.read_hash(str(p))
     h.depth_range(2, 100)
