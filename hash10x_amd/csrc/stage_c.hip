@@ -369,17 +369,22 @@ __device__ __forceinline__ void min_u16(u16 *arr, u32 idx, u32 val) {
 // Dense and ranked placements in LDS come in two widths, chosen per block: a u32 per entry where the block's working set
 // leaves the room (minimum = one fire-and-forget ds_min_u32, no loop), the u16 of the CAS-min otherwise. The list loop is
 // bound by scalar and branch instructions (0.8 per CU cycle), and the CAS loop is mostly those.
-template <bool FIRST_LDS> struct FirstDense {
+// The dense width is a template parameter: a block runs in the instantiation of cluster_one_block of its width (dense_first_wide), so
+// neither form carries the other's update behind a run-time test.
+template <bool FIRST_LDS, bool WIDE = false> struct FirstDense {
+  static_assert(FIRST_LDS || !WIDE, "4-byte entries: LDS only");
   static constexpr bool MASK_TAIL = false;
   static constexpr bool SELF = true;                          // a lane without an entry (and the barcode's own number) keeps the barcode's own slot as its handle: first[] of the barcode
                                                              // itself is never written and reads "unseen", so the read-back needs no test and no exec mask
+  static constexpr bool SHORT_ROUNDS = WIDE;                 // the list loop takes rounds of one-chunk lists straight through (short_round): built on the one-instruction update
+  static constexpr u32 wide = WIDE ? 1u : 0u;                // 1 = 4-byte entries (their low half, at the same address, is the value)
   u32 none;                                                  // (the barcode's own number: set per barcode)
-  u16 *first; u32 wide;                                      // wide: 1 = 4-byte entries (their low half, at the same address, is the value), else 0
-  __device__ __forceinline__ u32 update(u32 cj, u32 i) const {
-    if (FIRST_LDS && wide) atomicMin(&((u32 *)first)[cj], i); else min_u16<FIRST_LDS>(first, cj, i);
+  u16 *first;
+  __device__ __forceinline__ u32 update(u32 cj, u32 i) const {   // (not for the barcode's own number, nor for a lane without an entry, which holds it)
+    if (WIDE) atomicMin(&((u32 *)first)[cj], i); else min_u16<FIRST_LDS>(first, cj, i);
     return cj;
   }
-  __device__ __forceinline__ u32 peek(u32 h) const {         // one read for both widths, no branch
+  __device__ __forceinline__ u32 peek(u32 h) const {
     if (FIRST_LDS) return *(const u16 *)((const unsigned char *)first + (u32)(h << (1 + wide)));
     return ld_shared<FIRST_LDS>(&first[h]);
   }
@@ -388,6 +393,7 @@ template <bool FIRST_LDS> struct FirstDense {
 };
 struct FirstRanked {
   static constexpr bool SELF = false;
+  static constexpr bool SHORT_ROUNDS = false;
   static constexpr bool MASK_TAIL = false;
   u16 *first; const u32 *bm; const u16 *pre; u32 wide;
   u32 none;                                                  // handle of a lane without an entry: one slot behind the last barcode present, always unseen
@@ -716,8 +722,83 @@ template <int CL_THREADS> __device__ __forceinline__ void fill16(void *p, size_t
   const uint4 v4 = make_uint4(v, v, v, v);
   for (u32 i = threadIdx.x; i < (u32)(bytes / 16); i += CL_THREADS) ((uint4 *)p)[i] = v4;
 }
+// v_writelane_b32: v with lane l, a constant, replaced by the wave-uniform s. Where clang has no builtin for it (ROCm 7.2.0, AMD clang 22.0.0git: none) the declaration is
+// bound to the intrinsic by its mangled name, llvm.amdgcn.writelane.i32 as of that LLVM (checked there: one v_writelane_b32, hazards padded by the compiler); a compiler
+// that names the intrinsic otherwise fails the build of this file at link time of the device code, it does not miscompile.
+#if __has_builtin(__builtin_amdgcn_writelane)
+__device__ __forceinline__ int writelane_u32(int s, int l, int v) { return __builtin_amdgcn_writelane(s, l, v); }
+#else
+extern "C" __device__ int writelane_u32(int s, int l, int v) __asm("llvm.amdgcn.writelane.i32");
+#endif
+// The part behind the barrier of a straight-line round of the dense list loop (cluster_one_block): msBest / msMax / msTot and the pointToMin counts of RIF lists of at
+// most one chunk each, as row_mode_hist<true, 1> forms them, but for the lists together and without a test of any list's length or activity — the loop is bound by its
+// scalar and branch instructions (8 more scalar ones per list: + 7.7 % on the launch, 8 more vector ones: + 2.6 %; HISTORY §11):
+//  * the RIF read-backs are issued together, then the RIF counting passes, then the RIF DPP maximum chains side by side, step by step (a chain by itself leaves the
+//    hazard slots of its steps empty);
+//  * what a list yields stays out of the scalar unit: its key, msTot and count go into lane 32 + t of a register each (the lane that holds the list's length in the
+//    descriptor register dv). Those lanes take the fields apart, look root[msBest] up and put the result words together for all the lists at once, and store root[] and
+//    the words with one ds_write_b16 and one global_store_dwordx2 per round;
+//  * a list of length 0 reads "unseen" in every lane, which is below no rank (ib), and lane 32 + t holds its length: 0, not stored.
+// A list does not see the root an earlier list of the same round has just found (they are stored together): it reads NONE16 and is settled behind the loop, like the
+// ranks whose msBest lies in another wave's part of the round — the settle phase gives the same counts.
+template <int RIF, typename FT>
+__device__ __forceinline__ void short_round(const FT &ft, const u32 (&h)[RIF] /* handles of the lists' entries */, u32 dv, u32 i0, u32 *hist, u16 *root, u64 *res, u32 thr) {
+  const u32 lane = threadIdx.x & (WAVE - 1);
+  // ranks are compared as 16-bit numbers: i0 is a multiple of RIF and a real rank is below NONE16, so the cap changes no real list's rank, and a rank past the
+  // last one stays <= NONE16 — no first[] value is below it where every lane reads NONE16
+  constexpr u32 I0_CAP = (u32)NONE16 & ~(u32)(RIF - 1);
+  const u32 ib = i0 < I0_CAP ? i0 : I0_CAP;
+  u32 f[RIF], c[RIF], key[RIF];
+  u32 totV = 0, keyV = 0, qV = 0;
+#pragma unroll
+  for (int t = 0; t < RIF; ++t) f[t] = ft.peek(h[t]);
+#pragma unroll
+  for (int t = 0; t < RIF; ++t) {                            // counted and cleared in one exec region (ds ops of a wave stay in order), the returns of the RIF lists in flight together
+    const bool ok = f[t] < ib + t;
+    totV = (u32)writelane_u32((int)__popcll(__builtin_amdgcn_ballot_w64(ok)), 32 + t, (int)totV);
+    c[t] = 0xFFFFFFFFu;                                      // a lane that does not count: arrival count 0 below (all ones + 1 in every byte position), a key under every real one
+    if (ok) { c[t] = atomicAdd(&hist[f[t] >> 2], 1u << ((f[t] & 3) * 8)); hist[f[t] >> 2] = 0; }
+  }
+#pragma unroll
+  for (int t = 0; t < RIF; ++t) key[t] = ((((c[t] >> ((f[t] & 3) * 8)) + 1) & 0xFFu) << 16) | (0xFFFFu - f[t]);   // (arrival count, lowest rank): a list has at most 64 entries, the byte does not carry
+#define H10X_DPP_MAX(ctrl, rowmask) { _Pragma("unroll") for (int t = 0; t < RIF; ++t) { const u32 o = (u32)__builtin_amdgcn_update_dpp(0, (int)key[t], ctrl, rowmask, 0xf, false); key[t] = o > key[t] ? o : key[t]; } }
+  H10X_DPP_MAX(0x111, 0xf)      // as wave_max_u32
+  H10X_DPP_MAX(0x112, 0xf)
+  H10X_DPP_MAX(0x114, 0xf)
+  H10X_DPP_MAX(0x118, 0xf)
+  H10X_DPP_MAX(0x142, 0xa)
+  H10X_DPP_MAX(0x143, 0xc)
+#undef H10X_DPP_MAX
+#pragma unroll
+  for (int t = 0; t < RIF; ++t) keyV = (u32)writelane_u32(__builtin_amdgcn_readlane((int)key[t], 63), 32 + t, (int)keyV);
+  const bool live = lane >= 32 && dv != 0;                   // lane 32 + t of a list that exists (the lanes behind them hold 0)
+  const u32 bcnt = keyV >> 16, best = 0xFFFFu - (keyV & 0xFFFFu);   // (best: only where bcnt >= 1 — the key of a lane that counted)
+  const bool act = live && bcnt >= thr;                      // hash10x.c:807 (thr >= 1)
+  u32 rbV = NONE16;
+  if (act) rbV = root[best];
+#pragma unroll
+  for (int t = 0; t < RIF; ++t) {
+    const u32 rb = (u32)__builtin_amdgcn_readlane((int)rbV, 32 + t);
+    qV = (u32)writelane_u32((int)__popcll(__builtin_amdgcn_ballot_w64(f[t] == rb)), 32 + t, (int)qV);   // (rb = NONE16, no root on record or inactive: matches the lanes without an entry — dropped below)
+  }
+  if (live) {
+    const u32 i = i0 + lane - 32;
+    const u32 q = rbV != NONE16 ? qV : 0u;
+    root[i] = (u16)(act ? rbV : i);
+    const u32 lo = (act ? best : (u32)NONE16) | (q << 16), hi = (q >> 16) | (totV << 8);   // RES_PACK in 32-bit halves
+    res[i] = ((u64)hi << 32) | lo;
+  }
+}
 struct WorkAcc { u32 depth; unsigned long long *s; };
-template <bool IN_LDS, int FIRST_MODE /* 0 dense in LDS, 1 ranked in LDS, 2 dense on an HBM slot, 3 hashed in LDS */, int CL_THREADS, int KLASS>
+// Dense placement in LDS: does block `code` (local number) run with 4-byte entries of first[] — where that costs the list loop no wave (see FirstDense)? The kernel asks
+// per block and calls cluster_one_block in the instantiation of that width.
+template <int CL_THREADS> __device__ __forceinline__ bool dense_first_wide(const ClusterArgs &a, u32 code) {
+  if (a.narrowFirst == 1) return false;
+  const u32 n = (u32)__builtin_amdgcn_readfirstlane((int)a.nGood[__builtin_amdgcn_readfirstlane((int)code)]);
+  const u32 nW = histWaves(a.nBlocksFirst, n, CL_THREADS / WAVE, 0, a.ldsBudget), nW4 = histWaves(2 * a.nBlocksFirst, n, CL_THREADS / WAVE, 0, a.ldsBudget);
+  return nW4 >= nW || (a.narrowFirst >= 2 && nW4 >= a.narrowFirst);   // (A/B: accept down to narrowFirst waves)
+}
+template <bool IN_LDS, int FIRST_MODE /* 0 dense in LDS, 1 ranked in LDS, 2 dense on an HBM slot, 3 hashed in LDS */, int CL_THREADS, int KLASS, bool WIDE = false /* dense in LDS: 4-byte entries (dense_first_wide) */>
 __device__ __forceinline__ void cluster_one_block(const ClusterArgs &a, u32 code, unsigned char *region, u16 *firstGlobal, u32 *sh /* small shared ints */, WorkAcc &acc) {   // code: local block number
   constexpr int CL_WAVES = CL_THREADS / WAVE;
   // lists a wave keeps in flight: 4, but 2 where the kernel must stay within 64 VGPRs (two workgroups per CU) AND carries
@@ -735,22 +816,17 @@ __device__ __forceinline__ void cluster_one_block(const ClusterArgs &a, u32 code
   // work queue then serve nearly every barcode; the phases behind the loop always use the whole workgroup)
   u32 nW;
   if constexpr (RANKED) nW = 0;                       // ranked placement: decided once the bitmap pass has counted the barcodes present
-  else nW = IN_LDS ? histWaves(FIRST_LDS ? a.nBlocksFirst : 0, n, CL_WAVES, bmWords, a.ldsBudget) : (u32)CL_WAVES;
+  else nW = IN_LDS ? histWaves(FIRST_LDS ? (WIDE ? 2 : 1) * a.nBlocksFirst : 0, n, CL_WAVES, bmWords, a.ldsBudget) : (u32)CL_WAVES;
   if (!RANKED && !nW) return;                                // cannot happen: the classification sends such a barcode to the HBM-scratch class
-  // dense placement in LDS: 4-byte entries where that costs the list loop no wave (see FirstDense)
-  bool wideFirst = false;
-  if (FIRST_LDS && !RANKED && a.narrowFirst != 1) {
-    const u32 nW4 = histWaves(2 * a.nBlocksFirst, n, CL_WAVES, bmWords, a.ldsBudget);
-    wideFirst = nW4 >= nW || (a.narrowFirst >= 2 && nW4 >= a.narrowFirst);   // (A/B: accept down to narrowFirst waves)
-    if (wideFirst) nW = nW4;
-  }
+  static_assert(!WIDE || (FIRST_LDS && !RANKED), "4-byte entries by template parameter: the dense placement in LDS");
+  constexpr bool wideFirst = WIDE;
   // ranked placement: first[] lies BEHIND the histograms and both are laid out after the bitmap pass, when the number of
   // barcodes present is known: the list loop then runs on as many waves as what is left of the budget has room for
   Work w = carve(region, RANKED ? 0 : (FIRST_LDS || !IN_LDS ? (wideFirst ? 2 * a.nBlocksFirst : a.nBlocksFirst) : 0), n, bmWords);
   if (IN_LDS && FIRST_MODE == 2) w.first = firstGlobal;      // hybrid: first[] on this workgroup's HBM slot, the rest in LDS
-  typename std::conditional<RANKED, FirstRanked, FirstDense<FIRST_LDS>>::type ft{};
+  typename std::conditional<RANKED, FirstRanked, FirstDense<FIRST_LDS, WIDE>>::type ft{};
   if constexpr (RANKED) { ft.first = w.first; ft.bm = w.bm; ft.pre = w.pre; ft.wide = 0; }
-  else { ft.first = w.first; ft.wide = wideFirst ? 1u : 0u; }
+  else ft.first = w.first;
   const u32 lcode = code; code = a.segs.globalOf(lcode);
   if constexpr (!RANKED) ft.none = code;     // from here on `code` is the global barcode number (what the lists hold)
   const u32 rsh = a.rowShift;
@@ -864,6 +940,8 @@ __device__ __forceinline__ void cluster_one_block(const ClusterArgs &a, u32 code
   u32 cjN[RIF], cj2N[RIF], cjNN[RIF];
   u32 dvCur, dvN, dvNN, dvD;                                 // descriptors of this round's lists and of the next three rounds' (see descLoad)
   u32 sDepth = 0;                                            // entries of the lists this wave has worked through (work counter)
+  u32 vDepth = 0;                                            // the same, kept per lane by the straight-line rounds: the lengths as they lie in the descriptor register
+  using FTT = decltype(ft);
   H10X_LOAD_D(listWave ? uwave * RIF : n, dvN)
   H10X_LOAD_D(listWave ? uwave * RIF + stepR : n, dvNN)
   H10X_LOAD_D(listWave ? uwave * RIF + 2 * stepR : n, dvD)
@@ -875,7 +953,7 @@ __device__ __forceinline__ void cluster_one_block(const ClusterArgs &a, u32 code
     u32 cj[RIF], cj2[RIF], dl[RIF];
     dvCur = dvN; dvN = dvNN; dvNN = dvD;
 #pragma unroll
-    for (int t = 0; t < RIF; ++t) { cj[t] = cjN[t]; cj2[t] = cj2N[t]; cjN[t] = cjNN[t]; dl[t] = (u32)__builtin_amdgcn_readlane((int)dvCur, 32 + t); }
+    for (int t = 0; t < RIF; ++t) { cj[t] = cjN[t]; cj2[t] = cj2N[t]; cjN[t] = cjNN[t]; if constexpr (!FTT::SHORT_ROUNDS) dl[t] = (u32)__builtin_amdgcn_readlane((int)dvCur, 32 + t); }
     if constexpr (FIRST_MODE != 0) H10X_LOAD_B(cj2N, dvN) else
     // (dense placement = small data sets, where most lists fit one chunk; lanes 32 .. 32 + RIF - 1 of the descriptor register hold the lengths: one compare and a ballot say whether any list of the next round is longer than
     // a chunk — at yeast scale one list in seven is, so more than half of the rounds skip the RIF address set-ups; the registers then keep stale values that
@@ -883,11 +961,27 @@ __device__ __forceinline__ void cluster_one_block(const ClusterArgs &a, u32 code
     if (__builtin_amdgcn_ballot_w64(lane >= 32 && dvN > (u32)WAVE)) H10X_LOAD_B(cj2N, dvN)
     H10X_LOAD_A(cjNN, dvNN)
     H10X_LOAD_D(listWave ? i0 + 3 * stepR : n, dvD)
+    if constexpr (FTT::SHORT_ROUNDS) {
+      // Straight-line round (dense placement, 4-byte entries): none of the wave's lists is longer than a chunk — six rounds in seven at yeast scale, the ranks of a
+      // barcode ascend in depth — asked of the lengths in lanes 32 .. of the descriptor register like the second-chunk test above. No test of a length from here on:
+      // a list of length 0 (rank 0, past the last rank) offers no rank, reads "unseen" in every lane and is masked out of the round's one store.
+      if (listWave && !__builtin_amdgcn_ballot_w64(lane >= 32 && dvCur > (u32)WAVE)) {
+#pragma unroll
+        for (int t = 0; t < RIF; ++t) if (cj[t] != code) ft.update(cj[t], i0 + t);
+        SYNC_LDS();
+        short_round<RIF>(ft, cj, dvCur, i0, w.hist + wave * w.histWords, w.root, res, thr);
+        vDepth += lane >= 32 ? dvCur : 0u;
+        continue;
+      }
+    }
 #define RS_OF(t) ((u32)__builtin_amdgcn_readlane((int)dvCur, t))   /* list offset of this round's list t: only lists of more than two chunks ask */
+    if constexpr (FTT::SHORT_ROUNDS) {                       // (the lengths as scalars: only the rounds that take the general code need them)
+#pragma unroll
+      for (int t = 0; t < RIF; ++t) dl[t] = (u32)__builtin_amdgcn_readlane((int)dvCur, 32 + t);
+    }
 #pragma unroll
     for (int t = 0; t < RIF; ++t) {
       const u32 i = i0 + t;
-      using FTT = decltype(ft);
       if constexpr (FTT::SELF) { if (cj[t] != code) ft.update(cj[t], i); }          // dense: the barcode number IS the handle (the barcode's own: reads "unseen")
       else cj[t] = cj[t] != code ? ft.update(cj[t], i) : ft.none;    // from here on cj / cj2 hold handles
       if (dl[t] > WAVE) {
@@ -900,7 +994,6 @@ __device__ __forceinline__ void cluster_one_block(const ClusterArgs &a, u32 code
     // the first[] values of all the round's lists are read back in one go (one wait for up to 2 RIF LDS reads instead of one per list):
     // from here on cj / cj2 hold first[] values, NONE16 where a lane has no entry
     constexpr u32 NOENTRY = NOHANDLE;
-    u32 rootV = 0; u64 resV = 0; bool mine = false;          // results of the round's lists, list t in lane t: one LDS and one HBM store per round (H10X_BATCH)
 #pragma unroll
     for (int t = 0; t < RIF; ++t) {
       const u32 i = i0 + t;
@@ -922,7 +1015,6 @@ __device__ __forceinline__ void cluster_one_block(const ClusterArgs &a, u32 code
         sDepth += d;
       }
     }
-    (void)rootV; (void)resV; (void)mine;
   }
 #undef RS_OF
 #undef H10X_LOAD_D
@@ -999,6 +1091,7 @@ __device__ __forceinline__ void cluster_one_block(const ClusterArgs &a, u32 code
   // work counters: kept per lane over the barcodes of the workgroup, posted once when the kernel ends (19 atomics per
   // barcode on four shared words would queue up in L2 behind those of every other workgroup)
   if (lane == 0) acc.depth += sDepth;
+  if constexpr (FTT::SHORT_ROUNDS) acc.depth += vDepth;
   if (tid == 0) { acc.s[3] += (u32)(gr[0] >> 32); acc.s[0] += n; acc.s[1] += a.blocks[lcode].nHash; acc.s[2] += 1; }
   if (!FIRST_LDS) {                                          // leave first[] clean for the next barcode of this workgroup
     SYNC();
@@ -1992,6 +2085,11 @@ void cluster_kernel(ClusterArgs a) {
     // of the spills and 170 of 6900 instructions, and is 3-4 % SLOWER: 2.49 against 2.41 ms, measured round 2)
     if constexpr (FIRST_MODE == 5) cluster_one_block_tp<CL_THREADS, KLASS>(a, wi < a.nFront ? a.front[wi] : a.list[wi - a.nFront], region, sh, acc);
     else if constexpr (FIRST_MODE == 4) cluster_one_block_tr<CL_THREADS, KLASS>(a, wi < a.nFront ? a.front[wi] : a.list[wi - a.nFront], region, sh, acc);
+    else if constexpr (IN_LDS && FIRST_MODE == 0) {           // dense in LDS: the block's list loop in the width of its first[] (neither form carries the other's update)
+      const u32 code = wi < a.nFront ? a.front[wi] : a.list[wi - a.nFront];
+      if (dense_first_wide<CL_THREADS>(a, code)) cluster_one_block<IN_LDS, FIRST_MODE, CL_THREADS, KLASS, true>(a, code, region, firstGlobal, sh, acc);
+      else cluster_one_block<IN_LDS, FIRST_MODE, CL_THREADS, KLASS, false>(a, code, region, firstGlobal, sh, acc);
+    }
     else cluster_one_block<IN_LDS, FIRST_MODE, CL_THREADS, KLASS>(a, wi < a.nFront ? a.front[wi] : a.list[wi - a.nFront], region, firstGlobal, sh, acc);
   }
   u64 depth = acc.depth;
