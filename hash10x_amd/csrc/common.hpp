@@ -187,7 +187,7 @@ struct Ctx {
   DevBuf<u8>  within;         // hashNumber
   DevBuf<u16> goodPos;        // H : per block [blockOff[c], blockOff[c]+nGood[c])
   DevBuf<u32> nGood;          // nBlocks
-  DevBuf<u64> goodRow;        // H : per good hash of a block, in rank order: (offset of its barcode list in rows[] >> rowShift, its length) — stage_c.hip good_rows_kernel
+  DevBuf<u64> goodRow;        // H : per good hash of a block, in rank order: (offset of its barcode list in rows[] >> rowShift, its length) — stage_c_good.hip good_rows_kernel
   DevBuf<u32> goodEntries;    // nBlocks : sum of the depths of a block's good hashes = entries of its barcode lists
   DevBuf<u32> clusterRaw;     // 2 x nBlocks, after --cluster: clusters before the read merge (bit 31: given up), good hashes labelled — the --verbose figures of codeClusterFind
   bool haveRange = false, haveGood = false; int rangeMin = 0, rangeMax = 0;
@@ -402,6 +402,7 @@ struct XGuard {
 static inline unsigned divUp(u64 a, u64 b) { return (unsigned)((a + b - 1) / b); }
 template <typename T> static inline T hmin(T a, T b) { return a < b ? a : b; }
 template <typename T> static inline T hmax(T a, T b) { return a > b ? a : b; }
+inline int bitsFor(u64 maxValue) { int b = 1; while (b < 64 && (maxValue >> b)) ++b; return b; }   // bits that hold values 0 .. maxValue (host: the sorts' key widths)
 
 // hashIndexFind(hash, FALSE) (hash10x.c:139-152): start hash & mask, odd stride ((hash >> B) & mask) | 1; 0 = absent
 __device__ __forceinline__ u32 probe_find(const u32 *__restrict__ table, const u64 *__restrict__ hashValue, int B, u64 h) {
@@ -423,6 +424,7 @@ int stageA_runStarts(Ctx *c, const u32 *dRec, u64 nRec, std::vector<u64> &starts
 int replayChunks(const std::vector<u64> &starts, const std::vector<u32> &zeroRuns, u64 chunk, std::vector<u64> &merges, bool eofPass);   // stable sort of .fqb records by their first 4 bytes
 int stageB_run(Ctx *c, DevBuf<u64> &entHash, DevBuf<u32> &entCode, DevBuf<u32> &entRead);
 void warm_prim(hipStream_t), warm_stageA(hipStream_t), warm_stageB(hipStream_t), warm_stageC(hipStream_t), warm_stageD(hipStream_t), warm_stageE(hipStream_t), warm_stageF(hipStream_t), warm_shard(hipStream_t);   // h10x_warm
+void warm_stageCGood(hipStream_t), warm_stageCHost(hipStream_t), warm_stageCSplit(hipStream_t);   // the other units of --hashDepthRange / --cluster / --clusterSplit: warm_stageC calls them
 int stageB_buildCSR(Ctx *c);                   // rows/rowStart from clusHash + hashDepth (fillHashTable)
 int stageB_finishClusHash(Ctx *c, DevBuf<u64> &key);   // key[e] = index << 32 | read16 in block order -> clusHash sorted per block
 int stageB_finishClusHashFromReplies(Ctx *c, const u32 *replyIdx, const u32 *replyPos, const u32 *entRead);   // sharded: entry e's index is replyIdx[replyPos[e]]

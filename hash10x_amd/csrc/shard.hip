@@ -238,7 +238,6 @@ static int xchg_hostGather(Ctx *c, Comm *cm, const void *send, void *recv, size_
   if (ts) c->tstop(*ts);
   return rc;
 }
-static int bitsForS(u64 v) { int b = 1; while (b < 64 && (v >> b)) ++b; return b; }
 static unsigned gridFor(u64 n) { return (unsigned)hmin<u64>(divUp(n ? n : 1, 256), 65535u * 2); }
 
 struct ShardInfo { u64 barcodes, entries, records; };
@@ -346,7 +345,7 @@ int shard_readFqb(Ctx *c, Comm *cm, const u32 *dRec, u64 nRec) {
   } else {                                                   // very many ranks: a stable one-pass radix partition on the owner number
     DevBuf<u32> io, oKey, oKeyS; H10X_HIP(c, io.alloc(H)); H10X_HIP(c, oKey.alloc(H)); H10X_HIP(c, oKeyS.alloc(H));
     if (H) { iota_kernel<<<gridFor(H), 256, 0, st>>>(io.p, H); owner_key_kernel<<<gridFor(H), 256, 0, st>>>(entHash.p, H, dLow.p, N, oKey.p); }
-    H10X_TRY(prim_sort_pairs_u32_u32(c, pt, oKey.p, oKeyS.p, io.p, perm.p, H, 0, bitsForS((u64)N - 1)));
+    H10X_TRY(prim_sort_pairs_u32_u32(c, pt, oKey.p, oKeyS.p, io.p, perm.p, H, 0, bitsFor((u64)N - 1)));
     if (H) gather_send_kernel<<<gridFor(H), 256, 0, st>>>(entHash.p, entCode.p, perm.p, H, c->codeBase, sHash.p, sCodeG.p);
     owner_key_bounds_kernel<<<divUp((u64)N + 1, 256), 256, 0, st>>>(oKeyS.p, H, N, dBound.p);
     H10X_HIP(c, hipMemcpyAsync(bound.data(), dBound.p, ((size_t)N + 1) * 8, hipMemcpyDeviceToHost, st));
@@ -402,7 +401,7 @@ int shard_readFqb(Ctx *c, Comm *cm, const u32 *dRec, u64 nRec) {
   // my distinct hashes in (first barcode, hash) order: a stable sort by first barcode of the hash-ordered list; the runs of
   // equal first barcode give the per-barcode counts the numbering needs
   DevBuf<u32> order, dFirstSorted; H10X_HIP(c, order.alloc(Uo)); H10X_HIP(c, dFirstSorted.alloc(Uo)); H10X_HIP(c, c->oIndex.alloc(Uo));
-  H10X_TRY(prim_sort_pairs_u32_u32(c, pt, dFirst.p, dFirstSorted.p, dio.p, order.p, Uo, 0, bitsForS(nB)));
+  H10X_TRY(prim_sort_pairs_u32_u32(c, pt, dFirst.p, dFirstSorted.p, dio.p, order.p, Uo, 0, bitsFor(nB)));
   first_runs_kernel<<<divUp(nB, 256), 256, 0, st>>>(dFirstSorted.p, Uo, nB, myStart.p, cntFirst.p);
   { std::vector<u64> sc((size_t)N, nB), so((size_t)N, 0), rc((size_t)N, nB), ro((size_t)N);
     for (int r = 0; r < N; ++r) ro[r] = (u64)r * nB;
@@ -468,7 +467,7 @@ int shard_readFqb(Ctx *c, Comm *cm, const u32 *dRec, u64 nRec) {
   const bool runsByIndex = c->optOverlap != 0 && N > 1;      // (one rank: its own run IS the whole table in hash order — nothing to walk in step; knob 0 = round 5's form throughout)
   if (runsByIndex) {
     H10X_HIP(c, sIdx.alloc(Uo)); H10X_HIP(c, sDepth.alloc(Uo));
-    H10X_TRY(prim_sort_pairs_u32_u32(c, pt, c->oIndex.p, sIdx.p, dDepth.p, sDepth.p, Uo, 0, bitsForS((u64)U + 1)));
+    H10X_TRY(prim_sort_pairs_u32_u32(c, pt, c->oIndex.p, sIdx.p, dDepth.p, sDepth.p, Uo, 0, bitsFor((u64)U + 1)));
   }
   const int besideClus = c->optOverlap ? (int)T_CLUSHASH : -1;
   XGuard xGuard(c);                                          // (an error return below must not park gIdx / gDepth / dDepth while the exchange stream still uses them)
@@ -858,7 +857,7 @@ int shard_rebuildOwnerLists(Ctx *c) {
   sPair.release();
   if (M != c->oM) return c->fail("owner lists: %llu entries arrived for %llu list slots", (u64)M, (u64)c->oM);
   if (M) owner_key_of_kernel<<<gridFor(M), 256, 0, st>>>(rPair.p, M, ordOf.p);
-  H10X_TRY(prim_sort_keys_u64(c, pt, rPair.p, rSorted.p, M, 0, 32 + bitsForS(Uo)));
+  H10X_TRY(prim_sort_keys_u64(c, pt, rPair.p, rSorted.p, M, 0, 32 + bitsFor(Uo)));
   H10X_HIP(c, c->oRows.alloc(M));
   if (M) low_word_kernel<<<gridFor(M), 256, 0, st>>>(rSorted.p, M, c->oRows.p);
   H10X_HIP(c, hipStreamSynchronize(st));

@@ -17,7 +17,6 @@
 namespace h10x {
 
 constexpr u32 SLOT_EMPTY = 0xFFFFFFFFu;
-static int bitsFor(u64 maxValue) { int b = 1; while (b < 64 && (maxValue >> b)) ++b; return b; }
 
 // ------------------------------------------------------------------------------------------ distinct hashes
 // (position i starts a run iff the ordinal steps there: ord has n + 1 entries)

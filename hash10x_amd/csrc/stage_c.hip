@@ -1,282 +1,31 @@
-// stage_c.hip — depth filter, good-hash lists and per-barcode clustering.
+// stage_c.hip — the kernels of --cluster and the functions that launch them (the host driver is stage_c_host.hip).
 //
-// Replaces hashWithinRangeBuild + goodHashesBuild (hash10x.c:528-539, 738-766), codeClusterFind
-// (hash10x.c:770-835), codeClusterReadMerge (hash10x.c:837-868) and the OMP --cluster loop
-// (hash10x.c:1241-1261).
+// Replaces codeClusterFind (hash10x.c:770-835) and codeClusterReadMerge (hash10x.c:837-868) for the barcodes the
+// reference's OMP loop hands out (hash10x.c:1241-1261).
 //
 // The reference's codeClusterFind is dense: per good hash i it clears and rescans an n-entry count
 // array (O(n^2) per barcode) and callocs an int per barcode of the data set. Here it is sparse
 // (verified bit-exact there): one workgroup owns one barcode and keeps everything
 // in LDS —
-//   (a) first[cj]   = lowest good-hash rank i >= 1 whose barcode list contains cj   (LDS u16 table,
-//                     filled by all waves with CAS-min while streaming the lists from HBM)
-//   (b) per rank i  : one wavefront gathers first[] for the <= 256 entries of list i into registers and
-//                     finds the mode among values < i (ties -> lowest rank) and their count with
-//                     ballot/popcount/readlane — the reference's msBest / msMax / msTot
-//   (c) one lane replays the order-dependent part (cluster creation, > 255 abort, labels)
-//   (d) per rank i  : the count for the cluster's founding rank (a second gather only when it is not
-//                     msBest) and the IEEE double quotient
-//   (e) point_sum_kernel: one LANE per barcode adds the quotients in rank order => bit-identical pointToMin
-//       (a serial fp64 chain per barcode: 64 barcodes per wave instruction instead of one)
-//   (f) read_merge_kernel: connected components over <= 255 labels linked by shared reads, renumbered by
+//   first[cj] = lowest good-hash rank i >= 1 whose barcode list contains cj, filled by all waves with a minimum while the
+//               lists stream in from HBM (dense, ranked or translated placement: FirstDense, FirstRanked, SlotTable);
+//   per rank i, one wavefront finds the mode among the first[] values of list i below i and its count in a byte histogram —
+//               the reference's msBest / msMax / msTot — and the count for the founding rank of the cluster it joins;
+//               one result word per rank goes to HBM (cluster_kernel over cluster_one_block, _tr, _tp);
+//   replay_kernel restates the order-dependent part (cluster creation, > 255 abort, labels) from those words, one workgroup per barcode;
+//   point_sum_kernel: one WAVE per barcode adds the quotients in rank order => bit-identical pointToMin;
+//   read_merge_kernel: connected components over <= 255 labels linked by shared reads, renumbered by
 //       ascending minimum label — small workgroups of its own, not 1024 lanes waiting on 255 labels.
 // Barcodes whose working set exceeds the LDS budget run the same code on a per-workgroup HBM scratch.
-#include "common.hpp"
-#include <chrono>
-#include "prim.hpp"
+#include "cluster.hpp"
 #include <type_traits>
-#include <rocprim/block/block_radix_sort.hpp>
 
 namespace h10x {
 
-
-constexpr int CL_THREADS_SMALL = 1024;                     // <= 79 KB working sets, two workgroups per CU
-constexpr int CL_THREADS_HUGE = 1024;                      // the whole LDS of a CU, one workgroup per CU
 constexpr u16 NONE16 = 0xFFFF;
 constexpr u32 NOHANDLE = 0xFFFFFFFFu;                        // (argument of row_mode_hist for a chunk a list does not have)
 constexpr int ROWS_IN_FLIGHT = 4;                                 // barcode lists a wavefront keeps in flight
 constexpr int RCHUNK = 4;                                   // register chunks: lists up to 256 entries
-
-// ------------------------------------------------------------------------------------------ depth range
-__global__ void within_kernel(const u32 *__restrict__ depth, u32 hashNumber, int lo, int hi, u8 *__restrict__ within) {
-  const u32 i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= hashNumber) return;
-  const int n = (int)depth[i];
-  if (n >= lo && n < hi) within[i] = 1;                     // only ever set (hash10x.c:535)
-}
-__global__ void within_depth_kernel(const u32 *__restrict__ depth, const u8 *__restrict__ within, u32 hashNumber, u32 *__restrict__ out,
-                                    const u64 *__restrict__ rowStart, u32 rowShift, u64 *__restrict__ rowInfo /* null, or per hash: where its barcode list starts (>> rowShift) | (depth + 1, 0 outside the range) << 32 */) {
-  const u32 i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < hashNumber) {
-    const u32 wd = within[i] ? depth[i] + 1 : 0;             // 0 = outside the range(s); depth + 1 otherwise (one word tells both)
-    out[i] = wd; if (rowInfo) rowInfo[i] = (u64)(u32)(rowStart[i] >> rowShift) | ((u64)wd << 32);
-  }
-}
-
-// per block: keys (depth << 16 | position) of its in-range hashes, appended in any order; KT = u32 while the largest
-// in-range depth fits 16 bits (the segmented sort then moves half the bytes)
-template <typename KT>
-__global__ __launch_bounds__(256)
-void good_keys_kernel(const h10x_clushash *__restrict__ ch, const u64 *__restrict__ blockOff, const h10x_block *__restrict__ blocks,
-                      u32 nBlocks, const u32 *__restrict__ wdepth /* 0 = not in range, else depth + 1 */,
-                      KT *__restrict__ key, u32 *__restrict__ nGood, u32 *__restrict__ segEnd, u32 *__restrict__ entries /* sum of depths, saturating */) {
-  __shared__ u32 sCount; __shared__ unsigned long long sDepth;
-  for (u32 c = blockIdx.x; c < nBlocks; c += gridDim.x) {
-    const u64 o = blockOff[c]; const u32 nHash = blocks[c].nHash;
-    __syncthreads();
-    if (threadIdx.x == 0) { sCount = 0; sDepth = 0; }
-    __syncthreads();
-    unsigned long long myDepth = 0;
-    if (nHash <= 65535) {                                    // hash10x.c:748-753: bigger blocks are ignored
-      for (u32 base = 0; base < nHash; base += blockDim.x) {
-        const u32 p = base + threadIdx.x;
-        u32 wd = 0; bool good = false;
-        if (p < nHash) { wd = wdepth[ch[o + p].hash]; good = wd != 0; if (good) myDepth += wd - 1; }
-        const u64 bal = __ballot(good);
-        const int lane = threadIdx.x & (WAVE - 1);
-        u32 wb = 0;
-        if (lane == 0 && bal) wb = atomicAdd(&sCount, (u32)__popcll(bal));
-        wb = __shfl(wb, 0);
-        if (good) key[o + wb + (u32)__popcll(bal & ((1ULL << lane) - 1))] = (KT)(((KT)(wd - 1) << 16) | (KT)p);
-      }
-    }
-    for (int sft = 32; sft; sft >>= 1) myDepth += __shfl_down(myDepth, sft);
-    if ((threadIdx.x & (WAVE - 1)) == 0 && myDepth) atomicAdd(&sDepth, myDepth);
-    __syncthreads();
-    if (threadIdx.x == 0) { nGood[c] = sCount; segEnd[c] = (u32)o + sCount; entries[c] = sDepth > 0xFFFFFFFFull ? 0xFFFFFFFFu : (u32)sDepth; }
-  }
-}
-template <typename KT>
-__global__ void good_pos_kernel(const KT *__restrict__ key, u64 n, u16 *__restrict__ pos) {
-  u64 i = (u64)blockIdx.x * blockDim.x + threadIdx.x;
-  const u64 stride = (u64)gridDim.x * blockDim.x;
-  for (; i < n; i += stride) pos[i] = (u16)(key[i] & 0xFFFF);
-}
-__global__ void offsets32c_kernel(const u64 *__restrict__ off, u32 n, u32 *__restrict__ out) {
-  const u32 i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < n) out[i] = (u32)off[i];
-}
-
-// The good list of a block in one workgroup: the in-range hashes' depths as keys, their positions as values, sorted in LDS
-// (rocPRIM block radix sort, stable), positions written out — instead of key kernel + device-wide segmented sort + position
-// kernel. Blocks up to BLOCK_SORT_MAX entries, depths below 2^16; three launch classes by block size like clushash_block_kernel.
-// Round 5: ONE random read per entry. The chip does some 55 G independent random reads a second whatever the table's size (scratch/r5_gather_rate.hip: 64 MB .. 4 GB
-// tables, 1 .. 8 byte entries, all within 15 %), and this kernel used to make two — the depth byte of every entry, then the list offset of every good one: 4.1 G look-ups
-// in 72 ms on the 3 Gb set, i.e. at that wall. rowInfo[] (within_depth_kernel) holds both in a word; the offset rides through the sort as part of the value.
-template <int THREADS, int IPT>
-__global__ __launch_bounds__(THREADS)
-void good_block_kernel(const h10x_clushash *__restrict__ ch, const u64 *__restrict__ blockOff, const h10x_block *__restrict__ blocks,
-                       const u32 *__restrict__ list, const u32 *__restrict__ count /* this class's blocks: stageB_blockClassLists */,
-                       const u64 *__restrict__ rowInfo /* per hash: list offset | (0 = not in range, else depth + 1) << 32 */, int sortBits,
-                       u16 *__restrict__ goodPos, u32 *__restrict__ nGood, u32 *__restrict__ entries /* sum of depths, saturating */,
-                       u64 *__restrict__ goodRow /* list descriptor per rank: see good_rows_kernel */) {
-  using Sort = rocprim::block_radix_sort<u32, THREADS, IPT, u64>;
-  __shared__ typename Sort::storage_type storage;
-  __shared__ u32 sCount; __shared__ unsigned long long sDepth;
-  const u32 nList = *count;
-  for (u32 wi = blockIdx.x; wi < nList; wi += gridDim.x) {
-    const u32 c = list[wi];
-    const u32 nHash = blocks[c].nHash;                       // (the smallest class also takes the empty blocks: their counts are written too)
-    const u64 o = blockOff[c];
-    __syncthreads();
-    if (threadIdx.x == 0) { sCount = 0; sDepth = 0; }
-    __syncthreads();
-    // blocked arrangement: a thread holds IPT consecutive positions, so the positions are ascending in the order the sort
-    // takes as given, and a STABLE sort on the depth bits alone (one 8-bit pass for depths below 128, where depth and
-    // position in one key needed three) leaves equal depths in ascending position
-    u32 k[IPT]; u64 v[IPT]; u32 mine = 0; unsigned long long myDepth = 0;
-#pragma unroll
-    for (int j = 0; j < IPT; ++j) { k[j] = 0xFFFFFFFFu; v[j] = threadIdx.x * IPT + (u32)j; }
-    if (nHash) {
-      // (positions past the block's end read its last record: loads without a branch around them — written as `if (p < nHash) load` every entry was a branch, a load and a
-      // wait of its own, twelve memory latencies in a row per lane — the IPT records and then the IPT look-ups are in flight together)
-      u32 hs[IPT]; u64 ri[IPT];
-#pragma unroll
-      for (int j = 0; j < IPT; ++j) { const u32 p = threadIdx.x * IPT + (u32)j; hs[j] = ch[o + (p < nHash ? p : nHash - 1)].hash; }
-#pragma unroll
-      for (int j = 0; j < IPT; ++j) ri[j] = rowInfo[hs[j]];
-#pragma unroll
-      for (int j = 0; j < IPT; ++j) {
-        const u32 p = threadIdx.x * IPT + (u32)j; const u32 wd = (u32)(ri[j] >> 32);
-        if (p < nHash && wd) { k[j] = wd - 1; ++mine; myDepth += wd - 1; v[j] = (u64)p | ((ri[j] & 0xFFFFFFFFull) << 16); }   // value: position (16 bits: blocks of at most BLOCK_SORT_MAX entries) | list offset << 16
-      }
-    }
-    for (int sft = 32; sft; sft >>= 1) { mine += (u32)__shfl_down((int)mine, sft); myDepth += __shfl_down(myDepth, sft); }
-    if ((threadIdx.x & (WAVE - 1)) == 0 && mine) { atomicAdd(&sCount, mine); atomicAdd(&sDepth, myDepth); }
-    Sort().sort_to_striped(k, v, storage, 0, sortBits);      // ascending (depth, position): hash10x.c:726-730,758; padding keys last
-    __syncthreads();
-    const u32 nG = sCount;
-#pragma unroll
-    for (int j = 0; j < IPT; ++j) {                          // striped: coalesced stores
-      const u32 e = (u32)j * THREADS + threadIdx.x;
-      if (e < nG) {
-        goodPos[o + e] = (u16)v[j];
-        // where the rank's barcode list lies and how long it is (the sort key IS the depth): the cluster kernel streams these
-        // instead of gathering position -> hash index -> offset, depth per barcode
-        goodRow[o + e] = (u64)(u32)(v[j] >> 16) | ((u64)k[j] << 32);
-      }
-    }
-    if (threadIdx.x == 0) { nGood[c] = nG; entries[c] = sDepth > 0xFFFFFFFFull ? 0xFFFFFFFFu : (u32)sDepth; }
-  }
-}
-
-__global__ void good_rows_kernel(const h10x_clushash *__restrict__ ch, const u64 *__restrict__ blockOff, const u32 *__restrict__ nGood, const u16 *__restrict__ goodPos, u32 nBlocks,
-                                 const u32 *__restrict__ hashDepth, const u64 *__restrict__ rowStart, u32 rowShift, u64 *__restrict__ goodRow);
-static int bitsForC(u64 maxValue) { int b = 1; while (b < 64 && (maxValue >> b)) ++b; return b; }
-
-int stageC_depthRange(Ctx *c, int lo, int hi) {
-  hipStream_t st = c->stream; PrimTemp pt;
-  if (!c->haveState) return c->fail("no hash state loaded: use readFQB or readHash first");
-  c->haveGood = false;                                       // (a call that fails half-way must not leave the lists of an earlier one standing: rows[] and the offsets are replaced below)
-  c->tstart(T_GOOD);
-  const u32 U1 = c->hashNumber; const u32 nBlocks = c->nBlocks; const u64 H = c->nEntries;
-  if (!(c->haveRange && lo == c->rangeMin && hi == c->rangeMax)) {       // hash10x.c:530
-    if (!c->haveRange) { H10X_HIP(c, c->within.alloc(U1)); H10X_HIP(c, hipMemsetAsync(c->within.p, 0, U1, st)); }
-    within_kernel<<<divUp(U1, 256), 256, 0, st>>>(c->hashDepth.p, U1, lo, hi, c->within.p);
-    c->haveRange = true; c->rangeMin = lo; c->rangeMax = hi;
-    if (hi > 0 && (u32)hi > c->rangeHiMax) c->rangeHiMax = (u32)hi;
-  }
-  // sharded: the barcode lists of the in-range hashes come from their owners first (they depend on the ranges alone), so that
-  // the good lists below can point into them
-  XGuard xGuard(c);                                          // (the lists may still be arriving on the exchange stream when this function leaves early)
-  if (c->sharded) { c->tstop(T_GOOD); H10X_TRY(shard_exchangeRows(c)); c->tstart(T_GOOD); }
-  // goodHashesBuild (hash10x.c:738-766)
-  DevBuf<u64> key, keyS; DevBuf<u32> key32, keyS32, off32, segEnd, wdepth, red;
-  H10X_HIP(c, off32.alloc((size_t)nBlocks + 1));
-  H10X_HIP(c, segEnd.alloc(nBlocks)); H10X_HIP(c, wdepth.alloc(U1)); H10X_HIP(c, red.alloc(2));
-  H10X_HIP(c, c->nGood.alloc(nBlocks)); H10X_HIP(c, c->goodPos.alloc(H)); H10X_HIP(c, c->goodEntries.alloc(nBlocks)); H10X_HIP(c, c->goodRow.alloc(H));
-  // no in-range depth exceeds this, known without a round trip: the data set's barcode count (Ctx::depthBound) or the ranges' limit
-  const u32 goodDepthBound = hmin<u32>(c->depthBound, c->rangeHiMax ? c->rangeHiMax - 1 : 0);
-  const bool narrow = goodDepthBound <= 65535u;
-  const bool byBlocks = narrow && c->maxBlockHashes <= BLOCK_SORT_MAX;       // every block's list is built and sorted by one workgroup
-  DevBuf<u64> rowInfo; if (byBlocks) H10X_HIP(c, rowInfo.alloc(U1));
-  within_depth_kernel<<<divUp(U1, 256), 256, 0, st>>>(c->hashDepth.p, c->within.p, U1, wdepth.p, c->rowStart.p, (u32)c->rowShift, rowInfo.p);
-  H10X_TRY(prim_reduce_max_u32(c, pt, wdepth.p, red.p, U1));
-  if (byBlocks) {
-    int db = 1; while (db < 16 && (goodDepthBound >> db)) ++db;
-    const int sortBits = db + 1;                                              // one bit more than the largest depth: padding keys sort last
-    DevBuf<u32> lists, counts;
-    H10X_TRY(stageB_blockClassLists(c, lists, counts));
-    const unsigned gridBig = hmin<u32>(nBlocks, (u32)c->numCU * 8), gridSmall = hmin<u32>(nBlocks, 65535u * 4);
-    const int side = c->maxBlockHashes > BLOCK_SORT_CAP1 ? 2 : (c->maxBlockHashes > BLOCK_SORT_CAP0 ? 1 : 0);
-    ForkGuard forkGuard(c);
-    if (side) H10X_TRY(c->forkStreams(side));
-#define H10X_GOOD_LAUNCH(T, I, CLS, STREAM)                                                                                         \
-    { const u32 *const L = lists.p + (size_t)CLS * nBlocks, *const N = counts.p + CLS; const unsigned grid = CLS == 0 ? gridSmall : gridBig; \
-      good_block_kernel<T, I><<<grid, T, 0, STREAM>>>(c->clusHash.p, c->blockOff.p, c->blocks.p, L, N, rowInfo.p, sortBits, c->goodPos.p, c->nGood.p, c->goodEntries.p, c->goodRow.p); }
-    H10X_GOOD_LAUNCH(H10X_BS_T0, H10X_BS_I0, 0, st)
-    if (side >= 1) H10X_GOOD_LAUNCH(H10X_BS_T1, H10X_BS_I1, 1, c->aux[0])
-    if (side >= 2) H10X_GOOD_LAUNCH(1024, 8, 2, c->aux[1])
-#undef H10X_GOOD_LAUNCH
-    H10X_TRY(c->faultAt(3));
-    if (side) H10X_TRY(c->joinStreams(side));
-    forkGuard.done();
-  }
-  else if (narrow) { H10X_HIP(c, key32.alloc(H)); H10X_HIP(c, keyS32.alloc(H)); } else { H10X_HIP(c, key.alloc(H)); H10X_HIP(c, keyS.alloc(H)); }
-  if (byBlocks) {}
-  else if (narrow) good_keys_kernel<u32><<<hmin<u32>(nBlocks, 16384), 256, 0, st>>>(c->clusHash.p, c->blockOff.p, c->blocks.p, nBlocks, wdepth.p,
-                                                                             key32.p, c->nGood.p, segEnd.p, c->goodEntries.p);
-  else good_keys_kernel<u64><<<hmin<u32>(nBlocks, 16384), 256, 0, st>>>(c->clusHash.p, c->blockOff.p, c->blocks.p, nBlocks, wdepth.p,
-                                                                      key.p, c->nGood.p, segEnd.p, c->goodEntries.p);
-  H10X_TRY(prim_reduce_max_u32(c, pt, c->nGood.p, red.p + 1, nBlocks));
-  DevBuf<u64> redSum; H10X_HIP(c, redSum.alloc(1));
-  H10X_TRY(prim_reduce_sum_u32_u64(c, pt, c->nGood.p, redSum.p, nBlocks));
-  u32 hr[2]; u64 sumGood = 0;
-  H10X_TRY(c->readback(hr, red.p, 8));
-  H10X_TRY(c->readback(&sumGood, redSum.p, 8));
-  H10X_TRY(c->syncReadbacks());
-  hr[0] = hr[0] ? hr[0] - 1 : 0;                              // wdepth holds depth + 1
-  c->maxGoodDepth = hr[0]; c->maxGood = hr[1]; c->meanGood = nBlocks > 1 ? (u32)(sumGood / (nBlocks - 1)) : 0;
-  offsets32c_kernel<<<divUp((u64)nBlocks + 1, 256), 256, 0, st>>>(c->blockOff.p, nBlocks + 1, off32.p);
-  // ascending (depth, position): qsort by depth, stable => ties by position (hash10x.c:726-730,758)
-  if (H && !byBlocks) {
-    if (narrow) {
-      H10X_TRY(prim_seg_sort_keys_u32(c, pt, key32.p, keyS32.p, (u32)H, nBlocks, off32.p, segEnd.p, 0, 16 + bitsForC(hr[0])));
-      good_pos_kernel<u32><<<(unsigned)hmin<u64>(divUp(H, 256), 65535u * 2), 256, 0, st>>>(keyS32.p, H, c->goodPos.p);
-    } else {
-      H10X_TRY(prim_seg_sort_keys_u64(c, pt, key.p, keyS.p, (u32)H, nBlocks, off32.p, segEnd.p, 0, 16 + bitsForC(hr[0])));
-      good_pos_kernel<u64><<<(unsigned)hmin<u64>(divUp(H, 256), 65535u * 2), 256, 0, st>>>(keyS.p, H, c->goodPos.p);
-    }
-  }
-  // list descriptors per good hash, in rank order: written by good_block_kernel; the device-wide sort path adds them here
-  if (!byBlocks && nBlocks) good_rows_kernel<<<hmin<u32>(nBlocks, 65535u * 4), 256, 0, st>>>(c->clusHash.p, c->blockOff.p, c->nGood.p, c->goodPos.p, nBlocks, c->hashDepth.p, c->rowStart.p,
-                                                                                           (u32)c->rowShift, c->goodRow.p);
-  H10X_HIP(c, hipGetLastError());                            // (no round trip here: --cluster, the next command, starts with one)
-  H10X_TRY(c->xJoin());                                      // sharded: the in-range lists have arrived before anything queued from here on runs (and before the next collective)
-  c->haveGood = true;
-  c->tstop(T_GOOD);
-  return 0;
-}
-
-// ------------------------------------------------------------------------------------------ cluster kernel
-struct ClusterArgs {
-  h10x_block *blocks; const u64 *blockOff; h10x_clushash *clusHash;
-  const u16 *goodPos; const u32 *nGood;
-  const u64 *goodRow;                                       // per rank (slice of block c at blockOff[c]): low word = list offset in rows[] (>> rowShift), high word = list length = hashDepth
-  const u32 *rows;
-  const u32 *list; u32 nList; u32 *workCounter;
-  u32 *started;                 // host-visible word per workgroup, set when the workgroup starts (whole-CU class only)
-  const u32 *front; u32 nFront;                             // handed out before list[]: the largest barcodes of the launch
-  u32 nBlocks; int threshold;
-  SegMap segs;                                              // local block number -> global barcode number (what the lists hold); identity when unsharded
-  u32 rowShift;                                             // rows[]: a list starts at entry (rs << rowShift) — sharded runs with more than 2^32 list entries
-  u32 nBlocksFirst;                                         // size of first[]: barcodes of the whole data set + 1
-  u32 firstCap;                                             // ranked placement, test knob: cap on the first[] entries of a block (0 = what the budget leaves)
-  u32 hashMinSlots;                                         // translated placement: table slots below which the 10-bit tag is too narrow for the data set's barcode count
-  u32 hashBits;                                             // b
-  u16 *handles; size_t handleStride; u32 hStride;           // translated placement: HBM slot of the workgroup (handleStride u16 each), u16 per list (a power of two >= 64 that holds the longest list)
-  const u32 *entries;                                       // per block: entries of its barcode lists (sum of depths of its good hashes)
-  u32 *overflow, *overflowCount;                            // ranked / hashed placement: blocks whose table was too small (re-run in the next larger placement)
-  unsigned char *scratch; size_t scratchStride;             // global-mode working set per workgroup
-  u32 maxGood;
-  u32 ldsBudget;                                            // LDS bytes of the launch class (list loop: as many waves as have room for a histogram)
-  u64 *res;                                                 // out, per rank (slice of block c at blockOff[c]): RES_PACK(msBest or NONE16 if msMax < threshold,
-                                                            // minShareCount[clusterMin], msTot) — replay_kernel turns it into the rank's pointToMin term in place
-  u64 *stats;                                               // [0] sum good, [1] sum good depth, [2] sum nHash, [3] codes
-  u64 *phase;                                               // diagnostic per-phase ticks (null = off)
-  u32 narrowFirst;                                          // test / A-B knob: keep first[] at 2 bytes per entry in every block
-  u32 tpClassT;                                             // packed translated placement: class T (lists of 65 .. 96 entries, two to a unit of three chunks) in use
-};
 
 // Working set of the list loop inside a region (LDS or HBM scratch). Since round 3 the per-rank arrays of the reference's
 // bookkeeping (list offset and length, msMax, msTot, msBest, label: 15 bytes per rank) are gone from it: the list
@@ -286,7 +35,6 @@ struct ClusterArgs {
 // and one byte-histogram per wave.
 // one word per rank: bits 0-15 msBest of an active rank (NONE16: inactive), 16-39 minShareCount[clusterMin[label]], 40-63 msTot (hash10x.c:803-821)
 #define RES_PACK(best, q, tot) ((u64)(best) | ((u64)(q) << 16) | ((u64)(tot) << 40))
-constexpr u32 RES_COUNT_MAX = (1u << 24) - 1;               // list lengths beyond this do not fit the word: refused by stageC_cluster
 struct Work {
   u16 *first;        // NONE16 = unseen; indexed by barcode (dense) or by the barcode's rank among those present (ranked)
   u32 *bm; u16 *pre; // ranked placement: presence bitmap over all barcodes and its exclusive popcount prefix per word (< 65536 present)
@@ -295,31 +43,6 @@ struct Work {
   u32 *hist;         // CL_WAVES private byte-histograms over ranks (4 counters per word), all zero between lists
   u32 histWords;     // words per wave
 };
-__host__ __device__ inline size_t pad16(size_t b) { return (b + 15) & ~(size_t)15; }
-__host__ __device__ inline size_t workBytes(u32 nFirst, u32 n, u32 nWaves, u32 bmWords) {
-  size_t b = pad16((size_t)nFirst * 2) + pad16((size_t)bmWords * 4) + pad16((size_t)bmWords * 2);
-  b += pad16((size_t)n * 2);                                // root
-  b += (size_t)nWaves * (((size_t)n + 3) / 4) * 4;          // hist (the list of unsettled ranks, 2 n bytes at most, overlays it after the loop: nWaves >= 5)
-  return b + 16;
-}
-// waves of the workgroup that take part in the list loop of a barcode with n ranks: as many as have room for a private
-// histogram in what the fixed part leaves of `budget` (0 = does not fit)
-constexpr u32 MIN_HIST_WAVES = 5;
-constexpr u32 RANKED_FIRST_PER_RANK = 6;                    // ranked placement: first[] entries budgeted per rank when a block is classified
-                                                           // (3-7 barcodes present per rank on the synthetic sets); the kernel then takes
-                                                           // whatever the budget leaves, and a block that still overflows is re-run with
-                                                           // first[] on an HBM slot
-__host__ __device__ inline u32 rankedFirstEstimate(u32 nBarcodes, u32 n) { const u64 e = (u64)RANKED_FIRST_PER_RANK * n; return e < nBarcodes ? (u32)e : nBarcodes; }
-// … and, where the entries of the block's lists are known (classification): a seventh of them (6-8 % on the yeast-like
-// sets, more on deeper ones), whichever is larger. Erring low is cheap: the ranked kernel knows the true number right
-// after its bitmap pass and hands the block on before the list loop.
-__host__ __device__ inline u32 rankedFirstEstimateE(u32 nBarcodes, u32 n, u32 entries, u32 div = 7) { const u32 a = rankedFirstEstimate(nBarcodes, n), b = entries / div; const u32 m = a > b ? a : b; return m < nBarcodes ? m : nBarcodes; }
-__host__ __device__ inline u32 histWaves(u32 nFirst, u32 n, u32 maxWaves, u32 bmWords, size_t budget) {
-  const size_t fixed = workBytes(nFirst, n, 0, bmWords), per = (((size_t)n + 3) / 4) * 4;
-  if (fixed + MIN_HIST_WAVES * per > budget) return 0;
-  const size_t wv = (budget - fixed) / (per ? per : 1);
-  return wv < maxWaves ? (u32)wv : maxWaves;
-}
 __device__ inline Work carve(unsigned char *base, u32 nFirst, u32 n, u32 bmWords = 0) {
   Work w; size_t o = 0;
   w.first = (u16 *)(base + o); o += pad16((size_t)nFirst * 2);
@@ -415,9 +138,6 @@ struct FirstRanked {
 // (home bucket, tag) of barcode cj: x = the b scrambled bits of cj at the top of a word (b = bits of the data set's barcode
 // count), home = floor(x NB / 2^32) (one v_mul_hi), tag = the top bits of the fraction (x NB mod 2^32) — barcodes of one home
 // bucket are consecutive x, their fractions NB apart, so b - floor(log2 NB) <= 10 bits of it tell them apart.
-constexpr u32 TR_QUEUE = 16384;                              // entries of a wave's queue in pass A (8 bytes each, behind the handles on the workgroup's HBM slot)
-constexpr u32 TR_MIN_SLOTS = 1024;                             // tables are not made smaller than this
-constexpr u32 TR_MAX_SLOTS = 65532;                          // handles are 16 bits; slot S (<= 65532) is the handle of "no entry" and reads unseen
 struct SlotTable {
   u32 *tab; u32 NB /* buckets */, xsh /* 32 - b */, tsh; u32 *ovf; u32 hbase /* handle of the table's slot 0 */;
   u32 base3;                                                 // the table's LDS byte address (probeHome; 0 = the table is not in LDS), kept in a scalar register
@@ -506,53 +226,12 @@ struct FirstSlots {                                          // pass B: first[] 
   __device__ __forceinline__ u32 lookup(u32 h) const { return peek(h); }
   __device__ __forceinline__ u32 entry(const void *row, u32 j, u32) const { return peek(((const u16 *)row)[j]); }   // row: the list's handles
 };
-// slots of a block's table and what pass B then looks like: S = 0 if the block does not fit `budget`. The table gets every byte
-// pass A can give it (the emptier, the shorter the probes) but no more than twice the entries of the block's lists — a table at
-// most half full cannot overflow — and no more than pass B can keep at 2 bytes per slot beside root[] and five histograms.
-// S2: slots of a SECOND table, should the first fill up (only then: it is "closed" at 7/8 and the barcodes that turn up afterwards
-// are parked): it lives in the half of the first table's LDS that the compaction of its ranks frees, as far as pass B then still
-// has room for 2 bytes per slot of both. 0 = none (the first table holds every barcode the lists can bring, or nothing is left).
-__host__ __device__ inline void translatedShape(u32 n, u32 maxWaves, size_t budget, u32 minSlots, u32 entries, u32 nBarcodes, u32 cap /* test knob */,
-                                                u32 &S, u32 &S2, u32 &nW, bool &compact) {
-  const size_t per = (((size_t)n + 3) / 4) * 4, fixedB = pad16((size_t)n * 2) + 64;
-  S = 0; S2 = 0; nW = 0; compact = false;
-  if (fixedB + MIN_HIST_WAVES * per + 2 * 256 + 64 >= budget) return;
-  const size_t sA = (budget - 64) / 4, sB = (budget - fixedB - MIN_HIST_WAVES * per) / 2 - 16;
-  size_t s = sA < sB ? sA : sB;
-  if (s > TR_MAX_SLOTS) s = TR_MAX_SLOTS;
-  size_t useful = 2 * (size_t)(entries < nBarcodes ? entries : nBarcodes) + 64;
-  if (useful < TR_MIN_SLOTS) useful = TR_MIN_SLOTS;
-  if (useful < minSlots) useful = minSlots;                  // (the tag's width asks for this many: a block with few entries still gets them)
-  const bool all = s >= useful;                              // holds whatever the lists bring
-  if (all) s = useful;
-  if (cap && s > cap) s = cap;
-  s &= ~(size_t)3;
-  if (s < 64 || s < minSlots) return;                        // (16 buckets at least: the probe stride is below that)
-  S = (u32)s;
-  if (!all || cap) {
-    const long a2 = ((long)budget - (long)pad16(2 * (s + 8)) - 64) / 4, b2 = ((long)budget - (long)fixedB - (long)(MIN_HIST_WAVES * per) - 2 * (long)(s + 8) - 64) / 2;
-    long s2 = a2 < b2 ? a2 : b2;
-    if (s2 > (long)TR_MAX_SLOTS - (long)s - 4) s2 = (long)TR_MAX_SLOTS - (long)s - 4;
-    if (cap && s2 > (long)cap) s2 = (long)cap;
-    s2 &= ~3L;
-    if (s2 >= 64 && s2 >= (long)minSlots) S2 = (u32)s2;
-  }
-  if (pad16(4 * (s + 4)) + fixedB + (size_t)maxWaves * per <= budget) { nW = maxWaves; return; }   // the table stays as it is: every wave has its histogram anyway
-  compact = true;
-  const size_t wv = (budget - fixedB - pad16(2 * (s + 8))) / (per ? per : 1);
-  nW = wv < maxWaves ? (u32)wv : maxWaves;
-}
+
 __host__ __device__ inline u32 translatedCloseAt(u32 S, u32 S2) { return S2 ? S - S / 8 : 0xFFFFFFFFu; }   // inserts into the first table stop here when there is a second one
 // list-loop waves of pass B when both tables are in use
 __host__ __device__ inline u32 translatedWaves2(u32 n, u32 maxWaves, size_t budget, u32 S, u32 S2) {
   const size_t per = (((size_t)n + 3) / 4) * 4, fixedB = pad16((size_t)n * 2) + 64, wv = (budget - fixedB - pad16(2 * ((size_t)S + S2 + 16))) / (per ? per : 1);
   return wv < maxWaves ? (u32)wv : maxWaves;
-}
-__host__ __device__ inline bool translatedFits(u32 S, u32 S2, u32 est, u32 entries, u32 nBarcodes) {      // classification: do the tables hold the barcodes expected in the block's lists?
-  if (!S) return false;
-  if ((size_t)S >= 2 * (size_t)(entries < nBarcodes ? entries : nBarcodes)) return true;
-  const size_t capacity = S2 ? (size_t)(S - S / 8) + (S2 - S2 / 8) : (size_t)S - S / 8;
-  return capacity >= (size_t)est + est / 8;
 }
 
 // wave64 max in registers: DPP row shifts (1,2,4,8) then row broadcasts 15/31 (gfx9 DPP), result in lane 63.
@@ -798,11 +477,11 @@ template <int CL_THREADS> __device__ __forceinline__ bool dense_first_wide(const
   const u32 nW = histWaves(a.nBlocksFirst, n, CL_THREADS / WAVE, 0, a.ldsBudget), nW4 = histWaves(2 * a.nBlocksFirst, n, CL_THREADS / WAVE, 0, a.ldsBudget);
   return nW4 >= nW || (a.narrowFirst >= 2 && nW4 >= a.narrowFirst);   // (A/B: accept down to narrowFirst waves)
 }
-template <bool IN_LDS, int FIRST_MODE /* 0 dense in LDS, 1 ranked in LDS, 2 dense on an HBM slot, 3 hashed in LDS */, int CL_THREADS, int KLASS, bool WIDE = false /* dense in LDS: 4-byte entries (dense_first_wide) */>
+template <bool IN_LDS, int FIRST_MODE /* 0 dense in LDS, 1 ranked in LDS, 2 dense on an HBM slot */, int CL_THREADS, int KLASS, bool WIDE = false /* dense in LDS: 4-byte entries (dense_first_wide) */>
 __device__ __forceinline__ void cluster_one_block(const ClusterArgs &a, u32 code, unsigned char *region, u16 *firstGlobal, u32 *sh /* small shared ints */, WorkAcc &acc) {   // code: local block number
   constexpr int CL_WAVES = CL_THREADS / WAVE;
   // lists a wave keeps in flight: 4, but 2 where the kernel must stay within 64 VGPRs (two workgroups per CU) AND carries
-  // the ranked / hashed lookup: fewer registers spilled is worth more there than the deeper prefetch (8x set: 52.8 -> 41.4 ms);
+  // the ranked lookup: fewer registers spilled is worth more there than the deeper prefetch (8x set: 52.8 -> 41.4 ms);
   constexpr int RIF = (KLASS == 0 && CL_THREADS == 1024 && FIRST_MODE == 1) ? 2 : ROWS_IN_FLIGHT;
   const int tid = threadIdx.x, lane = tid & (WAVE - 1), wave = tid / WAVE;
   code = (u32)__builtin_amdgcn_readfirstlane((int)code);     // (the block number reaches every lane through LDS: say that it is uniform)
@@ -1776,7 +1455,7 @@ __device__ __forceinline__ void cluster_one_block_tp(const ClusterArgs &a, u32 c
   {
     // the first table, four entries per lane and step (round 6): 16-byte reads, 8-byte writes, rounds of 3 x 1024 x 4 entries with ONE barrier each — two rounds for the
     // largest table — where a word at a time took a barrier per 4096 entries and five times the LDS instructions; the phase is workgroup-synchronous (nobody to hide its
-    // latencies behind but the CU's other workgroup): this and the 16-byte clears took the 3 Gb set's cluster time from 285 to ... ms. Round r writes bytes
+    // latencies behind but the CU's other workgroup): this and the 16-byte clears took the 3 Gb set's cluster time from 285 to 274 ms. Round r writes bytes
     // [r * 24 K, (r + 1) * 24 K), which lie inside what rounds <= r have read (every round's reads are behind a barrier before the next round writes).
     const u32 noneWord = tab[S];                             // (the word of handle `none`, index S: read before anything is overwritten — S >= 64, so it is not in round 0's writes... kept by every lane, written by one)
     const uint4 *const src4 = (const uint4 *)tab; uint2 *const dst2 = (uint2 *)region; const u32 count4 = S / 4;
@@ -2098,20 +1777,21 @@ void cluster_kernel(ClusterArgs a) {
   if (threadIdx.x == 0 && accS[2]) { atomicAdd((u64 *)&a.stats[0], (u64)accS[0]); atomicAdd((u64 *)&a.stats[1], (u64)accS[3]); atomicAdd((u64 *)&a.stats[2], (u64)accS[1]); atomicAdd((u64 *)&a.stats[3], (u64)accS[2]); }
 }
 
-// ---- list descriptors: per good hash of a block, in rank order, where its barcode list starts in rows[] and how long it is.
-// Built once per --hashDepthRange (after the list exchange of a sharded run), read by every --cluster that follows: the
-// cluster kernel used to fetch them per barcode through three dependent gathers (position -> hash index -> offset, depth)
-// into LDS arrays of 6 bytes per rank.
-__global__ __launch_bounds__(256)
-void good_rows_kernel(const h10x_clushash *__restrict__ ch, const u64 *__restrict__ blockOff, const u32 *__restrict__ nGood, const u16 *__restrict__ goodPos, u32 nBlocks,
-                      const u32 *__restrict__ hashDepth, const u64 *__restrict__ rowStart, u32 rowShift, u64 *__restrict__ goodRow) {
-  for (u32 c = blockIdx.x; c < nBlocks; c += gridDim.x) {
-    const u32 n = nGood[c]; const u64 o = blockOff[c];
-    for (u32 i = threadIdx.x; i < n; i += blockDim.x) {
-      const u32 x = ch[o + goodPos[o + i]].hash;
-      goodRow[o + i] = (u64)(u32)(rowStart[x] >> rowShift) | ((u64)hashDepth[x] << 32);
-    }
-  }
+// ---- the launches (see cluster.hpp): the 22 instantiations below and no others — five placements in the half-CU class at three workgroup sizes and in the
+// whole-CU class, the last resort behind both (first[] on an HBM slot, KLASS 3), and the HBM-scratch form (no dynamic LDS, hence no attribute call)
+using LaunchFn = int (*)(Ctx *, size_t, u32, hipStream_t, const ClusterArgs &);
+template <bool IN_LDS, int MODE, int THREADS, int K> static int launch_one(Ctx *c, size_t ldsBytes, u32 grid, hipStream_t st, const ClusterArgs &g) {
+  if (IN_LDS) H10X_HIP(c, hipFuncSetAttribute((const void *)cluster_kernel<IN_LDS, MODE, THREADS, K>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsBytes));
+  cluster_kernel<IN_LDS, MODE, THREADS, K><<<grid, THREADS, ldsBytes, st>>>(g); return 0;
+}
+template <int MODE> static LaunchFn lds_form(int klass, int lanes) {
+  return klass == 2 ? (lanes == 1024 ? &launch_one<true, MODE, 1024, 2> : nullptr) : klass != 0 ? nullptr : lanes == 512 ? &launch_one<true, MODE, 512, 0> : lanes == 768 ? &launch_one<true, MODE, 768, 0> : lanes == 1024 ? &launch_one<true, MODE, 1024, 0> : nullptr;
+}
+int stageC_launchCluster(Ctx *c, int placement, int klass, int lanes, size_t ldsBytes, u32 grid, hipStream_t st, const ClusterArgs &g) {
+  const LaunchFn f = !ldsBytes ? (placement == 2 && klass == 0 && lanes == 1024 ? &launch_one<false, 2, 1024, 0> : nullptr)
+                   : placement == 2 && klass == 3 && lanes == 1024 ? &launch_one<true, 2, 1024, 3>
+                   : placement == 0 ? lds_form<0>(klass, lanes) : placement == 1 ? lds_form<1>(klass, lanes) : placement == 2 ? lds_form<2>(klass, lanes) : placement == 4 ? lds_form<4>(klass, lanes) : placement == 5 ? lds_form<5>(klass, lanes) : nullptr;
+  return f ? f(c, ldsBytes, grid, st, g) : c->fail("no cluster kernel for placement %d in class %d with %d lanes and %zu bytes of LDS", placement, klass, lanes, ldsBytes);
 }
 
 // ---- (c) the order-dependent part of hash10x.c:807-822, restated without a serial walk, from the msBest column the list
@@ -2249,7 +1929,6 @@ void replay_kernel(ReplayArgs a) {
 }
 #undef SYNC
 __host__ __device__ inline size_t replayBytes(u32 n) { return 4 * (((size_t)n * 2 + 15) & ~(size_t)15) + 16; }
-constexpr u32 REPLAY_SMALL = 2040, REPLAY_MID = 16376;       // rank counts up to which a block's replay runs in 16 KB / 128 KB of LDS
 
 // ---- (e) pointToMin = the terms added in rank order (hash10x.c:821): a serial fp64 chain per barcode. One WAVE per
 // barcode: 64 terms per coalesced load, added in order through readlane (the chain costs one v_add_f64 latency per
@@ -2362,318 +2041,32 @@ void read_merge_kernel(h10x_block *__restrict__ blocks, const u64 *__restrict__ 
 #undef H10X_FOR_ENTRIES
 }
 
-// launch classes by working-set size: 0 = half a CU's LDS (barcodes with many ranks run their list loop on fewer waves:
-// histWaves), 2 = the whole LDS of a CU, 3 = HBM scratch (class 1 is no longer used)
-__global__ void cluster_classify_kernel(const h10x_block *__restrict__ blocks, const u32 *__restrict__ nGood, const u32 *__restrict__ entries, u32 codeMin, u32 codeMax,
-                                        u32 nBlocks /* LDS entries of first[] (ranked, hashed: barcodes of the data set) */, int ranked /* 1 ranked, 3 translated */, u32 hashMinSlots, u32 maxTrRanks, u32 firstCap, u32 bmWords, u32 waves0, size_t budget0, size_t budgetSmall, size_t budgetBig, u32 bigRanks, u32 estDiv /* translated placement: a block's barcodes are taken to be this fraction of its list entries */,
-                                        u32 *__restrict__ list0, u32 *__restrict__ list1, u32 *__restrict__ list2, u32 *__restrict__ list3,
-                                        u32 *__restrict__ listBig /* blocks with more ranks than the small replay class holds: counts[9] */, u32 *__restrict__ counts, unsigned long long *__restrict__ work) {
-  const u32 c = codeMin + blockIdx.x * blockDim.x + threadIdx.x;
-  const int lane = threadIdx.x & (WAVE - 1);
-  const u32 n = c < codeMax ? nGood[c] : 0;
-  int cls = -1; u32 nRead = 0;
-  if (n) {
-    nRead = blocks[c].nRead;
-    if (ranked == 3) {                             // translated placement: the table of pass A must hold the barcodes expected in the block's lists
-      u32 S, S2, nW; bool compact;
-      translatedShape(n, waves0, budget0, hashMinSlots, entries[c], nBlocks, firstCap, S, S2, nW, compact);
-      if (n > maxTrRanks) cls = 3;                       // (its handles would not fit the workgroup's HBM slot)
-      // (a sixth of the entries, not a seventh as in the ranked placement: the blocks in between would run in the half-CU class on a second table and
-      //  with few list-loop waves — they are faster with a CU to themselves: full configs[2] 583 -> 567 ms, 17 % of the blocks in the whole-CU class
-      //  instead of 8 %; at a fifth the whole-CU class holds more than half of the CUs and the launches no longer overlap: 890 ms)
-      else if (translatedFits(S, S2, rankedFirstEstimateE(nBlocks, n, entries[c], estDiv), entries[c], nBlocks)) cls = 0;
-      else { translatedShape(n, CL_THREADS_HUGE / WAVE, budgetBig, hashMinSlots, entries[c], nBlocks, firstCap, S, S2, nW, compact); cls = S ? 2 : 3; }
-    }
-    else if (histWaves(ranked ? rankedFirstEstimateE(nBlocks, n, entries[c]) : nBlocks, n, waves0, bmWords, budget0)) cls = 0;
-    else if (histWaves(ranked ? rankedFirstEstimate(nBlocks, n) : nBlocks, n, CL_THREADS_HUGE / WAVE, bmWords, budgetBig)) cls = 2;
-    else cls = 3;
-  }
-  // the largest barcodes of the main class go to the front of its work queue (list1, handed out before list0): the launch
-  // then does not end on a workgroup that drew a big one last. (Ordering the WHOLE queue by size was measured 17 % slower:
-  // like-sized workgroups run their phases in step.)
-  if (cls == 0 && n > bigRanks) cls = 1;
-  for (int s = 32; s; s >>= 1) nRead = max(nRead, (u32)__shfl_xor((int)nRead, s));
-  if (lane == 0 && nRead) atomicMax(&counts[8], nRead);
-  {                                                          // most ranks of a block per LDS class: the translated placement sizes its handle slots by them
-    u32 n0 = (cls == 0 || cls == 1) ? n : 0u, n2 = cls == 2 ? n : 0u;
-    for (int s = 32; s; s >>= 1) { n0 = max(n0, (u32)__shfl_xor((int)n0, s)); n2 = max(n2, (u32)__shfl_xor((int)n2, s)); }
-    if (lane == 0) { if (n0) atomicMax(&counts[12], n0); if (n2) atomicMax(&counts[13], n2); }
-  }
-  if (work) {                                            // work of the half-CU classes and of the whole-CU class (list entries + a charge per rank): the launches split the CUs by it
-    unsigned long long w0 = (cls == 0 || cls == 1) ? (unsigned long long)entries[c] + 64ull * n : 0ull, w2 = cls == 2 ? (unsigned long long)entries[c] + 64ull * n : 0ull;
-    for (int s = 32; s; s >>= 1) { w0 += __shfl_xor(w0, s); w2 += __shfl_xor(w2, s); }
-    if (lane == 0) { if (w0) atomicAdd(&work[0], w0); if (w2) atomicAdd(&work[1], w2); }
-  }
-  {
-    const u64 bal = __ballot(n > REPLAY_SMALL);
-    if (bal) {
-      u32 base = 0;
-      if (lane == 0) base = atomicAdd(&counts[9], (u32)__popcll(bal));
-      base = (u32)__shfl((int)base, 0);
-      if (n > REPLAY_SMALL) listBig[base + (u32)__popcll(bal & ((1ULL << lane) - 1))] = c;
-    }
-  }
-  u32 *const lists[4] = {list0, list1, list2, list3};
-#pragma unroll
-  for (int k = 0; k < 4; ++k) {                              // one atomic per wave and class
-    const u64 bal = __ballot(cls == k);
-    if (!bal) continue;
-    u32 base = 0;
-    if (lane == 0) base = atomicAdd(&counts[k], (u32)__popcll(bal));
-    base = (u32)__shfl((int)base, 0);
-    if (cls == k) lists[k][base + (u32)__popcll(bal & ((1ULL << lane) - 1))] = c;
-  }
-}
-
-// one contiguous range of LOCAL block numbers; `more` = a further range of the same command has run before (counters add up)
-static int cluster_local_range(Ctx *c, int codeMin, int codeMax, int threshold, bool more) {
-  hipStream_t st = c->stream;
-  const u32 nGlobal = c->sharded ? c->nBlocksGlobal : c->nBlocks;
-  c->tstart(T_CLUSTER);
-  const u32 span = (u32)(codeMax - codeMin);
-  DevBuf<u32> list0, list1, list2, list3, listBig; DevBuf<u64> zeroed; DevBuf<u64> term;
-  H10X_HIP(c, list0.alloc(span)); H10X_HIP(c, list1.alloc(span)); H10X_HIP(c, list2.alloc(span)); H10X_HIP(c, list3.alloc(span)); H10X_HIP(c, listBig.alloc(span));
-  // every small counter of the command in one buffer, cleared by one memset: counts[0..3] class sizes, [4] [6] [7] work
-  // queue positions, [8] largest nRead, [10] [11] overflowed blocks (lists A, B); stats[0..7] the work counters
-  H10X_HIP(c, zeroed.alloc(8 + 8 + 2)); H10X_HIP(c, term.alloc(c->nEntries));   // (+ work of the half-CU and the whole-CU classes)
-  H10X_HIP(c, hipMemsetAsync(zeroed.p, 0, (8 + 8 + 2) * 8, st));
-  struct { u32 *p; } counts{(u32 *)zeroed.p}; struct { u64 *p; } stats{zeroed.p + 8};   // counts[12] [13]: most ranks of a block in the half-CU classes / the whole-CU class (sizes the handle slots)
-  const size_t budgetSmall = c->optClusterLds > 0 ? (size_t)c->optClusterLds : 80 * 1024 - 1024;
-  const size_t budgetBig = c->optClusterLds > 0 ? (size_t)c->optClusterLds : 160 * 1024 - 1024;
-  const int threads0 = c->optClusterThreads0 == 512 ? 512 : (c->optClusterThreads0 == 768 ? 768 : 1024);   // tuning knobs for class 0
-  const size_t budget0 = c->optClusterLds > 0 ? (size_t)c->optClusterLds : (c->optClusterBudget0 > 0 ? (size_t)c->optClusterBudget0 : budgetSmall);
-  // Placement of first[] (FirstDense / FirstRanked / SlotTable + FirstSlots): dense in LDS while 2 B per barcode of the data set is
-  // small; ranked in LDS while the presence bitmap + prefix (3/16 B per barcode) leaves room for the rest; translated (handles
-  // into a table in LDS) up to 2^22 barcodes (beyond that the 10-bit tag needs more slots than LDS has); dense on a per-workgroup
-  // HBM slot (L2/MALL resident, atomics + L1-bypassing loads) as the last resort and for blocks whose LDS tables filled up twice.
-  const u32 bmWordsAll = (nGlobal + 31) / 32;
-  int hashBits = 1; while (hashBits < 32 && (1ull << hashBits) < (unsigned long long)nGlobal) ++hashBits;
-  const u32 hashMinSlots = hashBits > 10 ? 4u << (hashBits - 10) : 0u;       // 10-bit tag: buckets >= 2^(b-10)
-  // The ranked form reads the lists twice but needs no probing (100 k-barcode set: 39 ms against 56 translated), so it is TRIED wherever the
-  // bitmap + prefix leave the whole-CU class any room (up to 100 KB of them: 546 k barcodes) and kept unless the classification then
-  // sends more than a few blocks to the HBM-scratch class; up to 48 KB (262 k barcodes) it is taken as before.
-  const bool rankedSure = (size_t)bmWordsAll * 6 <= 48 * 1024, rankedTry = !rankedSure && (size_t)bmWordsAll * 6 <= 100 * 1024 && hashBits <= 22;
-  int firstMode = (size_t)nGlobal * 2 <= 48 * 1024 ? 0 : (rankedSure || rankedTry ? 1 : (hashBits <= 22 ? 4 : 2));
-  if (c->optFirstGlobal == 1) firstMode = 2; else if (c->optFirstGlobal == 2) firstMode = 1;                                          // test knobs
-  else if ((c->optFirstGlobal == 3 || c->optFirstGlobal == 4) && hashBits <= 22) firstMode = 4;                                        // (3: round 3's one-pass hashed table, replaced by the translated placement)
-  // translated placement: u16 per list on a workgroup's handle slot (a multiple of 64 that holds the longest list), ranks per slot
-  u32 hStride = 64; while (hStride < c->maxGoodDepth && hStride < (1u << 24)) hStride <<= 1;   // (a power of two: a handle's position tells its rank)
-  const size_t trSlotCapBytes = (size_t)32 << 20;
-  const u32 maxTrRanks = (u32)hmin<size_t>(0xFFFFFFFFu, trSlotCapBytes / ((size_t)hStride * 2));
-  const bool packed = c->optTrPacked != 0;                   // translated placement: the packed form (several lists per wave instruction, round 5) unless the knob says 0
-  // a workgroup's handle slot: the handles of its largest block (ranks x the slot's list stride; + 256: the packed form's class regions start at multiples of 64), then the waves' queues.
-  // Sized per launch class by the largest block THAT class holds and by its waves (round 4 took the context's largest block and 16 waves for every class: tens of GB on sets
-  // with a few giant barcodes that never run here); blocks handed on by the half-CU class run in the whole-CU class, whose slots therefore cover both
-  auto trSlotFor = [&](u32 maxRanks, u32 waves) { return (size_t)hmin<u32>(hmax<u32>(maxRanks, 1u), maxTrRanks) * hStride + 256 + (size_t)waves * TR_QUEUE * 4; };
-  const u32 firstCap = c->optFirstCap > 0 ? (u32)c->optFirstCap : 0u;      // test knob only
-  u32 hc[14]; u64 hw[2] = {0, 0}; u32 nFirstLds = 0, bmWords = 0;
-  for (int attempt = 0; attempt < 2; ++attempt) {
-    nFirstLds = firstMode == 0 ? nGlobal : 0;
-    bmWords = firstMode == 1 ? bmWordsAll : 0;
-    cluster_classify_kernel<<<divUp(span, 256), 256, 0, st>>>(c->blocks.p, c->nGood.p, c->goodEntries.p, (u32)codeMin, (u32)codeMax,
-                                                            firstMode == 1 || firstMode >= 3 ? nGlobal : nFirstLds, firstMode == 1 ? 1 : (firstMode == 4 ? 3 : 0), hashMinSlots, maxTrRanks, firstCap,
-                                                            bmWords, (u32)threads0 / WAVE, budget0, budgetSmall, budgetBig, c->optBigRanks > 0 ? (u32)c->optBigRanks : c->meanGood + c->meanGood / 2, c->optTrEstDiv > 0 ? (u32)c->optTrEstDiv : 6u,
-                                                            list0.p, list1.p, list2.p, list3.p, listBig.p, counts.p, (unsigned long long *)(zeroed.p + 16));
-    H10X_TRY(c->readback(hc, counts.p, 56));
-    H10X_TRY(c->readback(hw, zeroed.p + 16, 16));
-    H10X_TRY(c->syncReadbacks());
-    const u32 classified = hc[0] + hc[1] + hc[2] + hc[3];
-    if (attempt || !rankedTry || c->optFirstGlobal || firstMode != 1 || hc[3] <= 16 + classified / 200) break;
-    firstMode = 4;                                           // too many blocks without room beside the bitmap: the translated placement after all
-    H10X_HIP(c, hipMemsetAsync(counts.p, 0, 16, st));        // the four class sizes
-    H10X_HIP(c, hipMemsetAsync(counts.p + 9, 0, 4, st));
-    H10X_HIP(c, hipMemsetAsync(zeroed.p + 16, 0, 16, st));
-    H10X_HIP(c, hipMemsetAsync(counts.p + 12, 0, 8, st));
-  }
-  // (the work queue hands barcodes out in the order the classification appended them, i.e. mixed sizes: sorting the
-  // queue by descending rank count was measured 17 % SLOWER — workgroups of like size run their phases in step and
-  // contend for the same unit at the same time)
-  ClusterArgs a{};
-  a.blocks = c->blocks.p; a.blockOff = c->blockOff.p; a.clusHash = c->clusHash.p; a.goodPos = c->goodPos.p; a.nGood = c->nGood.p;
-  a.goodRow = c->goodRow.p; a.rows = c->rows.p; a.nBlocks = c->nBlocks; a.threshold = threshold;
-  a.segs = c->segs; a.nBlocksFirst = nGlobal; a.rowShift = (u32)c->rowShift;
-  if (c->sharded && c->optRowsFakeBase) a.rows = c->rows.p - (size_t)c->optRowsFakeBase;   // test knob: rowStart[] carries the same offset (shard_exchangeRows)
-  a.narrowFirst = (u32)c->optNarrowFirst; a.tpClassT = c->optTrClassT != 0 ? 1u : 0u;
-  a.maxGood = c->maxGood; a.stats = stats.p; a.res = term.p; a.entries = c->goodEntries.p;
-  a.firstCap = firstCap; a.hashMinSlots = hashMinSlots;
-  a.hashBits = (u32)hashBits; a.hStride = hStride;
-  const size_t trStride[3] = {trSlotFor(hc[12], (u32)threads0 / WAVE), trSlotFor(hmax<u32>(hc[12], hc[13]), CL_THREADS_HUGE / WAVE), trSlotFor(hmax<u32>(hc[12], hc[13]), CL_THREADS_HUGE / WAVE)};   // [1]: the whole-CU class's second launch
-  // ranked / hashed placement: blocks whose table was too small are re-run — those of the half-CU class (list A) with the
-  // whole LDS of a CU, those that fail there as well (list B) with first[] dense on an HBM slot
-  DevBuf<u32> ovfA, ovfB; H10X_HIP(c, ovfA.alloc(span)); H10X_HIP(c, ovfB.alloc(span));
-  u32 *const ovfCountA = counts.p + 10, *const ovfCountB = counts.p + 11;
-  DevBuf<u64> phase;
-  if (c->optStamps) { H10X_HIP(c, phase.alloc(8)); H10X_HIP(c, hipMemsetAsync(phase.p, 0, 64, st)); a.phase = phase.p; }
-  // HBM working set per workgroup (class 3): first[] + per-rank arrays for the largest barcode
-  DevBuf<unsigned char> scratch;
-  size_t stride = 0; u32 grid3 = 0;
-  if (hc[3]) {
-    stride = (workBytes(nGlobal, c->maxGood, CL_THREADS_SMALL / WAVE, 0) + 255) & ~(size_t)255;
-    grid3 = hmin<u32>(hc[3], (u32)c->numCU);
-    H10X_HIP(c, scratch.alloc(stride * grid3));
-    H10X_HIP(c, hipMemsetAsync(scratch.p, 0xFF, stride * grid3, st));    // first[] = unseen everywhere
-  }
-  // hybrid placement: one first[] slot per resident workgroup of each LDS class
-  DevBuf<unsigned char> firstSlots[3];
-  const size_t firstStride = (((size_t)nGlobal * 2 + 255) & ~(size_t)255);
-  u32 gridOf[3] = {hmin<u32>(hc[0] + hc[1], (u32)c->numCU * (u32)hmax<size_t>(1, (160 * 1024) / (budget0 + 1024))), hmin<u32>(hc[1], (u32)c->numCU * 2), hmin<u32>(hc[2], (u32)c->numCU)};   // class 1 unused
-  // Both LDS classes are persistent launches that stay on the CUs they get: a whole-CU workgroup keeps two half-CU workgroups out. Where both have
-  // enough blocks to fill the chip, the CUs are split by the classes' work (the whole-CU class does a list entry at ~0.8 x the rate per CU: measured
-  // on the million-barcode set, where it used to finish 100 ms behind the main launch), so that the two launches end together.
-  u32 secondWind = 0;
-  if (firstMode == 4 && gridOf[2] && gridOf[0] >= (u32)c->numCU && hw[0] + hw[1]) {
-    const double share2 = 1.25 * (double)hw[1] / (1.25 * (double)hw[1] + (double)hw[0]);
-    // (+ 4 CUs: the blocks of that class are the ones with many ranks, which the work figure flatters; its CUs are not lost when it ends early —
-    // while it is the smaller side, the main launch brings two workgroups for EVERY CU, and those that find no room wait in the dispatcher
-    // for the whole-CU workgroups to leave: 3 Gb set, 2 169 such blocks: 657 ms on one CU behind a main launch of 510 ms before this)
-    // Whichever side the split errs on corrects itself: the main launch always brings two workgroups for every CU (they take over the whole-CU class's
-    // CUs when that ends first), and behind the main launch, on its stream, the whole-CU class is launched a SECOND time on the same work queue
-    // (secondWind): workgroups for every CU, which find the queue empty — or the CUs the main launch has just left free. (Before this the main launch
-    // was held to the CUs the split gave it once the whole-CU class had more than half of them: 890 ms instead of 570 on a set classified that way.)
-    // (round 6: never fewer than an eighth of the CUs, 32 of 256, while the class has the blocks: where it is a side show — 2 169 blocks of the 3 Gb set, ~130 of a rank's
-    // eighth of it — five CUs made it a 2 ms tail whenever the two launches do not run side by side, e.g. when their streams share a hardware queue (seen with eight ranks'
-    // forty streams in one process: the rank's --cluster 19.5 instead of 17.4 ms); with 32 CUs it is done in 0.3 ms, and the main launch's workgroups take the CUs over)
-    const u32 cu2 = hmin<u32>((u32)c->numCU > 16 ? (u32)c->numCU - 8 : (u32)c->numCU - 1, hmax<u32>(hmax<u32>(1u, (u32)c->numCU / 8u), (u32)(share2 * c->numCU + 0.5) + 4u));
-    gridOf[2] = hmin<u32>(hc[2], cu2);
-    gridOf[0] = hmin<u32>(gridOf[0], 2 * (u32)c->numCU);
-    secondWind = hc[2] > gridOf[2] ? hmin<u32>(hc[2] - gridOf[2], (u32)c->numCU) : 0u;
-  }
-  DevBuf<u16> trSlots[3];                                  // translated placement: one handle slot per resident workgroup of each LDS class
-  // (no room for a class's slots: fewer workgroups — down to one — before giving up; the launches are persistent, a smaller grid is only slower)
-  auto trAlloc = [&](int k, u32 &grid) -> int {
-    for (;;) {
-      if (trSlots[k].alloc(trStride[k] * grid) == hipSuccess) return 0;
-      (void)hipGetLastError();
-      if (grid <= 1) return c->fail("no device memory for the handle slots of the cluster kernel (%.1f MB per workgroup)", trStride[k] * 2 / 1e6);
-      grid = (grid + 1) / 2;
-    }
-  };
-  if (firstMode == 4) for (int k = 0; k < 3; k += 2) if (gridOf[k]) H10X_TRY(trAlloc(k, gridOf[k]));
-  if (secondWind) H10X_TRY(trAlloc(1, secondWind));
-  if (firstMode == 2) for (int k = 0; k < 3; k += 2) if (gridOf[k]) {       // class 0 serves list 0 AND the front list (hc[1]); class 1 has no launch
-    H10X_HIP(c, firstSlots[k].alloc(firstStride * gridOf[k]));
-    H10X_HIP(c, hipMemsetAsync(firstSlots[k].p, 0xFF, firstStride * gridOf[k], st));
-  }
-  // The classes are independent: fork them onto side streams so that the few largest barcodes (long, low
-  // parallelism) run beside the many small ones instead of in front of them. Every buffer they touch was
-  // allocated before the fork and is released after the join, which is what the block cache requires.
-  // a failure between here and the join must not let the buffers above go back to the block cache while a side stream
-  // still runs a kernel on them (the cache orders reuse within ONE stream only)
-  ForkGuard forkGuard(c);
-  c->tstart(T_CLUSTER_K);
-  H10X_TRY(c->forkStreams(3));
-  if (hc[3]) {
-    ClusterArgs g = a; g.list = list3.p; g.nList = hc[3]; g.workCounter = counts.p + 7; g.scratch = scratch.p; g.scratchStride = stride;
-    cluster_kernel<false, 2, CL_THREADS_SMALL><<<grid3, CL_THREADS_SMALL, 0, c->aux[0]>>>(g);
-  }
-#define H10X_LAUNCH_ONE(MODE, K, THREADS, BUDGET, GRID, STREAM)                                                                    \
-      { H10X_HIP(c, hipFuncSetAttribute((const void *)cluster_kernel<true, MODE, THREADS, K>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(BUDGET))); \
-        cluster_kernel<true, MODE, THREADS, K><<<GRID, THREADS, BUDGET, STREAM>>>(g); }
-#define H10X_LAUNCH_LDS(K, THREADS, BUDGET, STREAM, LIST, NLIST, GRID, CNT, OVFCNT, OVF)                                           \
-  {                                                                                                                                \
-    ClusterArgs g = a; g.list = LIST; g.nList = NLIST; g.workCounter = counts.p + CNT; g.ldsBudget = (u32)(BUDGET);                \
-    g.overflow = (OVF); g.overflowCount = (OVFCNT);                                                                                \
-    if (firstMode == 0) H10X_LAUNCH_ONE(0, K, THREADS, BUDGET, GRID, STREAM)                                                       \
-    else if (firstMode == 1) H10X_LAUNCH_ONE(1, K, THREADS, BUDGET, GRID, STREAM)                                                  \
-    else if (firstMode == 4) { g.handles = trSlots[K].p; g.handleStride = trStride[K]; if (packed) H10X_LAUNCH_ONE(5, K, THREADS, BUDGET, GRID, STREAM) else H10X_LAUNCH_ONE(4, K, THREADS, BUDGET, GRID, STREAM) } \
-    else { g.scratch = firstSlots[K].p; g.scratchStride = firstStride; H10X_LAUNCH_ONE(2, K, THREADS, BUDGET, GRID, STREAM) }      \
-  }
-  if (hc[2]) {
-    // The whole-CU class must be resident BEFORE the main launch: its workgroups need an empty CU, and once the main
-    // launch's persistent workgroups sit on every CU they only get one when those retire — the two launches then run one
-    // after the other instead of side by side (seen under rocprofv3: +0.15 ms). Its workgroups report in through pinned
-    // host words; the host holds the main launch back until they have (some 10 us), with a time limit as a safeguard.
-    if (!c->startFlags) H10X_HIP(c, hipHostMalloc((void **)&c->startFlags, 1024 * sizeof(u32), hipHostMallocDefault));
-    memset(c->startFlags, 0, 1024 * sizeof(u32));
-    // (only while that class is a side show: when it holds most of the barcodes its persistent workgroups would keep every
-    // CU to themselves until their queue is empty, and the two launches share the chip better by racing for the CUs —
-    // 1 M-barcode set: 2.20 s against 2.52 s)
-    a.started = (gridOf[2] * 2 <= (u32)c->numCU || secondWind) && gridOf[2] <= 1024 ? c->startFlags : nullptr;
-    H10X_LAUNCH_LDS(2, CL_THREADS_HUGE, budgetBig, c->aux[1], list2.p, hc[2], gridOf[2], 6, ovfCountB, ovfB.p)
-    if (a.started) {
-      const auto t0 = std::chrono::steady_clock::now();
-      for (;;) {
-        u32 up = 0;
-        for (u32 i = 0; i < gridOf[2]; ++i) up += __atomic_load_n(&c->startFlags[i], __ATOMIC_RELAXED) ? 1u : 0u;
-        if (up == gridOf[2] || std::chrono::steady_clock::now() - t0 > std::chrono::microseconds(500)) break;
-      }
-    }
-    a.started = nullptr;
-  }
-  // the main launch (class 0) counts its own work and has its own hipEvent bracket on its stream: that is the launch the
-  // roofline figure of bench.py is quoted for, and what a rocprofv3 kernel trace reports as cluster_kernel<true, *, 1024, 0>
-  if (hc[0] || hc[1]) {
-    a.stats = stats.p + 4; a.front = list1.p; a.nFront = hc[1];
-    c->tstart(T_CLUSTER_MAIN);
-    if (threads0 == 512) H10X_LAUNCH_LDS(0, 512, budget0, st, list0.p, hc[0], gridOf[0], 4, ovfCountA, ovfA.p)
-    else if (threads0 == 768) H10X_LAUNCH_LDS(0, 768, budget0, st, list0.p, hc[0], gridOf[0], 4, ovfCountA, ovfA.p)
-    else H10X_LAUNCH_LDS(0, CL_THREADS_SMALL, budget0, st, list0.p, hc[0], gridOf[0], 4, ovfCountA, ovfA.p)
-    c->tstop(T_CLUSTER_MAIN);
-    a.stats = stats.p; a.front = nullptr; a.nFront = 0;
-  }
-  if (secondWind) {                                          // (see the split above) same work queue, counters and overflow list as the first launch of the class; handle slots of its own
-    ClusterArgs g = a; g.list = list2.p; g.nList = hc[2]; g.workCounter = counts.p + 6; g.ldsBudget = (u32)budgetBig;
-    g.overflow = ovfB.p; g.overflowCount = ovfCountB; g.handles = trSlots[1].p; g.handleStride = trStride[1];
-    if (packed) H10X_LAUNCH_ONE(5, 2, CL_THREADS_HUGE, budgetBig, secondWind, st) else H10X_LAUNCH_ONE(4, 2, CL_THREADS_HUGE, budgetBig, secondWind, st)
-  }
-  H10X_HIP(c, hipGetLastError());
-  H10X_TRY(c->faultAt(4));
-  H10X_TRY(c->joinStreams(3));
-  u32 nOverflow = 0;
-  DevBuf<unsigned char> scratch2;
-  if (firstMode == 1 || firstMode == 4) {
-    u32 nA = 0, nB = 0;
-    H10X_HIP(c, hipMemcpyAsync(&nA, ovfCountA, 4, hipMemcpyDeviceToHost, st));
-    H10X_HIP(c, hipStreamSynchronize(st));
-    if (nA) {                                                // half-CU tables that were too small: again with the whole LDS of a CU
-      H10X_HIP(c, hipMemsetAsync(counts.p + 6, 0, 4, st));
-      u32 gridA = hmin<u32>(nA, (u32)c->numCU);
-      if (firstMode == 4 && trSlots[2].n < trStride[2] * gridA) H10X_TRY(trAlloc(2, gridA));
-      H10X_LAUNCH_LDS(2, CL_THREADS_HUGE, budgetBig, st, ovfA.p, nA, gridA, 6, ovfCountB, ovfB.p)
-      H10X_HIP(c, hipGetLastError());
-    }
-    H10X_HIP(c, hipMemcpyAsync(&nB, ovfCountB, 4, hipMemcpyDeviceToHost, st));
-    H10X_HIP(c, hipStreamSynchronize(st));
-    nOverflow = nA + nB;
-    if (nB) {
-      // last resort: first[] dense on a per-workgroup HBM slot and everything else in LDS (the hybrid form); a block that
-      // got this far fits the whole-CU budget without its table
-      const u32 grid = hmin<u32>(nB, (u32)c->numCU);
-      H10X_HIP(c, scratch2.alloc(firstStride * grid));
-      H10X_HIP(c, hipMemsetAsync(scratch2.p, 0xFF, firstStride * grid, st));
-      H10X_HIP(c, hipMemsetAsync(counts.p + 7, 0, 4, st));
-      ClusterArgs g = a; g.list = ovfB.p; g.nList = nB; g.workCounter = counts.p + 7; g.scratch = scratch2.p; g.scratchStride = firstStride;
-      g.ldsBudget = (u32)budgetBig;
-      H10X_HIP(c, hipFuncSetAttribute((const void *)cluster_kernel<true, 2, CL_THREADS_HUGE, 3>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)budgetBig));
-      cluster_kernel<true, 2, CL_THREADS_HUGE, 3><<<grid, CL_THREADS_HUGE, budgetBig, st>>>(g);
-      H10X_HIP(c, hipGetLastError());
-    }
-  }
-#undef H10X_LAUNCH_LDS
-#undef H10X_LAUNCH_ONE
+// ---- everything behind the main launches of blocks [codeMin, codeMax) (local numbers), queued on the context's stream and its first side stream
+int stageC_clusterTail(Ctx *c, u32 codeMin, u32 codeMax, u64 *res, const u32 *listBig, u32 nBig /* blocks with more than REPLAY_SMALL ranks */, u32 maxReads /* largest nRead of a block */) {
+  hipStream_t st = c->stream; const u32 span = codeMax - codeMin;
   // (c) labels, cluster counts and the > 255 clusters cut from the msBest column: one workgroup per barcode, classes by rank count
   DevBuf<unsigned char> replayScratch;
   {
     if (c->clusterRaw.n != 2 * (size_t)c->nBlocks) { H10X_HIP(c, c->clusterRaw.alloc(2 * (size_t)c->nBlocks)); H10X_HIP(c, hipMemsetAsync(c->clusterRaw.p, 0, 8 * (size_t)c->nBlocks, st)); }
     H10X_HIP(c, hipMemsetAsync(c->clusterRaw.p + 2 * (size_t)codeMin, 0, 8 * (size_t)span, st));   // blocks without good hashes say nothing
     ReplayArgs ra{}; ra.raw = c->clusterRaw.p; ra.blocks = c->blocks.p; ra.blockOff = c->blockOff.p; ra.clusHash = c->clusHash.p; ra.goodPos = c->goodPos.p; ra.nGood = c->nGood.p;
-    ra.res = term.p; ra.codeMin = (u32)codeMin; ra.span = span;
-    // the barcodes with more ranks than the common class holds (hc[9] of them, listed by the classification): workgroups for those only,
+    ra.res = res; ra.codeMin = codeMin; ra.span = span;
+    // the barcodes with more ranks than the common class holds (nBig of them, listed by the classification): workgroups for those only,
     // on a side stream beside the common class (disjoint blocks)
-    if (hc[9]) {
+    if (nBig) {
       H10X_TRY(c->forkStreams(1));
-      ReplayArgs rb = ra; rb.list = listBig.p; rb.span = hc[9];
+      ReplayArgs rb = ra; rb.list = listBig; rb.span = nBig;
       const size_t lds = replayBytes(hmin<u32>(REPLAY_MID, c->maxGood));
       H10X_HIP(c, hipFuncSetAttribute((const void *)replay_kernel<true, 1024>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
       rb.nLo = REPLAY_SMALL; rb.nHi = REPLAY_MID;
-      replay_kernel<true, 1024><<<hc[9], 1024, lds, c->aux[0]>>>(rb);
+      replay_kernel<true, 1024><<<nBig, 1024, lds, c->aux[0]>>>(rb);
     }
     ra.nLo = 0; ra.nHi = REPLAY_SMALL;
     replay_kernel<true, 256><<<span, 256, replayBytes(hmin<u32>(REPLAY_SMALL, hmax<u32>(c->maxGood, 1))), st>>>(ra);
-    ra.list = listBig.p; ra.span = hc[9];
-    if (hc[9]) H10X_TRY(c->joinStreams(1));
-    if (hc[9] && c->maxGood > REPLAY_MID) {
-      const u32 grid = hmin<u32>(hc[9], (u32)c->numCU);
+    ra.list = listBig; ra.span = nBig;
+    if (nBig) H10X_TRY(c->joinStreams(1));
+    if (nBig && c->maxGood > REPLAY_MID) {
+      const u32 grid = hmin<u32>(nBig, (u32)c->numCU);
       ra.scratchStride = (replayBytes(c->maxGood) + 255) & ~(size_t)255;
       H10X_HIP(c, replayScratch.alloc(ra.scratchStride * grid));
       ra.scratch = replayScratch.p; ra.nLo = REPLAY_MID; ra.nHi = 0xFFFFFFFFu;
@@ -2683,31 +2076,18 @@ static int cluster_local_range(Ctx *c, int codeMin, int codeMax, int threshold, 
   }
   // (e) the ordered sums on a side stream beside (f) the read merges: they touch disjoint fields
   H10X_TRY(c->forkStreams(1));
-  point_sum_kernel<<<divUp(span, SUM_THREADS / WAVE), SUM_THREADS, 0, c->aux[0]>>>(c->blocks.p, c->blockOff.p, c->nGood.p, (const double *)term.p, (u32)codeMin, (u32)codeMax);
+  point_sum_kernel<<<divUp(span, SUM_THREADS / WAVE), SUM_THREADS, 0, c->aux[0]>>>(c->blocks.p, c->blockOff.p, c->nGood.p, (const double *)res, codeMin, codeMax);
   {
     const size_t ldsSmall = mergeBytes(MERGE_SMALL_READS), ldsBig = mergeBytes(65536);
-    read_merge_kernel<false><<<span, MERGE_THREADS, ldsSmall, st>>>(c->blocks.p, c->blockOff.p, c->nGood.p, c->clusHash.p, (u32)codeMin);
-    if (hc[8] > MERGE_SMALL_READS) {
+    read_merge_kernel<false><<<span, MERGE_THREADS, ldsSmall, st>>>(c->blocks.p, c->blockOff.p, c->nGood.p, c->clusHash.p, codeMin);
+    if (maxReads > MERGE_SMALL_READS) {
       H10X_HIP(c, hipFuncSetAttribute((const void *)read_merge_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsBig));
-      read_merge_kernel<true><<<span, MERGE_THREADS, ldsBig, st>>>(c->blocks.p, c->blockOff.p, c->nGood.p, c->clusHash.p, (u32)codeMin);
+      read_merge_kernel<true><<<span, MERGE_THREADS, ldsBig, st>>>(c->blocks.p, c->blockOff.p, c->nGood.p, c->clusHash.p, codeMin);
     }
   }
   H10X_HIP(c, hipGetLastError());
   H10X_TRY(c->faultAt(5));
   H10X_TRY(c->joinStreams(1));
-  c->tstop(T_CLUSTER_K);
-  u64 hs[8];
-  H10X_TRY(c->readback(hs, stats.p, 64));
-  H10X_TRY(c->syncReadbacks());
-  c->tstop(T_CLUSTER);
-  if (c->optStamps) { H10X_HIP(c, hipMemcpy(c->ctr.cluster_phase_ticks, phase.p, 64, hipMemcpyDeviceToHost)); }
-  forkGuard.done();                                          // everything has been waited for
-  if (!more) { memset(c->ctr.cluster_main, 0, sizeof c->ctr.cluster_main); memset(c->ctr.cluster_class_counts, 0, sizeof c->ctr.cluster_class_counts);
-               c->ctr.sum_good = c->ctr.sum_good_depth = c->ctr.sum_hash_clustered = c->ctr.clustered_codes = c->ctr.cluster_overflow_blocks = 0; }
-  for (int k = 0; k < 4; ++k) { c->ctr.cluster_main[k] += hs[4 + k]; hs[k] += hs[4 + k]; }   // re-runs of overflowed blocks count again (they did the work twice)
-  c->ctr.sum_good += hs[0]; c->ctr.sum_good_depth += hs[1]; c->ctr.sum_hash_clustered += hs[2]; c->ctr.clustered_codes += span;
-  c->ctr.cluster_first_mode = (uint64_t)firstMode; c->ctr.cluster_overflow_blocks += nOverflow;
-  for (int k = 0; k < 4; ++k) c->ctr.cluster_class_counts[k] += hc[k];
   return 0;
 }
 
@@ -2723,132 +2103,8 @@ int stageC_readMerge(Ctx *c, u32 code) {
   return 0;
 }
 
-// the --cluster loop over GLOBAL block numbers [codeMin, codeMax): every segment of this context runs its part
-int stageC_cluster(Ctx *c, int codeMin, int codeMax, int threshold) {
-  if (!c->haveGood) return c->fail("!! you must set hashDepthRange before cluster");          // hash10x.c:1258
-  if (threshold < 1) return c->fail("clusterThreshold %d must be >= 1 (the reference reads an uninitialised msBest otherwise)", threshold);
-  if (c->maxGoodDepth > RES_COUNT_MAX) return c->fail("a hash of the depth range lies in %u barcodes: beyond %u, the limit of this build", c->maxGoodDepth, RES_COUNT_MAX);
-  const u32 nGlobal = c->sharded ? c->nBlocksGlobal : c->nBlocks;
-  if (!codeMin) codeMin = 1;                                                                    // hash10x.c:1243-1244
-  if (!codeMax) codeMax = (int)nGlobal;
-  if (codeMin < 0 || codeMax > (int)nGlobal) return c->fail("cluster code range %d..%d outside 1..%u", codeMin, codeMax, nGlobal);
-  bool any = false;
-  for (int k = 0; k < c->segs.n; ++k) {
-    const BlockSeg &sg = c->segs.s[k];
-    const long first = (long)sg.localStart + (k == 0 ? 1 : 0);                                  // slot 0 of the first segment is nobody's block
-    long lo = (long)codeMin - (long)sg.globalBase + (long)sg.localStart, hi = (long)codeMax - (long)sg.globalBase + (long)sg.localStart;
-    if (lo < first) lo = first;
-    if (hi > (long)sg.localStart + (long)sg.count) hi = (long)sg.localStart + (long)sg.count;
-    if (hi <= lo) continue;
-    H10X_TRY(cluster_local_range(c, (int)lo, (int)hi, threshold, any));
-    any = true;
-  }
-  if (!any) { memset(c->ctr.cluster_class_counts, 0, sizeof c->ctr.cluster_class_counts); memset(c->ctr.cluster_main, 0, sizeof c->ctr.cluster_main);
-              c->ctr.sum_good = c->ctr.sum_good_depth = c->ctr.sum_hash_clustered = c->ctr.clustered_codes = c->ctr.cluster_overflow_blocks = 0; }
-  return 0;
-}
-
-// ------------------------------------------------------------------------------------------ clusterSplit
-// clusterSplitCodes (hash10x.c:956-1013): every sub-cluster becomes a barcode block of its own, appended after the
-// original blocks (cluster j of the s-th clustered parent lands at nCodes - 1 + (sub-clusters before it) + j),
-// reads renumbered in order of first appearance, labels cleared; the parent keeps its unclustered hashes.
-// Not a hot path: one wavefront per parent block, lane 0 replays the reference's single pass over the block.
-__global__ void split_count_kernel(const h10x_block *__restrict__ oldB, const u64 *__restrict__ oldOff, const h10x_clushash *__restrict__ ch,
-                                   u32 nCodes, const u32 *__restrict__ subBefore /* exclusive scan of nSubCluster */, SegMap segs,
-                                   h10x_block *__restrict__ newB, u32 *__restrict__ newNHash) {
-  const u32 i = blockIdx.x; if (i >= nCodes) return;
-  const h10x_block ob = oldB[i];
-  __shared__ u32 cnt[256];
-  for (u32 t = threadIdx.x; t < 256; t += blockDim.x) cnt[t] = 0;
-  __syncthreads();
-  if (!ob.nSubCluster) {
-    if (threadIdx.x == 0) { h10x_block b = ob; b.clusHash = 0; newB[i] = b; newNHash[i] = (i >= 1) ? ob.nHash : 0; }
-    return;
-  }
-  const h10x_clushash *e = ch + oldOff[i];
-  for (u32 p = threadIdx.x; p < ob.nHash; p += blockDim.x) atomicAdd(&cnt[e[p].subCluster], 1u);
-  __syncthreads();
-  const u32 ext = nCodes - 1 + subBefore[i];
-  for (u32 j = threadIdx.x; j <= ob.nSubCluster && j < 256; j += blockDim.x) {
-    h10x_block b; memset(&b, 0, sizeof b);
-    if (j == 0) { b.nRead = ob.nRead; b.nHash = cnt[0]; newB[i] = b; newNHash[i] = cnt[0]; }      // hash10x.c:990: nRead kept, rest calloc'd
-    else { b.nHash = cnt[j]; b.clusterParent = segs.globalOf(i) + 1; newB[ext + j] = b; newNHash[ext + j] = cnt[j]; }   // nRead filled by the move pass (parent: global number)
-  }
-}
-
-__global__ void split_move_kernel(const h10x_block *__restrict__ oldB, const u64 *__restrict__ oldOff, const h10x_clushash *__restrict__ ch,
-                                  u32 nCodes, const u32 *__restrict__ subBefore, const u64 *__restrict__ readOff /* scan of nRead+1 */,
-                                  u32 *__restrict__ readMap /* zeroed */, h10x_block *__restrict__ newB, const u64 *__restrict__ newOff,
-                                  h10x_clushash *__restrict__ out) {
-  const u32 i = blockIdx.x; if (i >= nCodes) return;
-  const h10x_block ob = oldB[i];
-  const h10x_clushash *e = ch + oldOff[i];
-  if (!ob.nSubCluster) {                                     // *new1++ = *old (hash10x.c:996)
-    if (i >= 1) for (u32 p = threadIdx.x; p < ob.nHash; p += blockDim.x) out[newOff[i] + p] = e[p];
-    return;
-  }
-  if (threadIdx.x != 0) return;
-  __shared__ u32 cursor[256], nReadNew[256];
-  for (u32 j = 0; j <= ob.nSubCluster && j < 256; ++j) { cursor[j] = 0; nReadNew[j] = 0; }
-  const u32 ext = nCodes - 1 + subBefore[i];
-  u32 *rm = readMap + readOff[i];
-  for (u32 p = 0; p < ob.nHash; ++p) {                       // hash10x.c:980-989
-    h10x_clushash c = e[p]; const u32 cl = c.subCluster; c.subCluster = 0;
-    if (cl && cl <= ob.nSubCluster) {
-      if (!rm[c.read]) rm[c.read] = ++nReadNew[cl];
-      c.read = (u16)(rm[c.read] - 1);
-      out[newOff[ext + cl] + cursor[cl]++] = c;
-    } else out[newOff[i] + cursor[0]++] = c;
-  }
-  for (u32 j = 1; j <= ob.nSubCluster && j < 256; ++j) newB[ext + j].nRead = nReadNew[j];
-}
-
-__global__ void split_aux_kernel(const h10x_block *__restrict__ b, u32 n, u32 *__restrict__ nSub, u32 *__restrict__ nReadP1) {
-  const u32 i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < n) { nSub[i] = b[i].nSubCluster; nReadP1[i] = b[i].nSubCluster ? (b[i].nRead > 65535u ? 65536u : b[i].nRead) + 1 : 0; }
-}
-
-int stageC_split(Ctx *c) {
-  hipStream_t st = c->stream; PrimTemp pt;
-  if (!c->haveState) return c->fail("no hash state loaded: use readFQB or readHash first");
-  c->tstart(T_SPLIT);
-  const u32 nCodes = c->nBlocks;
-  DevBuf<u32> nSub, subBefore, nReadP1; DevBuf<u64> readOff;
-  H10X_HIP(c, nSub.alloc((size_t)nCodes + 1)); H10X_HIP(c, subBefore.alloc((size_t)nCodes + 1));
-  H10X_HIP(c, nReadP1.alloc((size_t)nCodes + 1)); H10X_HIP(c, readOff.alloc((size_t)nCodes + 1));
-  H10X_HIP(c, hipMemsetAsync(nSub.p + nCodes, 0, 4, st)); H10X_HIP(c, hipMemsetAsync(nReadP1.p + nCodes, 0, 4, st));
-  split_aux_kernel<<<divUp(nCodes, 256), 256, 0, st>>>(c->blocks.p, nCodes, nSub.p, nReadP1.p);
-  H10X_TRY(prim_exclusive_scan_u32(c, pt, nSub.p, subBefore.p, (size_t)nCodes + 1));
-  H10X_TRY(prim_exclusive_scan_u32_u64(c, pt, nReadP1.p, readOff.p, (size_t)nCodes + 1));
-  u32 totalSub = 0; u64 totalRead = 0;
-  H10X_HIP(c, hipMemcpyAsync(&totalSub, subBefore.p + nCodes, 4, hipMemcpyDeviceToHost, st));
-  H10X_HIP(c, hipMemcpyAsync(&totalRead, readOff.p + nCodes, 8, hipMemcpyDeviceToHost, st));
-  H10X_HIP(c, hipStreamSynchronize(st));
-  const u64 nNew64 = (u64)nCodes + totalSub;
-  if (nNew64 >= (1ULL << 31)) return c->fail("clusterSplit would create %llu barcode blocks", (u64)nNew64);
-  const u32 nNew = (u32)nNew64;
-  DevBuf<h10x_block> newB; DevBuf<u32> newNHash, readMap; DevBuf<u64> newOff; DevBuf<h10x_clushash> out;
-  H10X_HIP(c, newB.alloc(nNew)); H10X_HIP(c, newNHash.alloc((size_t)nNew + 1)); H10X_HIP(c, newOff.alloc((size_t)nNew + 1));
-  H10X_HIP(c, readMap.alloc(totalRead + 1)); H10X_HIP(c, out.alloc(c->nEntries));
-  H10X_HIP(c, hipMemsetAsync(newB.p, 0, (size_t)nNew * sizeof(h10x_block), st));
-  H10X_HIP(c, hipMemsetAsync(newNHash.p, 0, ((size_t)nNew + 1) * 4, st));
-  H10X_HIP(c, hipMemsetAsync(readMap.p, 0, (totalRead + 1) * 4, st));
-  split_count_kernel<<<nCodes, 256, 0, st>>>(c->blocks.p, c->blockOff.p, c->clusHash.p, nCodes, subBefore.p, c->segs, newB.p, newNHash.p);
-  H10X_TRY(prim_exclusive_scan_u32_u64(c, pt, newNHash.p, newOff.p, (size_t)nNew + 1));
-  split_move_kernel<<<nCodes, 64, 0, st>>>(c->blocks.p, c->blockOff.p, c->clusHash.p, nCodes, subBefore.p, readOff.p, readMap.p, newB.p, newOff.p, out.p);
-  H10X_HIP(c, hipGetLastError());
-  H10X_HIP(c, hipStreamSynchronize(st));
-  c->blocks.swap(newB); c->blockOff.swap(newOff); c->clusHash.swap(out);
-  c->nBlocks = nNew;
-  c->haveGood = false; c->goodPos.release(); c->nGood.release(); c->goodEntries.release(); c->goodRow.release();      // lists refer to the old blocks: a new --hashDepthRange is required
-  if (c->sharded) H10X_TRY(shard_split(c, subBefore.p, totalSub));   // new blocks get their global numbers; the hash owners rebuild their lists
-  else { c->segs.n = 1; c->segs.s[0] = BlockSeg{0, nNew, 0}; H10X_TRY(stageB_buildCSR(c)); }   // hash10x.c:1008-1012: hashCodes rebuilt, hashDepth unchanged
-  c->tstop(T_SPLIT);
-  return 0;
-}
-
-// h10x_warm: the first launch of a kernel loads the code object of its translation unit (HIP loads them on first use); this one is launched ahead of time
+// h10x_warm: the first launch of a kernel loads the code object of its translation unit (HIP loads them on first use); an empty one from each of the four units is launched ahead of time, in the order a run needs them
 __global__ void warm_stageC_kernel() {}
-void warm_stageC(hipStream_t st) { warm_stageC_kernel<<<1, 1, 0, st>>>(); }
+void warm_stageC(hipStream_t st) { warm_stageCGood(st); warm_stageCHost(st); warm_stageC_kernel<<<1, 1, 0, st>>>(); warm_stageCSplit(st); }
 
 }  // namespace h10x

@@ -270,7 +270,6 @@ void rs_classify_kernel(u32 nRuns, const u32 *__restrict__ perm, const u64 *__re
 }
 
 // ------------------------------------------------------------------------------------------------ drivers
-static int bitsFor(u64 v) { int b = 1; while (b < 64 && (v >> b)) ++b; return b; }           // bits that hold values 0 .. v
 
 static void rsInvalidate(ReadSet *rs) {
   rs->indexed = rs->tabled = false; rs->chunks.clear(); rs->pairStart.clear(); rs->cY.clear(); rs->cBits.clear(); rs->nRepeat.clear();

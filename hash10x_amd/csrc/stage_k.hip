@@ -4,7 +4,7 @@
 //
 //   nCodes = nBlocks (slot 0 unused), base[c] = records of blocks 1 .. c-1, R = base[nCodes]: record base[c] + r is read pair r of block c.
 //   A ClusterHash record of block c is clustered with label cl = subCluster when 1 <= subCluster <= nSubCluster[c] (split_move_kernel's
-//   guard, stage_c.hip) and its read lies inside the block. A read's label L is that of its FIRST clustered record in block order, its
+//   guard, stage_c_split.hip) and its read lies inside the block. A read's label L is that of its FIRST clustered record in block order, its
 //   slot the number of clustered reads of the block with the same label whose first clustered record lies earlier — the order of the
 //   reference's ++new2[clus].nRead —, its molecule nCodes - 1 + subBefore[c] + L, the block number --clusterSplit gives the cluster.
 //   An unclustered read keeps mol = c, slot = r. Split order: record -> start[mol] + slot for a molecule, start[c] + (unclustered records
