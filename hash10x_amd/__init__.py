@@ -237,6 +237,10 @@ def load_native():
     hip.h10x_crib_export.argtypes = [vp, vp, vp, vp, vp]
     host.h10x_session_hashCopies.argtypes = [vp, ci, cs, vp]
     host.h10x_session_hashCopiesRun.argtypes = [vp, ci, vp]
+    # the state as a mosh set (csrc/stage_o.hip)
+    hip.h10x_mosh_from_state.argtypes = [vp, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.POINTER(vp), vp]
+    host.h10x_session_moshSet.argtypes = [vp, ci, ci, ci, ci, ctypes.POINTER(vp), vp]
+    host.h10x_session_writeMosh.argtypes = [vp, ci, ci, ci, ci, cs, vp, vp]
     # mosh sets (csrc/stage_g.hip, host/mosh_host.c)
     pvp, ci32, cu32 = ctypes.POINTER(vp), ctypes.c_int32, ctypes.c_uint32
     hip.h10x_factors_from_seed.restype = None; hip.h10x_factors_from_seed.argtypes = [ci32, ctypes.POINTER(cu64), ctypes.POINTER(cu64)]
@@ -1046,6 +1050,27 @@ class Hash10x:
         crib the five HASH_COPIES lines, are appended to the file `out`."""
         self._with_file(out, lambda f: self._host.h10x_session_hashCopies(self._s, int(min_share), os.fsencode(path), f))
 
+    # ---- the state as a mosh set (h10x_mosh_from_state, csrc/stage_o.hip): the in-range hashes with 16-bit depths and copy classes ----
+    def mosh_set(self, copy1min, copy2min, copyMmin, bits=0):
+        """The hashes in the depth range as a MoshSet, built on the device from the state: value = the hash, depth = min(hashDepth, 65535),
+        class from the saturated depth by the three thresholds of moshutils -s and, where a hash_copies result is kept, corrected by linkage
+        (second >= 2 -> M, otherwise largest < 2 -> 0). bits = the table bits of the set, 0 = the state's B. The figures (kept, copy[4], toM,
+        to0, saturated, crib[5][4], hashNumber, bits, minShare: 0 = depth only) are kept in self.mosh_set_info. The kept hash_copies result stays."""
+        if not self._ctx():
+            raise Hash10xError("!! you must set hashDepthRange before writeMosh")
+        z = np.zeros(1, dtype=_STATE_MOSH_INFO)
+        h = ctypes.c_void_p()
+        self._chk(self._host.h10x_session_moshSet(self._s, int(bits), int(copy1min), int(copy2min), int(copyMmin), ctypes.byref(h), z.ctypes.data))
+        self.mosh_set_info = _state_mosh_info(z)
+        return MoshSet(_handle=h)
+
+    def write_mosh(self, bits, copy1min, copy2min, copyMmin, path, out=None):
+        """--writeMosh <bits> <copy1min> <copy2min> <copyMmin> <path>: that set written as an MSHSTv1 file; one line of counts, and with a crib
+        the five WRITE_MOSH lines, are appended to the file `out`. The figures are kept in self.mosh_set_info, as by mosh_set."""
+        z = np.zeros(1, dtype=_STATE_MOSH_INFO)
+        self._with_file(out, lambda f: self._host.h10x_session_writeMosh(self._s, int(bits), int(copy1min), int(copy2min), int(copyMmin), os.fsencode(path), f, z.ctypes.data))
+        self.mosh_set_info = _state_mosh_info(z)
+
     def export_within(self):
         """hashWithinRange[0 .. hashNumber) as uint8 (fails before --hashDepthRange)."""
         z = self.sizes()
@@ -1115,6 +1140,14 @@ def read_share_components(path):
 
 _HASH_COPIES_INFO = np.dtype([("inRange", "<u8"), ("rows", "<u8"), ("listEntries", "<u8"), ("oneGroup", "<u8"), ("split", "<u8"), ("hashNumber", "<u4"),
                               ("minShare", "<u4"), ("deepest", "<u4"), ("batches", "<u4"), ("windows", "<u4"), ("reserved", "<u4")])
+
+
+_STATE_MOSH_INFO = np.dtype([("kept", "<u8"), ("copy", "<u8", (4,)), ("toM", "<u8"), ("to0", "<u8"), ("saturated", "<u8"), ("crib", "<u8", (5, 4)),
+                             ("hashNumber", "<u4"), ("bits", "<u4"), ("minShare", "<u4"), ("reserved", "<u4")])   # h10x_state_mosh_info
+
+
+def _state_mosh_info(z):
+    return {n: (z[n][0].tolist() if z[n][0].ndim else int(z[n][0])) for n in _STATE_MOSH_INFO.names if n != "reserved"}
 
 
 def read_hash_copies(path):

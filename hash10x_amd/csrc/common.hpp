@@ -262,6 +262,8 @@ struct Ctx {
   // the per-hash linkage groups of the last h10x_hash_copies_run (stage_n.hip), kept until the next run, a new depth range, --clusterSplit or a new state:
   // hcOut = hcHashes records {u16 distinct, groups, largest, second}; hcTally[3 * t + k] = the counts per crib type t, [15] = the deepest in-range list
   DevBuf<u32> hcOut; u32 hcHashes = 0; bool haveHashCopies = false; u64 hcTally[16] = {}; h10x_hash_copies_info hcInfo{};
+  // the -r value prm.factor1 was drawn from (option "seqhash_seed"): a mosh set made from the state carries the hasher's second multiplier too (stage_o.hip)
+  int32_t seed = 0; bool haveSeed = false;
   // streaming ingest (h10x_ingest_fqb): the record image grows on the device as the chunks arrive
   DevBuf<u32> ingestBuf; u64 ingestRecords = 0, ingestCap = 0; bool ingestAsync = false;   // ingestAsync: chunks came through h10x_ingest_fqb_async (the closing call then checks the count)
   static constexpr int INGEST_SLOTS = 8; hipEvent_t ingestEv[INGEST_SLOTS] = {};   // h10x_ingest_fqb_async: one event per caller's buffer
@@ -532,6 +534,8 @@ int stageG_summary(Mosh *m, u32 *hist65536, u32 *copy4);
 void stageG_info(const Mosh *m, int *B, int *k, int *w, u64 *factor1, u64 *factor2, u32 *max, u32 *size);
 int stageG_export(Mosh *m, u64 indexFirst, u64 indexCount, u32 *index, u64 *value, u16 *depth, u8 *info);
 int stageG_lookup(Mosh *m, const u64 *hashes, u64 n, u32 *index, u16 *depth);
+// the state's in-range hashes as a classed mosh set (stage_o.hip)
+int stageO_run(Ctx *c, int bits, int copy1min, int copy2min, int copyMmin, Mosh **out, h10x_state_mosh_info *info);
 // readsets over a mosh set (stage_h.hip)
 struct ReadSet;
 int stageH_create(ReadSet **out, Mosh *m);

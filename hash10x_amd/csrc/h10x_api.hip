@@ -95,6 +95,13 @@ int h10x_mosh_export(h10x_mosh *s, uint64_t indexFirst, uint64_t indexCount, uin
   return s ? stageG_export(M(s), indexFirst, indexCount, index, (u64 *)value, depth, info) : -1;
 }
 int h10x_mosh_lookup(h10x_mosh *s, const uint64_t *hashes, uint64_t n, uint32_t *index, uint16_t *depth) { return s ? stageG_lookup(M(s), (const u64 *)hashes, n, index, depth) : -1; }
+// ---- the state as a mosh set (stage_o.hip) ----
+int h10x_mosh_from_state(h10x_ctx *h, int32_t bits, int32_t copy1min, int32_t copy2min, int32_t copyMmin, h10x_mosh **set, h10x_state_mosh_info *info) {
+  if (!h || !set) return -1;
+  *set = nullptr;
+  H10X_TRY(enter(h->c));
+  return stageO_run(&h->c, bits, copy1min, copy2min, copyMmin, reinterpret_cast<Mosh **>(set), info);
+}
 
 // ---- readsets: thin wrappers over stage_h.hip; the host vectors' std::bad_alloc stops here and becomes the error text
 struct h10x_readset;                                         // == h10x::ReadSet
@@ -993,6 +1000,7 @@ int h10x_set_option(h10x_ctx *h, const char *name, int64_t value) {
   if (!strcmp(name, "shard_rows_fake_base")) { if (value < 0) return h->c.fail("shard_rows_fake_base must be >= 0"); h->c.optRowsFakeBase = value; return 0; }
   if (!strcmp(name, "molmap_global")) { if (value < 0 || value > 1) return h->c.fail("molmap_global must be 0 or 1"); h->c.optMolGlobal = value; return 0; }
   if (!strcmp(name, "fqb_slab")) { if (value < 0 || value > (1 << 28)) return h->c.fail("fqb_slab must be 0..2^28"); h->c.optFqbSlab = value; return 0; }
+  if (!strcmp(name, "seqhash_seed")) { h->c.seed = (int32_t)value; h->c.haveSeed = true; return 0; }   // the -r value: checked against prm.factor1 where it is used (stage_o.hip)
   if (!strcmp(name, "neighbour_budget")) { if (value < 0) return h->c.fail("neighbour_budget must be >= 0"); h->c.optNbBudget = value; return 0; }
   return h->c.fail("unknown option %s", name);
 }

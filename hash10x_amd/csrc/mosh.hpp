@@ -37,6 +37,12 @@ template <typename F> static int moshBatches(Mosh *m, const u64 *seqStart, u32 n
   return 0;
 }
 
+// what a driver outside stage_g.hip builds a set with (stage_o.hip): an empty object on a stream of its own, its arrays (zeroed, `size` entries per
+// index), and the table entries of the new indices [max + 1, max + 1 + D) whose value[] is written
+int moshOpen(Mosh **out, int B, int k, int w, u64 factor1, u64 factor2, int device, char *err, int errlen);
+int moshAllocSet(Mosh *m, u32 size);
+int moshPlace(Mosh *m, u32 D);
+
 // one uploaded batch and the list its scan left (stage_g.hip)
 struct MoshBatch { DevBuf<u8> codes; DevBuf<u64> seq, run, tallies, outHash; DevBuf<u32> outOrd; u64 nRuns = 0, total = 0, listed = 0, found = 0; };
 int moshIota(Mosh *m, u32 *v, u64 n);

@@ -222,7 +222,7 @@ __global__ void mosh_iota_kernel(u32 *__restrict__ v, u64 n) {
 }
 
 // ------------------------------------------------------------------------------------------------ drivers
-static int moshAllocSet(Mosh *m, u32 size) {
+int moshAllocSet(Mosh *m, u32 size) {
   Ctx *c = &m->c; hipStream_t st = c->stream;
   const u64 T = (u64)1 << m->B;
   const u64 bytes = T * 4 + (u64)size * (8 + 2 + 1 + 4);
@@ -246,7 +246,7 @@ __attribute__((format(printf, 3, 4))) static int moshBad(char *err, int errlen, 
   return -1;
 }
 #define bad(...) moshBad(err, errlen, __VA_ARGS__)
-static int moshOpen(Mosh **out, int B, int k, int w, u64 factor1, u64 factor2, int device, char *err, int errlen) {
+int moshOpen(Mosh **out, int B, int k, int w, u64 factor1, u64 factor2, int device, char *err, int errlen) {
   *out = nullptr;
   if (k < 1 || k >= 32) return bad("seqhash k %d must be between 1 and 32\n", k);            // seqhash.c:24-25
   if (w < 1) return bad("seqhash w %d must be positive\n", w);
@@ -321,7 +321,7 @@ int stageG_setOption(Mosh *m, const char *name, int64_t v) {
 }
 
 // new indices [first, first + D) have their value[]: the die of moshset.c:57, then the table
-static int moshPlace(Mosh *m, u32 D) {
+int moshPlace(Mosh *m, u32 D) {
   Ctx *c = &m->c;
   if (!D) return 0;
   if ((u64)m->max + D >= (u64)m->size) return c->fail("hashTableSize %u is too small for %u", m->size, m->size);

@@ -146,6 +146,7 @@ static int apply_options(h10x_session *s) {
   h10x_timing_enable(s->ctx, s->timing);
   for (int i = 0; i < N_KNOBS; ++i) if (h10x_set_option(s->ctx, knobName[i], s->knob[i])) return fail_ctx(s);
   if (h10x_set_option(s->ctx, "chunk_size", 0)) return fail_ctx(s);
+  if (h10x_set_option(s->ctx, "seqhash_seed", s->r)) return fail_ctx(s);   /* -r itself: a mosh set made from the state carries both multipliers (--writeMosh) */
   return 0;
 }
 
@@ -1904,4 +1905,50 @@ int h10x_session_hashCopies(h10x_session *s, int minShare, const char *outPath, 
               (unsigned long long)counts[t][2]);
   }
   return 0;
+}
+
+/* ---- --writeMosh <bits> <copy1min> <copy2min> <copyMmin> <out.mosh>: the in-range hashes of the state as a classed mosh set (h10x_mosh_from_state).
+   The set is built on the device from the context's arrays and leaves it through h10x_mosh_set_write, the table in slices. ---- */
+int h10x_session_moshSet(h10x_session *s, int bits, int copy1min, int copy2min, int copyMmin, h10x_mosh **set, h10x_state_mosh_info *info) {
+  *set = 0;
+  if (!s->ctx) return fail(s, "!! you must set hashDepthRange before writeMosh");       /* nothing loaded: no range either */
+  h10x_shard_info_t z; if (h10x_shard_info(s->ctx, &z)) return fail_ctx(s);
+  if (z.nranks > 1) return fail(s, "writeMosh does not run on a sharded session (--gpus > 1)");
+  if (h10x_mosh_from_state(s->ctx, bits, copy1min, copy2min, copyMmin, set, info)) return fail_ctx(s);
+  return 0;
+}
+
+void h10x_host_print_state_mosh(FILE *out, const h10x_state_mosh_info *z, int withCrib) {
+  fprintf(out, "  mosh set of %llu hashes in range, bits %u: copy0 %llu copy1 %llu copy2 %llu copyM %llu", (unsigned long long)z->kept, z->bits,
+          (unsigned long long)z->copy[0], (unsigned long long)z->copy[1], (unsigned long long)z->copy[2], (unsigned long long)z->copy[3]);
+  if (z->minShare) fprintf(out, ", by linkage at minShare %u: %llu to M, %llu to 0", z->minShare, (unsigned long long)z->toM, (unsigned long long)z->to0);
+  else fprintf(out, ", by depth only");
+  if (z->saturated) fprintf(out, ", %llu depths cut to 65535", (unsigned long long)z->saturated);
+  fputc('\n', out);
+  if (withCrib)
+    for (int t = 0; t < 5; ++t)
+      fprintf(out, "WRITE_MOSH  %s copy0 %llu copy1 %llu copy2 %llu copyM %llu\n", cribTypeName[t], (unsigned long long)z->crib[t][0],
+              (unsigned long long)z->crib[t][1], (unsigned long long)z->crib[t][2], (unsigned long long)z->crib[t][3]);
+}
+
+int h10x_session_writeMosh(h10x_session *s, int bits, int copy1min, int copy2min, int copyMmin, const char *outPath, FILE *out, h10x_state_mosh_info *infoOut) {
+  h10x_mosh *set = 0; h10x_state_mosh_info info;
+  if (h10x_session_moshSet(s, bits, copy1min, copy2min, copyMmin, &set, &info)) return -1;
+  if (infoOut) *infoOut = info;
+  int rc = 0;
+  const size_t n = strlen(outPath);
+  char *part = (char *)malloc(n + 6);                                                   /* the file appears under its name when it is whole */
+  if (!part) { rc = fail(s, "out of host memory"); goto done; }
+  memcpy(part, outPath, n); memcpy(part + n, ".part", 6);
+  { FILE *t = fopen(part, "wb"); if (!t) { rc = fail(s, "failed to open output file %s", outPath); goto done; } fclose(t); }
+  if (h10x_mosh_set_write(set, part, s->err, (int)sizeof s->err)) { remove(part); rc = -1; goto done; }
+  if (rename(part, outPath)) { remove(part); rc = fail(s, "failed to write %s", outPath); goto done; }
+  if (out) {
+    uint32_t histDim = 0;
+    h10x_host_print_state_mosh(out, &info, h10x_crib_sizes(s->ctx, &histDim, 0) == 0);
+  }
+done:
+  free(part);
+  h10x_mosh_destroy(set);
+  return rc;
 }

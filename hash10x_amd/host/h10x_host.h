@@ -148,6 +148,19 @@ int  h10x_session_hashCopiesRun(h10x_session *s, int minShare, h10x_hash_copies_
 int  h10x_host_write_hash_copies(const char *path, const h10x_hash_copies_info *info, h10x_hash_copies_slab_fn slab, void *user, uint64_t slabHashes,
                                  char *err, int errlen);
 
+/* --writeMosh <bits> <copy1min> <copy2min> <copyMmin> <out.mosh> (addition; include/h10x.h "the state as a mosh set"): the in-range hashes of the state as
+   an MSHSTv1 file that moshutils, moshasm and moshmap read: the state's hash values, depths saturated to 16 bits, copy classes from depth by the three
+   thresholds of moshutils -s and, where a --hashCopies result is kept, corrected by linkage. bits = the table bits of the set, 0 = the state's -B. The file
+   is written as <out.mosh>.part and renamed when it is whole. The figures of the set to info (may be NULL), one line to out (may be NULL),
+     "  mosh set of N hashes in range, bits B: copy0 a copy1 b copy2 c copyM d, by linkage at minShare T: x to M, y to 0"   (or ", by depth only"),
+   with ", n depths cut to 65535" when depths saturated, and with a crib five lines "WRITE_MOSH  <err|htA|htB|hom|mul> copy0 a copy1 b copy2 c copyM d".
+   Fails with "!! ..." (the command then does nothing, no file is written) before --hashDepthRange, after --clusterSplit until a new range is set, for
+   thresholds that do not ascend and for bits outside 0, 20 .. 34; single-GPU sessions only.
+   h10x_session_moshSet is the build alone: *set is the caller's to use and destroy. h10x_host_print_state_mosh prints the lines (no device). */
+int  h10x_session_writeMosh(h10x_session *s, int bits, int copy1min, int copy2min, int copyMmin, const char *outPath, FILE *out, h10x_state_mosh_info *info);
+int  h10x_session_moshSet(h10x_session *s, int bits, int copy1min, int copy2min, int copyMmin, h10x_mosh **set, h10x_state_mosh_info *info);
+void h10x_host_print_state_mosh(FILE *out, const h10x_state_mosh_info *info, int withCrib);
+
 /* multi-GPU (include/h10x.h "multi-GPU"): one session per rank, each holding a contiguous barcode range of the sorted file
    (cut with h10x_host_partition / _partition_file; -N is applied by the launcher before cutting). Every command of a
    sharded session is collective: all ranks call it with the same arguments; the text commands print on the rank whose

@@ -23,7 +23,10 @@ extern "C" {
 #endif
 
 /* 2 (round 5): h10x_warm, h10x_alloc_stats, h10x_pinned_*, h10x_ingest_fqb_async / _wait, H10X_TABLE_CLUSTER_RAW, the exchange counters of
-   h10x_counters; option "cluster_dbg_skip" gone. libh10x_host.so and the Python loader refuse a libh10x_hip.so of another version. */
+   h10x_counters; option "cluster_dbg_skip" gone.
+   3: h10x_counters.shard_reply_path, options "shard_reply_sort" 2 .. 4 and "shard_owner_cut". Entry points added since (the census, share graph, components,
+   hash copies, mosh sets, readsets, reference maps, h10x_mosh_from_state) change no existing struct or table and leave the version alone.
+   libh10x_host.so and the Python loader refuse a libh10x_hip.so of another version. */
 #define H10X_ABI_VERSION 3
 
 typedef struct h10x_ctx h10x_ctx;
@@ -558,6 +561,39 @@ int  h10x_mosh_export(h10x_mosh *set, uint64_t indexFirst, uint64_t indexCount, 
 /* moshsetIndexFind(ms, hash, FALSE) per hash (reportDepths, moshutils.c:64-76): index (0 = absent) and depth (0 when absent) */
 int  h10x_mosh_lookup(h10x_mosh *set, const uint64_t *hashes, uint64_t n, uint32_t *index, uint16_t *depth);
 
+/* ---- the state as a mosh set (csrc/stage_o.hip): the in-range hashes of a context as a classed set, behind --writeMosh ----
+   hash10x (hash10x.c:1099-1104) and moshutils -c (moshutils.c:150-151) both call srandom(seed); seqhashCreate(k, w), take their hashes from
+   moshRCiterator and keep them in the same probe table (hashIndexFind, hash10x.c:139-152 = moshsetIndexFind, moshset.c:45-61), so a state with
+   -k K -w W -r R is a mosh set with hasher (K, W, seed R) that lacks the 16-bit depths and the info byte.
+   State: a loaded, unsharded context with a --hashDepthRange in force; --cluster / --clusterSplit may or may not have run before.
+   Parameters: bits = the table bits of the set (0 = the state's B, otherwise 20 .. 34); copy1min <= copy2min <= copyMmin, the thresholds of moshutils -s.
+   Kept hashes: the indices x >= 1 with hashWithinRange[x], ascending; the k-th kept hash gets set index k from 1 (what moshsetDepthPrune does
+   with the survivors of a set, moshset.c:63-76). Per kept hash: value = hashValue[x]; depth = min(hashDepth[x], 65535); info = the class in its
+   low two bits, nothing else:
+     1. the base class from the saturated depth d as moshutils.c:173-177: d < copy1min -> 0, d < copy2min -> 1, d < copyMmin -> 2, otherwise 3 (M);
+     2. if a --hashCopies result is kept for this state, x's record (distinct, groups, largest, second) overrides it: second >= 2 -> 3 (the hash's
+        molecules fall into two real groups: multicopy whatever its depth), otherwise largest < 2 -> 0 (no two blocks that hold it link at that
+        minShare), otherwise the base class stays;
+     3. without a kept result the base class stands ("depth only").
+   Table: index[2^bits] is what moshsetIndexFind(ms, value, TRUE) builds when the kept hashes are inserted in set-index order into an empty table.
+   Header: k, w and the two multipliers of the context's hasher. The context learns its -r value through option "seqhash_seed" (the session layer
+   sets it; the call fails without it, or if it does not give the context's factor1). For a state from --readHash these are trusted as the reference
+   trusts them: a .hash file does not store them. value[0] is 0.
+   The result depends on nothing but the state, the kept --hashCopies result and the five parameters: two calls give the same bytes. The call neither
+   releases nor changes the kept --hashCopies result.
+   info: kept; copy[q] = kept hashes of class q; toM / to0 = kept hashes whose class the linkage changed to M / to 0 (a hash whose depth had put it
+   there already does not count); saturated = kept hashes with hashDepth > 65535; crib[t][q] = kept hashes of crib type t (err, htA, htB, hom, mul)
+   and class q, all 0 without a crib; hashNumber; bits = the table bits used; minShare = that of the kept --hashCopies result, 0 = depth only.
+   *set is an ordinary h10x_mosh, full as after h10x_mosh_load; every h10x_mosh_* call works on it and the caller destroys it. On failure *set = NULL
+   and h10x_last_error(ctx) holds the text: no state; a sharded context; before --hashDepthRange and after --clusterSplit until a new range ("!! you
+   must set hashDepthRange before writeMosh"); "!! writeMosh needs 0 <= copy1min <= copy2min <= copyMmin"; "!! writeMosh bits N must be 0 or
+   20 .. 34"; kept + 1 >= 2^(bits-2): moshsetCreate's "Moshset size %u is too big for %d bits" (moshset.c:24). */
+typedef struct {
+  uint64_t kept, copy[4], toM, to0, saturated, crib[5][4];
+  uint32_t hashNumber, bits, minShare /* 0 = depth only */, reserved;
+} h10x_state_mosh_info;
+int  h10x_mosh_from_state(h10x_ctx *ctx, int32_t bits, int32_t copy1min, int32_t copy2min, int32_t copyMmin, h10x_mosh **set, h10x_state_mosh_info *info);
+
 /* ---- readsets (csrc/stage_h.hip): the Readset object of the reference's moshasm (moshasm.c) over a mosh set ----
    Long reads kept as their mosh hits only: per read the set indices hit, in position order (top bit = the forward hash was strictly
    the smaller, seqhash.c:67), and the 16-bit distance of each hit to the one before it. Read 0 is the reference's burned entry. The
@@ -733,7 +769,9 @@ int  h10x_get_counters(h10x_ctx *ctx, h10x_counters *out);
    the in-range barcode lists travel delta-coded where bytes are dear — more than one rank on the host-staged TCP backend, not over xGMI; 0 never; 1 always),
    "neighbour_budget" (gathered ClusterHash records per batch of the neighbour census; 0 = default 2^26; small values force batches and hash-index windows),
    "molmap_global" (1 = the molecule map keeps the first-clustered-position table of every clustered block in device memory, also where it fits LDS: tests of that form),
-   "fqb_slab" (records per device batch of h10x_census_add / h10x_fix_fqb and of the session's --codeCensus / --fixFQB / --fixFQBThresh; 0 = default 2^20). Unknown name: -1. */
+   "fqb_slab" (records per device batch of h10x_census_add / h10x_fix_fqb and of the session's --codeCensus / --fixFQB / --fixFQBThresh; 0 = default 2^20).
+   Not a knob: "seqhash_seed" = the -r value params.factor1 was drawn from (h10x_factor1_from_seed); h10x_mosh_from_state needs it for the second multiplier of the
+   set's header, and the session layer sets it. Unknown name: -1. */
 int  h10x_set_option(h10x_ctx *ctx, const char *name, int64_t value);
 
 #ifdef __cplusplus
