@@ -1963,19 +1963,21 @@ void point_sum_kernel(h10x_block *__restrict__ blocks, const u64 *__restrict__ b
 
 // ---- (f) codeClusterReadMerge (hash10x.c:837-868): components of labels that share a read, renumbered by ascending
 // minimum label. One small workgroup per barcode; BIG = blocks with more than MERGE_SMALL_READS read pairs.
+// --cluster merges every block of its range that carries clusters, whatever codeClusterFind did (hash10x.c:1250-1253): a block without good hashes keeps
+// the labels of its file, and those may be unmerged. codeExplore leaves such a block alone (it returns before its merge, hash10x.c:1361): goodOnly.
 constexpr int MERGE_THREADS = 256;
 constexpr u32 MERGE_SMALL_READS = 4096;
 template <bool BIG>
 __global__ __launch_bounds__(MERGE_THREADS)
 void read_merge_kernel(h10x_block *__restrict__ blocks, const u64 *__restrict__ blockOff, const u32 *__restrict__ nGood,
-                       h10x_clushash *__restrict__ clusHash, u32 codeMin) {
+                       h10x_clushash *__restrict__ clusHash, u32 codeMin, u32 goodOnly) {
   extern __shared__ __align__(16) unsigned char smem[];
   __shared__ u32 changed;
   const u32 c = codeMin + blockIdx.x;
-  if (!nGood[c]) return;
+  if (goodOnly && !nGood[c]) return;
   const h10x_block blk = blocks[c];
   const u32 nSub = blk.nSubCluster, nHash = blk.nHash, nRead = blk.nRead;
-  if (!nSub) return;                                         // hash10x.c:840
+  if (!nSub || !nHash || nSub > 255) return;                 // hash10x.c:840; (a file's block without records has nothing to merge, one with more clusters than a label can say is no valid state)
   if ((nRead > MERGE_SMALL_READS) != BIG) return;
   const int tid = threadIdx.x;
   const u32 nRep = nRead < 65536u ? nRead : 65536u;
@@ -2042,7 +2044,7 @@ void read_merge_kernel(h10x_block *__restrict__ blocks, const u64 *__restrict__ 
 }
 
 // ---- everything behind the main launches of blocks [codeMin, codeMax) (local numbers), queued on the context's stream and its first side stream
-int stageC_clusterTail(Ctx *c, u32 codeMin, u32 codeMax, u64 *res, const u32 *listBig, u32 nBig /* blocks with more than REPLAY_SMALL ranks */, u32 maxReads /* largest nRead of a block */) {
+int stageC_clusterTail(Ctx *c, u32 codeMin, u32 codeMax, u64 *res, const u32 *listBig, u32 nBig /* blocks with more than REPLAY_SMALL ranks */, u32 maxReads /* largest nRead of a block that has good hashes or clusters */) {
   hipStream_t st = c->stream; const u32 span = codeMax - codeMin;
   // (c) labels, cluster counts and the > 255 clusters cut from the msBest column: one workgroup per barcode, classes by rank count
   DevBuf<unsigned char> replayScratch;
@@ -2079,10 +2081,10 @@ int stageC_clusterTail(Ctx *c, u32 codeMin, u32 codeMax, u64 *res, const u32 *li
   point_sum_kernel<<<divUp(span, SUM_THREADS / WAVE), SUM_THREADS, 0, c->aux[0]>>>(c->blocks.p, c->blockOff.p, c->nGood.p, (const double *)res, codeMin, codeMax);
   {
     const size_t ldsSmall = mergeBytes(MERGE_SMALL_READS), ldsBig = mergeBytes(65536);
-    read_merge_kernel<false><<<span, MERGE_THREADS, ldsSmall, st>>>(c->blocks.p, c->blockOff.p, c->nGood.p, c->clusHash.p, codeMin);
+    read_merge_kernel<false><<<span, MERGE_THREADS, ldsSmall, st>>>(c->blocks.p, c->blockOff.p, c->nGood.p, c->clusHash.p, codeMin, 0u);
     if (maxReads > MERGE_SMALL_READS) {
       H10X_HIP(c, hipFuncSetAttribute((const void *)read_merge_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsBig));
-      read_merge_kernel<true><<<span, MERGE_THREADS, ldsBig, st>>>(c->blocks.p, c->blockOff.p, c->nGood.p, c->clusHash.p, codeMin);
+      read_merge_kernel<true><<<span, MERGE_THREADS, ldsBig, st>>>(c->blocks.p, c->blockOff.p, c->nGood.p, c->clusHash.p, codeMin, 0u);
     }
   }
   H10X_HIP(c, hipGetLastError());
@@ -2096,9 +2098,9 @@ int stageC_clusterTail(Ctx *c, u32 codeMin, u32 codeMax, u64 *res, const u32 *li
 int stageC_readMerge(Ctx *c, u32 code) {
   hipStream_t st = c->stream;
   const size_t ldsSmall = mergeBytes(MERGE_SMALL_READS), ldsBig = mergeBytes(65536);
-  read_merge_kernel<false><<<1, MERGE_THREADS, ldsSmall, st>>>(c->blocks.p, c->blockOff.p, c->nGood.p, c->clusHash.p, code);
+  read_merge_kernel<false><<<1, MERGE_THREADS, ldsSmall, st>>>(c->blocks.p, c->blockOff.p, c->nGood.p, c->clusHash.p, code, 1u);
   H10X_HIP(c, hipFuncSetAttribute((const void *)read_merge_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsBig));
-  read_merge_kernel<true><<<1, MERGE_THREADS, ldsBig, st>>>(c->blocks.p, c->blockOff.p, c->nGood.p, c->clusHash.p, code);
+  read_merge_kernel<true><<<1, MERGE_THREADS, ldsBig, st>>>(c->blocks.p, c->blockOff.p, c->nGood.p, c->clusHash.p, code, 1u);
   H10X_HIP(c, hipGetLastError());
   return 0;
 }

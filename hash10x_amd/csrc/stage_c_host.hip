@@ -61,6 +61,7 @@ __global__ void cluster_classify_kernel(const h10x_block *__restrict__ blocks, c
   // then does not end on a workgroup that drew a big one last. (Ordering the WHOLE queue by size was measured 17 % slower:
   // like-sized workgroups run their phases in step.)
   if (cls == 0 && n > bigRanks) cls = 1;
+  if (!n && c < codeMax && blocks[c].nSubCluster) nRead = blocks[c].nRead;   // no good hashes, but clusters in its file: the read merge still runs on it (hash10x.c:1252)
   for (int s = 32; s; s >>= 1) nRead = max(nRead, (u32)__shfl_xor((int)nRead, s));
   if (lane == 0 && nRead) atomicMax(&counts[8], nRead);
   {                                                          // most ranks of a block per LDS class: the translated placement sizes its handle slots by them
