@@ -241,6 +241,14 @@ def load_native():
     hip.h10x_mosh_from_state.argtypes = [vp, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.POINTER(vp), vp]
     host.h10x_session_moshSet.argtypes = [vp, ci, ci, ci, ci, ctypes.POINTER(vp), vp]
     host.h10x_session_writeMosh.argtypes = [vp, ci, ci, ci, ci, cs, vp, vp]
+    # from sequences to blocks (csrc/stage_p.hip)
+    hip.h10x_seq_hashes.argtypes = [vp, vp, vp, ctypes.c_uint32, vp]
+    hip.h10x_seq_hashes_get.argtypes = [vp, vp, vp, cu64]
+    hip.h10x_list_share_run.argtypes = [vp, ctypes.c_int64, vp, vp, ctypes.c_uint32, vp]
+    hip.h10x_seq_blocks_run.argtypes = [vp, ctypes.c_int64, vp, vp, ctypes.c_uint32, vp, vp]
+    hip.h10x_list_share_get.argtypes = [vp, vp, vp, vp, cu64]
+    hip.h10x_list_share_get_device.argtypes = [vp, vp, vp, vp, cu64]
+    host.h10x_session_seqBlocks.argtypes = [vp, ci, cs, cs, vp, ci]
     # mosh sets (csrc/stage_g.hip, host/mosh_host.c)
     pvp, ci32, cu32 = ctypes.POINTER(vp), ctypes.c_int32, ctypes.c_uint32
     hip.h10x_factors_from_seed.restype = None; hip.h10x_factors_from_seed.argtypes = [ci32, ctypes.POINTER(cu64), ctypes.POINTER(cu64)]
@@ -1071,6 +1079,81 @@ class Hash10x:
         self._with_file(out, lambda f: self._host.h10x_session_writeMosh(self._s, int(bits), int(copy1min), int(copy2min), int(copyMmin), os.fsencode(path), f, z.ctypes.data))
         self.mosh_set_info = _state_mosh_info(z)
 
+    # ---- from sequences to blocks (h10x_seq_hashes / h10x_list_share_* / h10x_seq_blocks_run, csrc/stage_p.hip) ----
+    @staticmethod
+    def _flatten_seqs(seqs):
+        """a list of sequences -> (codes uint8, seq_start uint64): a byte string is text (ACGT in either case, anything else 0 as N),
+        an array holds the codes 0 .. 3 themselves"""
+        out = []
+        for s in seqs:
+            if isinstance(s, (bytes, bytearray, str)):
+                s = np.frombuffer(s.encode() if isinstance(s, str) else bytes(s), dtype=np.uint8)
+                s = _SEQ_CODE[s]
+            out.append(np.ascontiguousarray(s, dtype=np.uint8).reshape(-1))
+        start = np.zeros(len(out) + 1, dtype=np.uint64)
+        if out:
+            start[1:] = np.cumsum([len(s) for s in out])
+        return (np.ascontiguousarray(np.concatenate(out)) if out else np.zeros(0, np.uint8)), start
+
+    def _seq_ctx(self, cmd):
+        ctx = self._ctx()
+        if not ctx:
+            raise Hash10xError("%s: no hash state loaded: use readFQB or readHash first" % cmd)
+        return ctx
+
+    def seq_hashes(self, seqs):
+        """Per sequence the distinct hash indices of its moshes that the state holds within the depth range, ascending: (offsets
+        uint64[n + 1], hash uint32[], figures) with figures a structured array of (moshes, found, query, entries) per sequence: the mosh
+        occurrences, those found in the state's table, the length of the list and the sum of hashDepth over it."""
+        ctx = self._seq_ctx("seqHashes")
+        codes, start = self._flatten_seqs(seqs)
+        n = len(start) - 1
+        fig = np.zeros(max(n, 1), dtype=_SEQ_FIGURES)
+        self._chk_ctx(self._hip.h10x_seq_hashes(ctx, codes.ctypes.data, start.ctypes.data, n, fig.ctypes.data))
+        off = np.zeros(n + 1, dtype=np.uint64)
+        self._chk_ctx(self._hip.h10x_seq_hashes_get(ctx, off.ctypes.data, None, 0))
+        m = int(off[-1])
+        hsh = np.zeros(max(m, 1), dtype=np.uint32)
+        self._chk_ctx(self._hip.h10x_seq_hashes_get(ctx, None, hsh.ctypes.data, m))
+        return off, hsh[:m], fig[:n][["moshes", "found", "query", "entries"]]
+
+    def _list_share_rows(self, ctx, z):
+        self.seq_blocks_info = {k: int(z[k][0]) for k in _LIST_SHARE_INFO.names}
+        m = self.seq_blocks_info["rows"]
+        off = np.zeros(self.seq_blocks_info["lists"] + 1, dtype=np.uint64)
+        blk, cnt = np.zeros(max(m, 1), dtype=np.uint32), np.zeros(max(m, 1), dtype=np.uint32)
+        self._chk_ctx(self._hip.h10x_list_share_get(ctx, off.ctypes.data, blk.ctypes.data, cnt.ctypes.data, m))
+        return off, blk[:m], cnt[:m]
+
+    def list_share(self, offsets, hashes, min_share):
+        """The list census: per list of hash indices (CSR: offsets[nq + 1], hashes[]) the blocks that stand at least min_share times in
+        the barcode lists of its hashes, as (offsets uint64[nq + 1], block uint32[], count uint32[]), ascending in block. No block is
+        left out and the depth range is not applied. The figures of the run (rows, listEntries, listHashes, maxCount, batches, windows,
+        wideBatches, nBlocks, lists) are kept in self.seq_blocks_info."""
+        ctx = self._seq_ctx("listShare")
+        o = np.ascontiguousarray(offsets, dtype=np.uint64); x = np.ascontiguousarray(hashes, dtype=np.uint32)
+        if len(o) < 1 or int(o[-1]) > len(x):
+            raise Hash10xError("listShare: offsets must hold nq + 1 entries and end within the hashes")
+        z = np.zeros(1, dtype=_LIST_SHARE_INFO)
+        self._chk_ctx(self._hip.h10x_list_share_run(ctx, int(min_share), o.ctypes.data, x.ctypes.data, len(o) - 1, z.ctypes.data))
+        return self._list_share_rows(ctx, z)
+
+    def seq_blocks(self, seqs, min_share):
+        """Per sequence the blocks that stand at least min_share times in the barcode lists of its in-range hashes (seq_hashes fed into
+        list_share on the device): (offsets, block, count, figures). The figures of the run are kept in self.seq_blocks_info."""
+        ctx = self._seq_ctx("seqBlocks")
+        codes, start = self._flatten_seqs(seqs)
+        n = len(start) - 1
+        fig = np.zeros(max(n, 1), dtype=_SEQ_FIGURES); z = np.zeros(1, dtype=_LIST_SHARE_INFO)
+        self._chk_ctx(self._hip.h10x_seq_blocks_run(ctx, int(min_share), codes.ctypes.data, start.ctypes.data, n, fig.ctypes.data, z.ctypes.data))
+        return self._list_share_rows(ctx, z) + (fig[:n][["moshes", "found", "query", "entries"]],)
+
+    def write_seq_blocks(self, min_share, seqfile, path, out=None, verbose=False):
+        """--seqBlocks <min_share> <seqfile> <path>: the rows of every sequence of a FASTA / FASTQ file (gzip or plain) written slab by slab
+        as a .sb file (read_seq_blocks reads it); one line of counts, and with verbose one SEQ_BLOCKS line per sequence, are appended to
+        the file `out`."""
+        self._with_file(out, lambda f: self._host.h10x_session_seqBlocks(self._s, int(min_share), os.fsencode(seqfile), os.fsencode(path), f, 1 if verbose else 0))
+
     def export_within(self):
         """hashWithinRange[0 .. hashNumber) as uint8 (fails before --hashDepthRange)."""
         z = self.sizes()
@@ -1078,6 +1161,13 @@ class Hash10x:
         self._chk_ctx(self._hip.h10x_export_slice(self._ctx(), 7, 0, z["hashNumber"], w.ctypes.data))
         return w[:z["hashNumber"]]
 
+
+_SEQ_FIGURES = np.dtype([("moshes", "<u4"), ("found", "<u4"), ("query", "<u4"), ("reserved", "<u4"), ("entries", "<u8")])
+_LIST_SHARE_INFO = np.dtype([("rows", "<u8"), ("listEntries", "<u8"), ("listHashes", "<u8"), ("maxCount", "<u4"), ("batches", "<u4"), ("windows", "<u4"),
+                             ("wideBatches", "<u4"), ("nBlocks", "<u4"), ("lists", "<u4")])
+_SEQ_CODE = np.zeros(256, dtype=np.uint8)
+for _i, _c in enumerate("ACGT"):
+    _SEQ_CODE[ord(_c)] = _SEQ_CODE[ord(_c.lower())] = _i
 
 _SHARE_GRAPH_INFO = np.dtype([("rows", "<u8"), ("listEntries", "<u8"), ("entriesRead", "<u8"), ("maxCount", "<u4"), ("batches", "<u4"), ("windows", "<u4"),
                               ("codeMin", "<u4"), ("codeMax", "<u4"), ("nBlocks", "<u4")])
@@ -1102,6 +1192,55 @@ def read_share_graph(path):
         raise Hash10xError("%s: the offsets do not ascend from 0 to the %d rows" % (path, rows))
     pairs = np.frombuffer(data, dtype="<u4", count=2 * rows, offset=24 + 8 * (n_blocks + 1)).reshape(-1, 2)
     return {"version": version, "nBlocks": n_blocks, "minShare": min_share, "rows": rows}, off, pairs[:, 0].copy(), pairs[:, 1].copy()
+
+
+_SB_RECORD = np.dtype([("len", "<u8"), ("moshes", "<u4"), ("found", "<u4"), ("query", "<u4"), ("reserved", "<u4")])
+
+
+def read_seq_blocks(path):
+    """A --seqBlocks file (magic "10XQ", u32 version 1, u32 nBlocks, u32 minShare, u64 nSeq, u64 rows, u64 nameBytes; rows pairs {u32 block,
+    u32 count}; nSeq records {u64 len, u32 moshes, u32 found, u32 query, u32 0}; nSeq + 1 u64 offsets; nSeq + 1 u64 name offsets; the names,
+    NUL-terminated; little-endian; needs no device): ({"version", "nBlocks", "minShare", "nSeq", "rows", "nameBytes"}, offsets, block, count,
+    table, names). The row of sequence s is [offsets[s], offsets[s + 1]). Raises Hash10xError for a file that is not one or does not hold
+    together: the sizes against the file's length, both offset arrays, blocks ascending within a row and below nBlocks, counts >= minShare."""
+    with open(path, "rb") as f:
+        data = f.read()
+    if len(data) < 40 or data[:4] != b"10XQ":
+        raise Hash10xError("%s: not a seq blocks file (magic 10XQ)" % path)
+    version, n_blocks, min_share = (int(v) for v in np.frombuffer(data, dtype="<u4", count=3, offset=4))
+    n_seq, rows, name_bytes = (int(v) for v in np.frombuffer(data, dtype="<u8", count=3, offset=16))
+    if version != 1:
+        raise Hash10xError("%s: seq blocks version %d, this reader knows 1" % (path, version))
+    need = 40 + 8 * rows + 24 * n_seq + 16 * (n_seq + 1) + name_bytes
+    if len(data) != need:
+        raise Hash10xError("%s: %d bytes, %d sequences, %d rows and %d name bytes need %d" % (path, len(data), n_seq, rows, name_bytes, need))
+    at = 40
+    pairs = np.frombuffer(data, dtype="<u4", count=2 * rows, offset=at).reshape(-1, 2); at += 8 * rows
+    table = np.frombuffer(data, dtype=_SB_RECORD, count=n_seq, offset=at).copy(); at += 24 * n_seq
+    off = np.frombuffer(data, dtype="<u8", count=n_seq + 1, offset=at).copy(); at += 8 * (n_seq + 1)
+    name_off = np.frombuffer(data, dtype="<u8", count=n_seq + 1, offset=at).copy(); at += 8 * (n_seq + 1)
+    blob = data[at:]
+    if off[0] != 0 or int(off[-1]) != rows or np.any(off[1:] < off[:-1]):
+        raise Hash10xError("%s: the offsets do not ascend from 0 to the %d rows" % (path, rows))
+    if name_off[0] != 0 or int(name_off[-1]) != name_bytes or np.any(name_off[1:] <= name_off[:-1]):
+        raise Hash10xError("%s: the name offsets do not ascend from 0 to the %d name bytes" % (path, name_bytes))
+    if any(blob[int(e) - 1] != 0 for e in name_off[1:]):
+        raise Hash10xError("%s: a name does not end in NUL" % path)
+    blk, cnt = pairs[:, 0].copy(), pairs[:, 1].copy()
+    if rows:
+        if int(blk.max()) >= n_blocks:
+            raise Hash10xError("%s: a row's block is beyond the %d blocks" % (path, n_blocks))
+        if int(cnt.min()) < max(min_share, 1):
+            raise Hash10xError("%s: a row's count is below minShare %d" % (path, min_share))
+        inner = np.ones(rows, dtype=bool)
+        inner[off[:-1][off[:-1] < rows].astype(np.int64)] = False   # the first entry of a row has no predecessor in it
+        if np.any(inner[1:] & (blk[1:] <= blk[:-1])):
+            raise Hash10xError("%s: the blocks of a row do not ascend" % path)
+    if np.any(table["reserved"] != 0):
+        raise Hash10xError("%s: a reserved word of the table is not 0" % path)
+    names = [blob[int(a):int(b) - 1].decode(errors="replace") for a, b in zip(name_off[:-1], name_off[1:])]
+    info = {"version": version, "nBlocks": n_blocks, "minShare": min_share, "nSeq": n_seq, "rows": rows, "nameBytes": name_bytes}
+    return info, off, blk, cnt, table, names
 
 
 _SHARE_COMPONENTS_INFO = np.dtype([("rows", "<u8"), ("listEntries", "<u8"), ("nBlocks", "<u4"), ("minShare", "<u4"), ("nComponents", "<u4"), ("largest", "<u4"),

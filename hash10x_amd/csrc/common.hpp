@@ -262,6 +262,12 @@ struct Ctx {
   // the per-hash linkage groups of the last h10x_hash_copies_run (stage_n.hip), kept until the next run, a new depth range, --clusterSplit or a new state:
   // hcOut = hcHashes records {u16 distinct, groups, largest, second}; hcTally[3 * t + k] = the counts per crib type t, [15] = the deepest in-range list
   DevBuf<u32> hcOut; u32 hcHashes = 0; bool haveHashCopies = false; u64 hcTally[16] = {}; h10x_hash_copies_info hcInfo{};
+  // from sequences to blocks (stage_p.hip). The query lists of the last h10x_seq_hashes / h10x_seq_blocks_run: sqHash = the distinct in-range hash indices of
+  // sequence s at [sqOffsets[s], sqOffsets[s + 1]) (sqHostOff: the same offsets on the host). The rows of the last h10x_list_share_run / h10x_seq_blocks_run:
+  // (block, count) of list q at [sbOffsets[q], sbOffsets[q + 1]). Both kept until the next run, a new depth range, --clusterSplit or a new state
+  DevBuf<u32> sqHash; DevBuf<u64> sqOffsets; std::vector<u64> sqHostOff; u64 sqEntries = 0; u32 sqSeqs = 0; bool haveSeqHashes = false;
+  DevBuf<u32> sbBlock, sbCount; DevBuf<u64> sbOffsets; u64 sbRows = 0; u32 sbLists = 0; bool haveSeqBlocks = false;
+  int64_t optSeqSlab = 0;     // bases per device batch of the sequence layer (0 = the mosh sets' default, 2^26); results do not depend on it
   // the -r value prm.factor1 was drawn from (option "seqhash_seed"): a mosh set made from the state carries the hasher's second multiplier too (stage_o.hip)
   int32_t seed = 0; bool haveSeed = false;
   // streaming ingest (h10x_ingest_fqb): the record image grows on the device as the chunks arrive
@@ -500,6 +506,13 @@ int stageN_get(Ctx *c, uint16_t *out, u64 first, u64 count, int toDevice);
 int stageN_tally(Ctx *c, u64 *counts15);
 void stageN_release(Ctx *c);
 inline void release_share_results(Ctx *c) { stageL_release(c); stageM_release(c); stageN_release(c); }   // the kept graph, components and hash copies
+// from sequences to blocks (stage_p.hip): the query lists of sequences, the census over lists, and both in one
+int stageP_seqHashes(Ctx *c, const u8 *codes, const u64 *seqStart, u32 nSeq, h10x_seq_figures *fig);
+int stageP_seqHashesGet(Ctx *c, u64 *offsets, u32 *hashes, u64 cap);
+int stageP_listShare(Ctx *c, int64_t minShare, const u64 *offsets, const u32 *hashes, u32 nq, h10x_list_share_info *info);
+int stageP_seqBlocks(Ctx *c, int64_t minShare, const u8 *codes, const u64 *seqStart, u32 nSeq, h10x_seq_figures *fig, h10x_list_share_info *info);
+int stageP_get(Ctx *c, u64 *offsets, u32 *block, u32 *count, u64 cap, int toDevice);
+void stageP_release(Ctx *c);
 int stageJ_censusBegin(Ctx *c, u64 hint);
 int stageJ_censusAdd(Ctx *c, const u32 *dRec, u64 n);
 int stageJ_censusClose(Ctx *c, int64_t thresh, h10x_census_t *out);

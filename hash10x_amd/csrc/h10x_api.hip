@@ -237,7 +237,7 @@ const char *h10x_last_error(const h10x_ctx *h) { return h ? h->c.err.c_str() : "
 
 static void reset_state(Ctx &c) {
   c.haveState = false; c.haveRange = false; c.haveGood = false; c.rangeMin = c.rangeMax = 0; c.depthBound = 0xFFFFFFFFu; c.rangeHiMax = 0;
-  release_share_results(&c);
+  release_share_results(&c); stageP_release(&c);
   c.within.release(); c.goodPos.release(); c.nGood.release(); c.goodEntries.release(); c.goodRow.release();
   // the tables of the state being replaced go back to the block cache NOW, not when their successors are swapped in: the second --readFQB of a
   // context then finds every block of the first one parked and allocates nothing (kept until the swap, rows[] and clusHash had no twin in the
@@ -408,6 +408,7 @@ int h10x_depth_range(h10x_ctx *h, int32_t lo, int32_t hi) {
   if (!h) return -1;
   H10X_TRY(enter(h->c));
   release_share_results(&h->c);   // a kept share graph, kept components and kept hash copies are of the lists this call replaces
+  stageP_release(&h->c);          // (so are the query lists and rows of sequences)
   return stageC_depthRange(&h->c, lo, hi);
 }
 
@@ -421,6 +422,7 @@ int h10x_cluster_split(h10x_ctx *h) {
   if (!h) return -1;
   H10X_TRY(enter(h->c));
   release_share_results(&h->c);   // (and of the blocks this call renumbers)
+  stageP_release(&h->c);
   return stageC_split(&h->c);
 }
 
@@ -702,6 +704,27 @@ int h10x_hash_copies_get_device(h10x_ctx *h, uint16_t *devOut, uint64_t first, u
   if (!h) return -1; H10X_TRY(enter(h->c)); return stageN_get(&h->c, devOut, first, count, 1);
 }
 int h10x_hash_copies_tally(h10x_ctx *h, uint64_t counts[5][3]) { if (!h || !counts) return -1; H10X_TRY(enter(h->c)); return stageN_tally(&h->c, (u64 *)&counts[0][0]); }
+
+// ---- from sequences to blocks (stage_p.hip) ----
+int h10x_seq_hashes(h10x_ctx *h, const uint8_t *codes, const uint64_t *seqStart, uint32_t nSeq, h10x_seq_figures *figures) {
+  if (!h) return -1; H10X_TRY(enter(h->c)); return stageP_seqHashes(&h->c, codes, (const u64 *)seqStart, nSeq, figures);
+}
+int h10x_seq_hashes_get(h10x_ctx *h, uint64_t *offsets, uint32_t *hashes, uint64_t cap) {
+  if (!h) return -1; H10X_TRY(enter(h->c)); return stageP_seqHashesGet(&h->c, (u64 *)offsets, hashes, cap);
+}
+int h10x_list_share_run(h10x_ctx *h, int64_t minShare, const uint64_t *offsets, const uint32_t *hashes, uint32_t nq, h10x_list_share_info *info) {
+  if (!h || !info) return -1; H10X_TRY(enter(h->c)); return stageP_listShare(&h->c, minShare, (const u64 *)offsets, hashes, nq, info);
+}
+int h10x_seq_blocks_run(h10x_ctx *h, int64_t minShare, const uint8_t *codes, const uint64_t *seqStart, uint32_t nSeq, h10x_seq_figures *figures,
+                        h10x_list_share_info *info) {
+  if (!h || !info) return -1; H10X_TRY(enter(h->c)); return stageP_seqBlocks(&h->c, minShare, codes, (const u64 *)seqStart, nSeq, figures, info);
+}
+int h10x_list_share_get(h10x_ctx *h, uint64_t *offsets, uint32_t *block, uint32_t *count, uint64_t cap) {
+  if (!h) return -1; H10X_TRY(enter(h->c)); return stageP_get(&h->c, (u64 *)offsets, block, count, cap, 0);
+}
+int h10x_list_share_get_device(h10x_ctx *h, uint64_t *devOffsets, uint32_t *devBlock, uint32_t *devCount, uint64_t cap) {
+  if (!h) return -1; H10X_TRY(enter(h->c)); return stageP_get(&h->c, (u64 *)devOffsets, devBlock, devCount, cap, 1);
+}
 
 int h10x_timing_enable(h10x_ctx *h, int on) { if (!h) return -1; h->c.timing = on != 0; return 0; }
 int h10x_timing_count(const h10x_ctx *) { return T_COUNT; }
@@ -1001,6 +1024,7 @@ int h10x_set_option(h10x_ctx *h, const char *name, int64_t value) {
   if (!strcmp(name, "molmap_global")) { if (value < 0 || value > 1) return h->c.fail("molmap_global must be 0 or 1"); h->c.optMolGlobal = value; return 0; }
   if (!strcmp(name, "fqb_slab")) { if (value < 0 || value > (1 << 28)) return h->c.fail("fqb_slab must be 0..2^28"); h->c.optFqbSlab = value; return 0; }
   if (!strcmp(name, "seqhash_seed")) { h->c.seed = (int32_t)value; h->c.haveSeed = true; return 0; }   // the -r value: checked against prm.factor1 where it is used (stage_o.hip)
+  if (!strcmp(name, "seq_slab")) { if (value < 0) return h->c.fail("seq_slab must be >= 0"); h->c.optSeqSlab = value; return 0; }
   if (!strcmp(name, "neighbour_budget")) { if (value < 0) return h->c.fail("neighbour_budget must be >= 0"); h->c.optNbBudget = value; return 0; }
   return h->c.fail("unknown option %s", name);
 }

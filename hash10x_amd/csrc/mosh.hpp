@@ -45,6 +45,10 @@ int moshPlace(Mosh *m, u32 D);
 
 // one uploaded batch and the list its scan left (stage_g.hip)
 struct MoshBatch { DevBuf<u8> codes; DevBuf<u64> seq, run, tallies, outHash; DevBuf<u32> outOrd; u64 nRuns = 0, total = 0, listed = 0, found = 0; };
+// the scan of one batch with a hasher given as arguments, on the stream of any context: acc = null lists every mosh in b.outHash / b.outOrd (in no
+// order; b.listed of them), else the moshes found in c's table count in acc[accSize] and only the others are listed (stage_g.hip; stage_p.hip)
+int moshScanWith(Ctx *c, int k, int w, u64 factor1, int B, u32 *acc, u32 accSize, MoshBatch &b, const u8 *codes, const u64 *seqStart, u32 nSeq, int skipOdd,
+                 u64 seqBase);
 int moshIota(Mosh *m, u32 *v, u64 n);
 int moshScanOrdered(Mosh *m, MoshBatch &b, DevBuf<u64> &sh, DevBuf<u32> &so, const u8 *codes, const u64 *seqStart, u32 nSeq, int skipOdd, u64 seqBase);
 

@@ -332,8 +332,10 @@ int moshPlace(Mosh *m, u32 D) {
 }
 
 // upload a batch and run the scan; the list is sized by an estimate and the scan repeated with the exact size if it was too small
-static int moshScanBatch(Mosh *m, MoshBatch &b, const u8 *codes, const u64 *seqStart, u32 nSeq, int skipOdd, u64 seqBase, bool add) {
-  Ctx *c = &m->c; hipStream_t st = c->stream; const int k = m->k;
+// (the hasher and the table are arguments: stage_p.hip scans with a context's hasher and no set; acc = null lists every mosh)
+int moshScanWith(Ctx *c, int k, int w, u64 factor1, int B, u32 *acc, u32 accSize, MoshBatch &b, const u8 *codes, const u64 *seqStart, u32 nSeq, int skipOdd,
+                 u64 seqBase) {
+  hipStream_t st = c->stream; const bool add = acc != nullptr;
   const u64 base = seqStart[0];
   std::vector<u64> rel((size_t)nSeq + 1), runStart((size_t)nSeq + 1, 0);
   struct SyncOnExit { hipStream_t s; ~SyncOnExit() { (void)hipStreamSynchronize(s); } } guard{st};   // every way out waits for the copies from the two vectors above
@@ -355,14 +357,14 @@ static int moshScanBatch(Mosh *m, MoshBatch &b, const u8 *codes, const u64 *seqS
   H10X_HIP(c, hipMemcpyAsync(b.codes.p, codes + base, b.total, hipMemcpyHostToDevice, st));
   H10X_HIP(c, hipMemcpyAsync(b.seq.p, rel.data(), ((size_t)nSeq + 1) * 8, hipMemcpyHostToDevice, st));
   H10X_HIP(c, hipMemcpyAsync(b.run.p, runStart.data(), ((size_t)nSeq + 1) * 8, hipMemcpyHostToDevice, st));
-  u64 cap = hmin<u64>(nK, 2 * (nK / (u64)m->w) + ((u64)1 << 16));
+  u64 cap = hmin<u64>(nK, 2 * (nK / (u64)w) + ((u64)1 << 16));
   const unsigned grid = (unsigned)hmin<u64>(divUp(b.nRuns, 256), (u64)c->numCU * 16);
   for (int attempt = 0; attempt < 2; ++attempt) {
     H10X_HIP(c, b.outHash.alloc(cap)); H10X_HIP(c, b.outOrd.alloc(cap));
     H10X_HIP(c, hipMemsetAsync(b.tallies.p, 0, 16, st));
-    if (add) mosh_scan_kernel<1><<<grid, 256, 0, st>>>(b.codes.p, b.seq.p, b.run.p, nSeq, skipOdd, seqBase, k, m->w, m->factor1, c->hashIndex.p, c->hashValue.p, m->B,
-                                                       m->acc.p, b.outHash.p, b.outOrd.p, cap, b.tallies.p);
-    else mosh_scan_kernel<0><<<grid, 256, 0, st>>>(b.codes.p, b.seq.p, b.run.p, nSeq, skipOdd, seqBase, k, m->w, m->factor1, nullptr, nullptr, m->B,
+    if (add) mosh_scan_kernel<1><<<grid, 256, 0, st>>>(b.codes.p, b.seq.p, b.run.p, nSeq, skipOdd, seqBase, k, w, factor1, c->hashIndex.p, c->hashValue.p, B,
+                                                       acc, b.outHash.p, b.outOrd.p, cap, b.tallies.p);
+    else mosh_scan_kernel<0><<<grid, 256, 0, st>>>(b.codes.p, b.seq.p, b.run.p, nSeq, skipOdd, seqBase, k, w, factor1, nullptr, nullptr, B,
                                                    nullptr, b.outHash.p, b.outOrd.p, cap, b.tallies.p);
     H10X_HIP(c, hipGetLastError());
     u64 ht[2];
@@ -372,9 +374,13 @@ static int moshScanBatch(Mosh *m, MoshBatch &b, const u8 *codes, const u64 *seqS
     if (b.listed <= cap) return 0;
     if (attempt) break;
     cap = b.listed;                                          // the estimate was too small: once more with the exact size
-    if (add) H10X_HIP(c, hipMemsetAsync(m->acc.p, 0, (size_t)m->size * 4, st));   // (acc[] is all zero between batches)
+    if (add) H10X_HIP(c, hipMemsetAsync(acc, 0, (size_t)accSize * 4, st));   // (acc[] is all zero between batches)
   }
   return c->fail("mosh scan: the list overflowed twice");
+}
+
+static int moshScanBatch(Mosh *m, MoshBatch &b, const u8 *codes, const u64 *seqStart, u32 nSeq, int skipOdd, u64 seqBase, bool add) {
+  return moshScanWith(&m->c, m->k, m->w, m->factor1, m->B, add ? m->acc.p : nullptr, m->size, b, codes, seqStart, nSeq, skipOdd, seqBase);
 }
 
 // addSequence over a batch of whole sequences (moshutils.c:19-30, 41-45)

@@ -17,7 +17,7 @@
 #define ARRAY_MAGIC 8918274                            /* array.h:56 */
 typedef struct { int32_t magic, pad0; uint64_t base; int32_t dim, size, max, pad1; } array_hdr;   /* array.h:41-50 */
 
-enum { N_KNOBS = 23 };
+enum { N_KNOBS = 24 };
 struct h10x_session {
   int k, w, r, B, N, chunk, ct, device;                /* params (hash10x.c:25-33) */
   int timing;                                          /* measurement hook: enable hipEvent timers on every new context */
@@ -32,7 +32,7 @@ struct h10x_session {
   char err[1024];
 };
 static const char *const knobName[N_KNOBS] = {"cluster_stamps", "cluster_lds_budget", "cluster_first_global", "cluster_first_cap",
-                                              "cluster_big_ranks", "cluster_threads0", "cluster_budget0", "shard_row_shift", "shard_rows_fake_base", "stage_a_max_slots", "cluster_narrow_first", "index_no_pack", "shard_delta_lists", "index_priv_table", "cluster_tr_packed", "cluster_tr_est_div", "cluster_tr_class_t", "shard_reply_sort", "shard_owner_cut", "shard_overlap", "index_probed_table", "fqb_slab", "molmap_global"};
+                                              "cluster_big_ranks", "cluster_threads0", "cluster_budget0", "shard_row_shift", "shard_rows_fake_base", "stage_a_max_slots", "cluster_narrow_first", "index_no_pack", "shard_delta_lists", "index_priv_table", "cluster_tr_packed", "cluster_tr_est_div", "cluster_tr_class_t", "shard_reply_sort", "shard_owner_cut", "shard_overlap", "index_probed_table", "fqb_slab", "molmap_global", "seq_slab"};
 
 static int fail(h10x_session *s, const char *fmt, ...) {
   va_list ap; va_start(ap, fmt); vsnprintf(s->err, sizeof s->err, fmt, ap); va_end(ap);
@@ -1951,4 +1951,130 @@ done:
   free(part);
   h10x_mosh_destroy(set);
   return rc;
+}
+
+/* ---- --seqBlocks <minShare> <seqfile> <out.sb>: per sequence of a file the blocks whose barcode lists hold its in-range hashes (h10x_seq_blocks_run).
+   The writer has three parts: the rows of each slab go to <out.sb>.part as they come; the per-sequence table, the offsets and the names are kept on the
+   host and written at the end, with the header; then the file takes its name. ---- */
+static int sb_grow(void **p, size_t *cap, size_t need, size_t elt) {
+  if (need <= *cap) return 0;
+  size_t n = *cap ? *cap : 64; while (n < need) n *= 2;
+  void *q = realloc(*p, n * elt); if (!q) return -1;
+  *p = q; *cap = n;
+  return 0;
+}
+
+int h10x_host_write_seq_blocks(const char *path, uint32_t nBlocks, uint32_t minShare, h10x_seq_blocks_slab_fn next, void *user, FILE *verbose,
+                               h10x_seq_blocks_totals *totals, char *err, int errlen) {
+  typedef struct { uint64_t len; uint32_t moshes, found, query, reserved; } Rec;
+  h10x_seq_blocks_totals t; memset(&t, 0, sizeof t);
+  Rec *table = 0; uint64_t *offsets = 0, *nameOff = 0; char *names = 0; uint32_t *pair = 0;
+  size_t capTable = 0, capOff = 0, capNameOff = 0, capNames = 0, capPair = 0; uint64_t nameBytes = 0;
+  int rc = 0; FILE *f = 0;
+  const size_t plen = strlen(path);
+  char *part = (char *)malloc(plen + 6);
+  if (!part) { snprintf(err, (size_t)errlen, "out of host memory"); return -1; }
+  memcpy(part, path, plen); memcpy(part + plen, ".part", 6);
+  if (!(f = fopen(part, "wb"))) { snprintf(err, (size_t)errlen, "failed to open output file %s", path); free(part); return -1; }
+  unsigned char head[40]; memset(head, 0, sizeof head);
+  if (fwrite(head, 1, sizeof head, f) != sizeof head) goto cannot_write;
+  if (sb_grow((void **)&offsets, &capOff, 1, 8) || sb_grow((void **)&nameOff, &capNameOff, 1, 8)) goto no_memory;
+  offsets[0] = 0; nameOff[0] = 0;
+  for (;;) {
+    h10x_seq_blocks_slab b; memset(&b, 0, sizeof b);
+    const int got = next(user, &b);
+    if (got < 0) { rc = -2; goto done; }                              /* the callback's own error stands */
+    if (!got) break;
+    const uint64_t rows = b.nSeq ? b.rowOff[b.nSeq] : 0;
+    if (sb_grow((void **)&table, &capTable, (size_t)(t.nSeq + b.nSeq), sizeof(Rec)) || sb_grow((void **)&offsets, &capOff, (size_t)(t.nSeq + b.nSeq + 1), 8) ||
+        sb_grow((void **)&nameOff, &capNameOff, (size_t)(t.nSeq + b.nSeq + 1), 8) || sb_grow((void **)&pair, &capPair, (size_t)rows, 8)) goto no_memory;
+    for (uint64_t i = 0; i < rows; ++i) { pair[2 * i] = b.block[i]; pair[2 * i + 1] = b.count[i]; }
+    if (rows && fwrite(pair, 8, (size_t)rows, f) != (size_t)rows) goto cannot_write;
+    for (uint32_t q = 0; q < b.nSeq; ++q) {
+      const uint64_t at = t.nSeq + q, len = b.seqStart[q + 1] - b.seqStart[q], r0 = b.rowOff[q], r1 = b.rowOff[q + 1];
+      const h10x_seq_figures *g = b.fig + q;
+      Rec rec = {len, g->moshes, g->found, g->query, 0};
+      table[at] = rec;
+      offsets[at + 1] = t.rows + r1;
+      const char *name = b.names + b.nameOff[q]; const size_t nl = strlen(name) + 1;
+      if (sb_grow((void **)&names, &capNames, (size_t)nameBytes + nl, 1)) goto no_memory;
+      memcpy(names + nameBytes, name, nl); nameBytes += nl; nameOff[at + 1] = nameBytes;
+      uint32_t best = 0, bestCount = 0;
+      for (uint64_t i = r0; i < r1; ++i) if (b.count[i] > bestCount) { bestCount = b.count[i]; best = b.block[i]; }
+      if (verbose) fprintf(verbose, "SEQ_BLOCKS  %s len %llu moshes %u found %u query %u rows %llu best %u count %u\n", name, (unsigned long long)len,
+                           g->moshes, g->found, g->query, (unsigned long long)(r1 - r0), best, bestCount);
+      t.bases += len; t.moshes += g->moshes; t.found += g->found; t.query += g->query;
+      if (r1 > r0) ++t.withRows;
+      if (bestCount > t.maxCount) t.maxCount = bestCount;
+    }
+    t.nSeq += b.nSeq; t.rows += rows;
+  }
+  {
+    const uint32_t version = 1;
+    if ((t.nSeq && fwrite(table, sizeof(Rec), (size_t)t.nSeq, f) != (size_t)t.nSeq) || fwrite(offsets, 8, (size_t)t.nSeq + 1, f) != (size_t)t.nSeq + 1 ||
+        fwrite(nameOff, 8, (size_t)t.nSeq + 1, f) != (size_t)t.nSeq + 1 || (nameBytes && fwrite(names, 1, (size_t)nameBytes, f) != (size_t)nameBytes)) goto cannot_write;
+    memcpy(head, "10XQ", 4); memcpy(head + 4, &version, 4); memcpy(head + 8, &nBlocks, 4); memcpy(head + 12, &minShare, 4);
+    memcpy(head + 16, &t.nSeq, 8); memcpy(head + 24, &t.rows, 8); memcpy(head + 32, &nameBytes, 8);
+    if (fseeko(f, 0, SEEK_SET) || fwrite(head, 1, sizeof head, f) != sizeof head) goto cannot_write;
+    const int closed = fclose(f); f = 0;
+    if (closed) goto cannot_write;
+    if (rename(part, path)) goto cannot_write;
+  }
+  if (totals) *totals = t;
+  goto done;
+no_memory:
+  snprintf(err, (size_t)errlen, "out of host memory for the table of %llu sequences", (unsigned long long)t.nSeq); rc = -1; goto done;
+cannot_write:
+  snprintf(err, (size_t)errlen, "failed to write %s", path); rc = -1;
+done:
+  if (f) fclose(f);
+  if (rc) remove(part);
+  free(part); free(table); free(offsets); free(nameOff); free(names); free(pair);
+  return rc;
+}
+
+typedef struct {
+  h10x_session *s; h10x_seqreader *r; int minShare; uint64_t slab;
+  h10x_seq_figures *fig; uint64_t *rowOff; uint32_t *block, *count; size_t capSeq, capOff, capRows;
+} SbFeed;
+
+static int sb_next_from_file(void *user, h10x_seq_blocks_slab *b) {
+  SbFeed *z = (SbFeed *)user; h10x_session *s = z->s;
+  const uint8_t *codes; const uint64_t *seqStart, *nameOff; const char *names; uint32_t nSeq = 0;
+  const int got = h10x_seq_next_named(z->r, z->slab, &codes, &seqStart, &nSeq, &names, &nameOff);
+  if (got < 0) return fail(s, "%s", h10x_seq_error(z->r));
+  if (!got) return 0;
+  if (sb_grow((void **)&z->fig, &z->capSeq, (size_t)nSeq + 1, sizeof *z->fig)) return fail(s, "out of host memory for %u sequences", nSeq);
+  if (sb_grow((void **)&z->rowOff, &z->capOff, (size_t)nSeq + 1, 8)) return fail(s, "out of host memory for %u sequences", nSeq);
+  h10x_list_share_info info;
+  if (h10x_seq_blocks_run(s->ctx, z->minShare, codes, seqStart, nSeq, z->fig, &info)) return fail_ctx(s);
+  if (info.rows > z->capRows) {
+    free(z->block); free(z->count);
+    z->capRows = (size_t)(info.rows + info.rows / 2);
+    z->block = (uint32_t *)malloc(z->capRows * 4); z->count = (uint32_t *)malloc(z->capRows * 4);
+    if (!z->block || !z->count) { z->capRows = 0; return fail(s, "out of host memory for %llu rows", (unsigned long long)info.rows); }
+  }
+  if (h10x_list_share_get(s->ctx, z->rowOff, z->block, z->count, info.rows)) return fail_ctx(s);
+  b->nSeq = nSeq; b->seqStart = seqStart; b->fig = z->fig; b->rowOff = z->rowOff; b->block = z->block; b->count = z->count; b->names = names; b->nameOff = nameOff;
+  return 1;
+}
+
+int h10x_session_seqBlocks(h10x_session *s, int minShare, const char *seqPath, const char *outPath, FILE *out, int verbose) {
+  if (!s->ctx) return fail(s, "!! you must set hashDepthRange before seqBlocks");       /* nothing loaded: no range either */
+  h10x_shard_info_t sh; if (h10x_shard_info(s->ctx, &sh)) return fail_ctx(s);
+  if (sh.nranks > 1) return fail(s, "seqBlocks does not run on a sharded session (--gpus > 1)");
+  h10x_list_share_info info;
+  if (h10x_seq_blocks_run(s->ctx, minShare, 0, 0, 0, 0, &info)) return fail_ctx(s);     /* the refusals, before any file is touched */
+  char msg[512] = ""; int fatal = 0;
+  SbFeed z; memset(&z, 0, sizeof z);
+  z.s = s; z.minShare = minShare; { const int v = h10x_session_get(s, "seq_slab"); z.slab = v > 0 ? (uint64_t)v : 0; }
+  if (!(z.r = h10x_seq_open(seqPath, msg, (int)sizeof msg, &fatal))) return fail(s, "%s%sfailed to open sequence file %s", msg, msg[0] ? "\n" : "", seqPath);
+  h10x_seq_blocks_totals t;
+  const int w = h10x_host_write_seq_blocks(outPath, info.nBlocks, (uint32_t)minShare, sb_next_from_file, &z, verbose ? out : 0, &t, s->err, (int)sizeof s->err);
+  h10x_seq_close(z.r); free(z.fig); free(z.rowOff); free(z.block); free(z.count);
+  if (w) return -1;                                                                       /* (-2: the callback has set the session's text) */
+  if (out) fprintf(out, "  seq blocks at minShare %d: %llu sequences, %llu bases, %llu moshes, %llu found, %llu in range, %llu rows, %llu sequences with rows, max count %u\n",
+                   minShare, (unsigned long long)t.nSeq, (unsigned long long)t.bases, (unsigned long long)t.moshes, (unsigned long long)t.found,
+                   (unsigned long long)t.query, (unsigned long long)t.rows, (unsigned long long)t.withRows, t.maxCount);
+  return 0;
 }

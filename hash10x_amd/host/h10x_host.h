@@ -148,6 +148,33 @@ int  h10x_session_hashCopiesRun(h10x_session *s, int minShare, h10x_hash_copies_
 int  h10x_host_write_hash_copies(const char *path, const h10x_hash_copies_info *info, h10x_hash_copies_slab_fn slab, void *user, uint64_t slabHashes,
                                  char *err, int errlen);
 
+/* --seqBlocks <minShare> <seqfile> <out.sb> (addition; include/h10x.h "from a sequence to its blocks"): per sequence of a FASTA / FASTQ file (gzip or
+   plain) the blocks that stand at least minShare times in the barcode lists of its in-range hashes. The file is read through h10x_seq_next_named in
+   slabs of "seq_slab" bases (h10x_session_set; 0 = 2^26; a longer sequence goes alone), each slab runs through h10x_seq_blocks_run and its rows are
+   appended to the file at once, so neither the host nor the device holds all rows; the per-sequence table and the names stay on the host until the end.
+   The file is written as <out.sb>.part and renamed when whole. Little-endian: "10XQ", u32 version 1, u32 nBlocks, u32 minShare, u64 nSeq, u64 rows,
+   u64 nameBytes (filled in at the end); rows pairs {u32 block, u32 count}; nSeq records {u64 len, u32 moshes, u32 found, u32 query, u32 0};
+   nSeq + 1 u64 offsets; nSeq + 1 u64 name offsets; the names, NUL-terminated, cut at the first blank or tab.
+   out gets one line of counts; verbose != 0 adds one SEQ_BLOCKS line per sequence: name, len, moshes, found, query, rows, the block of the largest
+   count (lowest on ties; 0 without rows) and that count. Soft errors as --shareGraph: no state or no range ("!! you must set hashDepthRange before
+   seqBlocks"), "!! seqBlocks minShare 0 must be >= 1"; a sequence file or an output path that cannot be opened fails without "!!". In every failure no
+   file is written and no .part is left behind.
+   h10x_host_write_seq_blocks is the writer alone, fed by a callback that yields one slab after the other (1 = a slab, 0 = no more, < 0 = failed); it
+   returns -2 when the callback failed (err untouched), -1 with err set for its own failures. */
+typedef struct {
+  uint32_t nSeq;
+  const uint64_t *seqStart;                  /* nSeq + 1: sequence s has seqStart[s + 1] - seqStart[s] bases */
+  const h10x_seq_figures *fig;               /* nSeq */
+  const uint64_t *rowOff;                    /* nSeq + 1: the slab's rows, from 0 */
+  const uint32_t *block, *count;             /* rowOff[nSeq] each */
+  const char *names; const uint64_t *nameOff;   /* sequence s is called names + nameOff[s] */
+} h10x_seq_blocks_slab;
+typedef struct { uint64_t nSeq, bases, moshes, found, query, rows, withRows; uint32_t maxCount, reserved; } h10x_seq_blocks_totals;
+typedef int (*h10x_seq_blocks_slab_fn)(void *user, h10x_seq_blocks_slab *slab);
+int  h10x_host_write_seq_blocks(const char *path, uint32_t nBlocks, uint32_t minShare, h10x_seq_blocks_slab_fn next, void *user, FILE *verbose,
+                                h10x_seq_blocks_totals *totals, char *err, int errlen);
+int  h10x_session_seqBlocks(h10x_session *s, int minShare, const char *seqPath, const char *outPath, FILE *out, int verbose);
+
 /* --writeMosh <bits> <copy1min> <copy2min> <copyMmin> <out.mosh> (addition; include/h10x.h "the state as a mosh set"): the in-range hashes of the state as
    an MSHSTv1 file that moshutils, moshasm and moshmap read: the state's hash values, depths saturated to 16 bits, copy classes from depth by the three
    thresholds of moshutils -s and, where a --hashCopies result is kept, corrected by linkage. bits = the table bits of the set, 0 = the state's -B. The file

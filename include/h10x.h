@@ -25,7 +25,7 @@ extern "C" {
 /* 2 (round 5): h10x_warm, h10x_alloc_stats, h10x_pinned_*, h10x_ingest_fqb_async / _wait, H10X_TABLE_CLUSTER_RAW, the exchange counters of
    h10x_counters; option "cluster_dbg_skip" gone.
    3: h10x_counters.shard_reply_path, options "shard_reply_sort" 2 .. 4 and "shard_owner_cut". Entry points added since (the census, share graph, components,
-   hash copies, mosh sets, readsets, reference maps, h10x_mosh_from_state) change no existing struct or table and leave the version alone.
+   hash copies, mosh sets, readsets, reference maps, h10x_mosh_from_state, h10x_seq_hashes / h10x_list_share_* / h10x_seq_blocks_run) change no existing struct or table and leave the version alone.
    libh10x_host.so and the Python loader refuse a libh10x_hip.so of another version. */
 #define H10X_ABI_VERSION 3
 
@@ -594,6 +594,56 @@ typedef struct {
 } h10x_state_mosh_info;
 int  h10x_mosh_from_state(h10x_ctx *ctx, int32_t bits, int32_t copy1min, int32_t copy2min, int32_t copyMmin, h10x_mosh **set, h10x_state_mosh_info *info);
 
+/* ---- from a sequence to its blocks (csrc/stage_p.hip): which blocks' barcode lists hold the hashes of a contig or a long read ----
+   State: a loaded, unsharded context with a --hashDepthRange in force; --cluster / --clusterSplit may or may not have run. The blocks are the
+   current ones: after --clusterSplit and a new range they are the molecules.
+   Hasher: the context's k, w and the seed it learnt through option "seqhash_seed", exactly as h10x_mosh_from_state takes them (the calls that
+   hash fail without the seed, or if it does not give the context's factor1).
+   Layer 1, sequence -> query list. A sequence s is one byte per base, 0..3, N -> 0 (what h10x_seq_next yields). Its moshes are what
+   moshRCiterator / moshRCnext give (seqhash.c:154-195), as h10x_mosh_scan yields them. Each is looked up as hashIndexFind(hash, FALSE)
+   (hash10x.c:139-152) in the state's own table: index x, or 0 if absent. Per sequence (h10x_seq_figures): moshes = occurrences; found =
+   occurrences with x >= 1, in range or not; query = |Q(s)|, Q(s) = the distinct x >= 1 with hashWithinRange[x], ascending (a mosh that occurs
+   twice in s counts once); entries = the sum over Q(s) of hashDepth[x]. A sequence shorter than one window, one of only out-of-range hashes and
+   one with no found hash all have an empty Q(s).
+   Layer 2, query lists -> rows (the list census). Input: nq lists of hash indices in CSR form (offsets[nq + 1], hashes[]); every index must be
+   >= 1 and < hashNumber ("!! listShare list Q entry E: hash index X is not in 1 .. N"). hashWithinRange is NOT applied here: the caller decides
+   which hashes go in. count_q[d] = the number of entries d in the barcode lists of the list's hashes, repeats as the lists hold them, a hash given
+   twice counted twice. No block is left out: a block of more than 65535 records stands in the lists and so in the rows. The result at minShare =
+   T >= 1 is, per list, the row {(d, count_q[d]) : count_q[d] >= T} ascending in d, in CSR form like the share graph. With the good hashes of
+   block c as the list (any order) the row is row c of the share graph at T plus the entry (c, sum over x of G[c,x] M[c,x]) if that reaches T; at
+   T = 1 the counts of a row sum to the list's entries.
+   h10x_seq_hashes is layer 1 for sequences [seqStart[s], seqStart[s + 1]) of codes, s < nSeq, in slabs of option "seq_slab" bases (whole
+     sequences; a longer one goes alone); figures[nSeq] may be NULL. The lists stay on the device; h10x_seq_hashes_get copies out offsets[nSeq + 1]
+     and the first min(cap, offsets[nSeq]) indices (either may be NULL).
+   h10x_list_share_run is layer 2 from host lists: keys (list - first of batch) << bits | d, every (list, hash) unit's place from a scan of the
+     unit sizes, a sort on the bits in use (32-bit keys where list and block fit, else 64-bit) and a run pass that keeps runs of length >= T.
+     Batches are cut by list entries against "neighbour_budget", a list above it runs alone in windows of block index; both are counted in
+     h10x_neighbour_stats. info: rows; listEntries = the entries gathered (the sum of all counts at T = 1); maxCount (0 without rows); batches,
+     windows, and wideBatches = the batches that took 64-bit keys; nBlocks; lists = nq; listHashes = offsets[nq].
+   h10x_seq_blocks_run is both layers, the lists never leaving the device: row s is the row of Q(s). It keeps the lists as h10x_seq_hashes does
+     and the rows as h10x_list_share_run does. figures may be NULL.
+   h10x_list_share_get / _get_device copy the kept rows out as h10x_share_graph_get does: offsets[lists + 1] and the first min(cap, rows) rows.
+   The result depends on none of "seq_slab", "neighbour_budget", the order in which anything lands, or the run: two calls give the same bytes.
+   The kept lists and rows are released by the next run of their kind (also a refused one), h10x_depth_range, h10x_cluster_split, a new state
+   and h10x_destroy; get without them fails. These calls neither release nor change a kept share graph, components or --hashCopies result.
+   They fail without a state, on a sharded context, before --hashDepthRange and after --clusterSplit until a new range ("!! you must set
+   hashDepthRange before seqBlocks" / "listShare" / "seqHashes") and for minShare < 1 ("!! seqBlocks minShare 0 must be >= 1"). */
+typedef struct {
+  uint32_t moshes, found, query, reserved;
+  uint64_t entries;
+} h10x_seq_figures;
+typedef struct {
+  uint64_t rows, listEntries, listHashes;
+  uint32_t maxCount, batches, windows, wideBatches, nBlocks, lists;
+} h10x_list_share_info;
+int  h10x_seq_hashes(h10x_ctx *ctx, const uint8_t *codes, const uint64_t *seqStart, uint32_t nSeq, h10x_seq_figures *figures);
+int  h10x_seq_hashes_get(h10x_ctx *ctx, uint64_t *offsets, uint32_t *hashes, uint64_t cap);
+int  h10x_list_share_run(h10x_ctx *ctx, int64_t minShare, const uint64_t *offsets, const uint32_t *hashes, uint32_t nq, h10x_list_share_info *info);
+int  h10x_seq_blocks_run(h10x_ctx *ctx, int64_t minShare, const uint8_t *codes, const uint64_t *seqStart, uint32_t nSeq, h10x_seq_figures *figures,
+                         h10x_list_share_info *info);
+int  h10x_list_share_get(h10x_ctx *ctx, uint64_t *offsets, uint32_t *block, uint32_t *count, uint64_t cap);
+int  h10x_list_share_get_device(h10x_ctx *ctx, uint64_t *dev_offsets, uint32_t *dev_block, uint32_t *dev_count, uint64_t cap);
+
 /* ---- readsets (csrc/stage_h.hip): the Readset object of the reference's moshasm (moshasm.c) over a mosh set ----
    Long reads kept as their mosh hits only: per read the set indices hit, in position order (top bit = the forward hash was strictly
    the smaller, seqhash.c:67), and the 16-bit distance of each hit to the one before it. Read 0 is the reference's burned entry. The
@@ -769,7 +819,8 @@ int  h10x_get_counters(h10x_ctx *ctx, h10x_counters *out);
    the in-range barcode lists travel delta-coded where bytes are dear — more than one rank on the host-staged TCP backend, not over xGMI; 0 never; 1 always),
    "neighbour_budget" (gathered ClusterHash records per batch of the neighbour census; 0 = default 2^26; small values force batches and hash-index windows),
    "molmap_global" (1 = the molecule map keeps the first-clustered-position table of every clustered block in device memory, also where it fits LDS: tests of that form),
-   "fqb_slab" (records per device batch of h10x_census_add / h10x_fix_fqb and of the session's --codeCensus / --fixFQB / --fixFQBThresh; 0 = default 2^20).
+   "fqb_slab" (records per device batch of h10x_census_add / h10x_fix_fqb and of the session's --codeCensus / --fixFQB / --fixFQBThresh; 0 = default 2^20),
+   "seq_slab" (bases per device batch of h10x_seq_hashes / h10x_seq_blocks_run; 0 = default 2^26; results do not depend on it).
    Not a knob: "seqhash_seed" = the -r value params.factor1 was drawn from (h10x_factor1_from_seed); h10x_mosh_from_state needs it for the second multiplier of the
    set's header, and the session layer sets it. Unknown name: -1. */
 int  h10x_set_option(h10x_ctx *ctx, const char *name, int64_t value);
