@@ -36,6 +36,9 @@ static_assert(sizeof(h10x_clushash) == 8, "ClusterHash layout (hash10x.c:35-43)"
 // Debug knobs: H10X_NOPOOL=1 (plain hipMalloc/hipFree), H10X_POISON=1 (fill every block handed out with 0xA5).
 struct DevCache {
   std::multimap<size_t, void *> parked; size_t parkedBytes = 0;
+  size_t liveBytes = 0;                                     // handed out and not yet released: the device memory the stream's context holds right now (DevBuf)
+  static void noteLive(int device, hipStream_t st, size_t bytes, bool add) { std::lock_guard<std::mutex> g(mu()); size_t &v = of(device, st).liveBytes; v = add ? v + bytes : (v > bytes ? v - bytes : 0); }
+  static size_t live(int device, hipStream_t st) { std::lock_guard<std::mutex> g(mu()); return of(device, st).liveBytes; }
   static std::mutex &mu() { static std::mutex m; return m; }
   // one cache per (device, stream): a parked block may only go back to work issued on the stream that last used it;
   // (device, nullptr) holds blocks whose stream has been synchronised (context destroyed): anyone may take those
@@ -84,7 +87,7 @@ template <typename T> struct DevBuf {
   DevBuf(const DevBuf &) = delete; DevBuf &operator=(const DevBuf &) = delete;
   ~DevBuf() { release(); }
   void release() {
-    if (p) { if (DevCache::disabled()) (void)hipFree(p); else DevCache::park(dev, st, p, cap); }
+    if (p) { DevCache::noteLive(dev, st, cap, false); if (DevCache::disabled()) (void)hipFree(p); else DevCache::park(dev, st, p, cap); }
     p = nullptr; n = 0; cap = 0;
   }
   hipError_t alloc(size_t count) {                       // contents undefined
@@ -102,7 +105,7 @@ template <typename T> struct DevBuf {
       if (e == hipSuccess) { __atomic_fetch_add(&DevCache::freshCalls(), 1, __ATOMIC_RELAXED); __atomic_fetch_add(&DevCache::freshBytes(), (unsigned long long)bytes, __ATOMIC_RELAXED); }
       if (log) { clock_gettime(CLOCK_MONOTONIC, &t1); fprintf(stderr, "h10x alloc: %.1f MB fresh, %.3f ms\n", bytes / 1e6, (t1.tv_sec - t0.tv_sec) * 1e3 + (t1.tv_nsec - t0.tv_nsec) / 1e6); }
     }
-    if (e == hipSuccess) { p = (T *)q; n = count; } else { p = nullptr; cap = 0; }
+    if (e == hipSuccess) { p = (T *)q; n = count; DevCache::noteLive(dev, st, cap, true); } else { p = nullptr; cap = 0; }
     if (e == hipSuccess && DevCache::poison()) (void)hipMemsetAsync(p, 0xA5, bytes, AllocScope::stream());
     return e;
   }
@@ -189,11 +192,16 @@ struct Ctx {
   DevBuf<u32> nGood;          // nBlocks
   DevBuf<u64> goodRow;        // H : per good hash of a block, in rank order: (offset of its barcode list in rows[] >> rowShift, its length) — stage_c_good.hip good_rows_kernel
   DevBuf<u32> goodEntries;    // nBlocks : sum of the depths of a block's good hashes = entries of its barcode lists
+  bool haveClusterRaw = false; // a --cluster has finished on these blocks since clusterRaw was allocated
   DevBuf<u32> clusterRaw;     // 2 x nBlocks, after --cluster: clusters before the read merge (bit 31: given up), good hashes labelled — the --verbose figures of codeClusterFind
   bool haveRange = false, haveGood = false; int rangeMin = 0, rangeMax = 0;
   u32 rangeHiMax = 0;             // largest upper limit of the ranges set so far: an in-range depth is below it
   u32 depthBound = 0xFFFFFFFFu;   // no hashDepth[] value exceeds this: barcodes of the data set after --readFQB, the largest value read after --readHash
-  u32 maxGoodDepth = 0, maxGood = 0, meanGood = 0;
+  u32 maxGoodDepth = 0, maxGood = 0, meanGood = 0;   // read them behind needGoodFigures()
+  // --hashDepthRange of an unsharded context ends without a round trip: good_totals_kernel leaves {largest in-range depth + 1, most good hashes of a block,
+  // their sum (64 bits)} in goodTotals, and the first command that wants the three figures above fetches them (stage_c_good.hip)
+  DevBuf<u32> goodTotals; bool goodFiguresPending = false;
+  int needGoodFigures();
 
   // crib (hash10x.c:406-521): per hash index, where the two truth genomes hold it
   DevBuf<u32> cribCount[2];   // occurrences in genome 1 / 2
@@ -225,6 +233,7 @@ struct Ctx {
   int64_t optPrivTable = 0;   // entry look-ups of the index build: 0 = the table of this library's own where key + index do not fit the 64-bit reference-shaped one, 1 = always (tests), 2 = never, 3 = always and too small (tests: the fall-back)
   int64_t optProbedTable = 0; // index build, the wide table's "probed" entry format (index | hash >> B | probe number: stage_b.hip probe_insertP_kernel): 0 = where the classic entry (index | hash / w) does not fit 64 bits (-B 29 / 30 at k = 21), 1 = always (tests), 2 = never (round 5: two tables), 3 = always with ONE bit of probe number (tests: the table fails and the two tables are built)
   int64_t optNoPack = 0;      // index build with separate key / block arrays even where the packed form fits (A/B, tests)
+  int64_t optRankFused = 0;   // index build, packed entries: rows[], distinct values and first barcodes written in the run scan's own pass: 0 = where the buffers sized by the bound are cheap (stage_b.hip), 1 = always, 2 = never (A/B, tests)
   int64_t optNarrowFirst = 0; // first[] of the cluster kernel at 2 bytes per entry in every block (default: 4 where the block's working set leaves room)
   int64_t optTrEstDiv = 0;    // tuning knob: translated placement, classification: a block's barcodes estimated as entries / this (0 = 6)
   int64_t optTrClassT = -1;   // packed translated placement: -1 / 1 = lists of 65 .. 96 entries run two to a unit (a whole chunk each + one shared by their tails: class T), 0 = as class D, a unit of two chunks each (A/B, tests)
@@ -281,6 +290,27 @@ struct Ctx {
   Timer timers[T_COUNT];
   XchgStat xs[X_COUNT];
   h10x_counters ctr{};
+
+  // Small device counters that must start at zero (class sizes, work-queue positions, maxima, sums) come from one 16 KB arena that a library command clears
+  // with ONE memset on the context's stream when it opens its ZeroScope (below): a memset of a few bytes is a dispatch of some 5 us like any other, and a step
+  // made two dozen of them. zeros() hands out 16-byte-aligned ranges that are zero when handed out and belong to the caller until the scope closes; side
+  // streams see the clear through forkStreams(). When the arena is used up, or no scope is open (the sharded drivers), a range is an allocation with a
+  // memset of its own, kept until the scope closes or the next command enters.
+  static constexpr size_t ZERO_WORDS = 4096;
+  DevBuf<u32> zeroArena; size_t zeroUsed = 0; bool zeroOpen = false;
+  std::vector<DevBuf<u32> *> zeroSpill;
+  u32 *zeros(size_t words) {                             // nullptr (and err set) only when the device is out of memory
+    const size_t need = ((words ? words : 1) + 3) & ~(size_t)3;
+    if (zeroOpen && zeroUsed + need <= ZERO_WORDS) { u32 *p = zeroArena.p + zeroUsed; zeroUsed += need; return p; }
+    DevBuf<u32> *b = new DevBuf<u32>();
+    if (b->alloc(need) != hipSuccess || hipMemsetAsync(b->p, 0, need * 4, stream) != hipSuccess) { delete b; fail("out of device memory for %zu zeroed words", words); return nullptr; }
+    zeroSpill.push_back(b);
+    return b->p;
+  }
+  void dropZeroSpill() { for (DevBuf<u32> *b : zeroSpill) delete b; zeroSpill.clear(); }   // (back to the stream-ordered block cache)
+  Ctx() = default;
+  Ctx(const Ctx &) = delete; Ctx &operator=(const Ctx &) = delete;
+  ~Ctx() { dropZeroSpill(); }
 
   int fail(const char *fmt, ...) {
     char buf[1024]; va_list ap; va_start(ap, fmt); vsnprintf(buf, sizeof buf, fmt, ap); va_end(ap);
@@ -382,6 +412,20 @@ struct Ctx {
   void flush(TimerId t) { flush(timers[t]); }
 };
 
+// One per library command that draws counters from the zeroed arena (Ctx::zeros): clears the arena on the context's stream and resets the bump pointer.
+// Nested scopes are a programming error: the inner one fails its command. Check rc behind the constructor.
+struct ZeroScope {
+  Ctx *c; int rc = 0; bool opened = false;
+  explicit ZeroScope(Ctx *c_) : c(c_) {
+    if (c->zeroOpen) { rc = c->fail("internal error: nested ZeroScope"); return; }   // (the outer scope's counters are live: neither cleared nor closed from here)
+    if (!c->zeroArena.p && c->zeroArena.alloc(Ctx::ZERO_WORDS) != hipSuccess) { rc = c->fail("out of device memory for the counter arena"); return; }
+    if (hipMemsetAsync(c->zeroArena.p, 0, Ctx::ZERO_WORDS * 4, c->stream) != hipSuccess) { rc = c->fail("hipMemsetAsync of the counter arena failed"); return; }
+    c->zeroUsed = 0; c->zeroOpen = true; opened = true;
+  }
+  ZeroScope(const ZeroScope &) = delete; ZeroScope &operator=(const ZeroScope &) = delete;
+  ~ZeroScope() { if (opened) { c->zeroOpen = false; c->dropZeroSpill(); } }
+};
+
 // A fork/join region: side streams run kernels on buffers that go back to the per-stream block cache when the function returns (the
 // cache orders reuse within ONE stream only). If the function leaves early — an error between fork and join — the guard waits for every
 // stream before those destructors run; after a successful join the main stream is ordered behind the side streams and done() disarms it.
@@ -449,7 +493,7 @@ int stageB_buildProbeTable(Ctx *c);            // hashIndex[] from hashValue[1..
 // the blocks of the three workgroup-local-sort classes as lists: lists[k * nBlocks ..] holds counts[k] block numbers (entries up to CAP0 — incl. the
 // empty blocks and slot 0 —, up to CAP1, up to BLOCK_SORT_MAX); larger blocks are in none. A class's kernel then starts workgroups for ITS blocks
 // only: launched over all blocks, the two large classes spent as long dispatching workgroups that had nothing to do as the small class spent working.
-int stageB_blockClassLists(Ctx *c, DevBuf<u32> &lists, DevBuf<u32> &counts);
+int stageB_blockClassLists(Ctx *c, DevBuf<u32> &lists, u32 *&counts /* from the zeroed arena (Ctx::zeros) */);
 int stageC_depthRange(Ctx *c, int min, int max);
 int stageC_cluster(Ctx *c, int codeMin, int codeMax, int threshold);
 int stageC_split(Ctx *c);

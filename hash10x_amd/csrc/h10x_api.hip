@@ -15,6 +15,7 @@ static int enter(Ctx &c) {
   AllocScope::stream() = c.stream; AllocScope::device() = c.device;
   DevCache::noteStream(c.device, c.stream);
   c.pendingReads.clear(); c.mailUsed = 0; c.mailDirect = false;                    // read-backs a failed call left behind point into its dead frame
+  c.dropZeroSpill();                                                                // (zeroed counters a command drew outside a ZeroScope)
   c.stageReset();                                                                   // (and so do the stage timers a failed call left open)
   return 0;                                                                         // (an exchange still on the exchange stream is joined by the command that needs its result: stageC_cluster, shard_*)
 }
@@ -236,14 +237,14 @@ void h10x_destroy(h10x_ctx *h) {
 const char *h10x_last_error(const h10x_ctx *h) { return h ? h->c.err.c_str() : "null context"; }
 
 static void reset_state(Ctx &c) {
-  c.haveState = false; c.haveRange = false; c.haveGood = false; c.rangeMin = c.rangeMax = 0; c.depthBound = 0xFFFFFFFFu; c.rangeHiMax = 0;
+  c.haveState = false; c.haveRange = false; c.haveGood = false; c.goodFiguresPending = false; c.rangeMin = c.rangeMax = 0; c.depthBound = 0xFFFFFFFFu; c.rangeHiMax = 0;
   release_share_results(&c); stageP_release(&c);
   c.within.release(); c.goodPos.release(); c.nGood.release(); c.goodEntries.release(); c.goodRow.release();
   // the tables of the state being replaced go back to the block cache NOW, not when their successors are swapped in: the second --readFQB of a
   // context then finds every block of the first one parked and allocates nothing (kept until the swap, rows[] and clusHash had no twin in the
   // cache, took larger blocks, and those were allocated afresh behind them: 50-150 ms of hipMalloc inside the sort at 200 M read pairs)
   c.hashIndex.release(); c.hashValue.release(); c.hashDepth.release(); c.rowStart.release(); c.rows.release();
-  c.blocks.release(); c.blockOff.release(); c.clusHash.release(); c.clusterRaw.release();
+  c.blocks.release(); c.blockOff.release(); c.clusHash.release(); c.clusterRaw.release(); c.haveClusterRaw = false;
   c.hashNumber = 1; c.nBlocks = 0; c.nEntries = 0; c.nRecords = 0; c.maxBlockHashes = 0xFFFFFFFFu;
   c.sharded = false; c.codeBase = 0; c.nBlocksGlobal = 0; c.oRows.release(); c.oSegStart.release(); c.oIndex.release(); c.oU = 0; c.oM = 0;
   c.oHash.release(); c.tablesPending = false;
@@ -259,6 +260,7 @@ int h10x_read_fqb_device(h10x_ctx *h, const uint32_t *dRec, uint64_t n) {
   H10X_TRY(enter(c));
   if (n && !dRec) return c.fail("h10x_read_fqb_device: null records");
   reset_state(c);
+  ZeroScope zeroScope(&c); H10X_TRY(zeroScope.rc);           // the counters of both stages: one clear
   static const bool prof = getenv("H10X_HOSTPROF") != nullptr;
   timespec t0, t1, t2; clock_gettime(CLOCK_MONOTONIC, &t0);
   DevBuf<u64> entHash; DevBuf<u32> entCode, entRead;
@@ -980,7 +982,7 @@ int h10x_export_slice(h10x_ctx *h, int table, uint64_t first, uint64_t count, vo
     case H10X_TABLE_HASHDEPTH: src = c.hashDepth.p; eb = 4; limit = c.hashNumber; break;
     case H10X_TABLE_BLOCKS:    src = c.blocks.p; eb = sizeof(h10x_block); limit = c.nBlocks; break;
     case H10X_TABLE_CLUSHASH:  src = c.clusHash.p; eb = sizeof(h10x_clushash); limit = c.nEntries; break;
-    case H10X_TABLE_CLUSTER_RAW: if (!c.clusterRaw.p || c.clusterRaw.n != 2 * (size_t)c.nBlocks) return c.fail("no --cluster has run on these blocks"); src = c.clusterRaw.p; eb = 8; limit = c.nBlocks; break;
+    case H10X_TABLE_CLUSTER_RAW: if (!c.clusterRaw.p || !c.haveClusterRaw || c.clusterRaw.n != 2 * (size_t)c.nBlocks) return c.fail("no --cluster has run on these blocks"); src = c.clusterRaw.p; eb = 8; limit = c.nBlocks; break;
     case H10X_TABLE_WITHIN:    if (!c.haveRange) return c.fail("no hashDepthRange set"); src = c.within.p; eb = 1; limit = c.hashNumber; break;
     case H10X_TABLE_NGOOD:     if (!c.haveGood) return c.fail("!! you must set hashDepthRange before clusterReport"); src = c.nGood.p; eb = 4; limit = c.nBlocks; break;
     default: return c.fail("h10x_export_slice: unknown table %d", table);
@@ -1009,6 +1011,7 @@ int h10x_set_option(h10x_ctx *h, const char *name, int64_t value) {
   if (!strcmp(name, "cluster_tr_class_t")) { h->c.optTrClassT = value; return 0; }
   if (!strcmp(name, "cluster_tr_est_div")) { h->c.optTrEstDiv = value; return 0; }
   if (!strcmp(name, "index_no_pack")) { h->c.optNoPack = value; return 0; }
+  if (!strcmp(name, "index_rank_fused")) { if (value < 0 || value > 2) return h->c.fail("index_rank_fused must be 0..2"); h->c.optRankFused = value; return 0; }
   if (!strcmp(name, "index_probed_table")) { if (value < 0 || value > 3) return h->c.fail("index_probed_table must be 0..3"); h->c.optProbedTable = value; return 0; }
   if (!strcmp(name, "index_priv_table")) { if (value < 0 || value > 3) return h->c.fail("index_priv_table must be 0..3"); h->c.optPrivTable = value; return 0; }
   if (!strcmp(name, "cluster_stamps")) { h->c.optStamps = value; return 0; }

@@ -1,6 +1,7 @@
 // prim.hip — rocPRIM instantiations (device-wide radix sort, segmented sort, scans, reductions).
 #include "prim.hpp"
 #include <thread>
+#include <iterator>
 #include <rocprim/rocprim.hpp>
 
 namespace h10x {
@@ -29,6 +30,45 @@ struct RunHead {
 int prim_run_ordinals_u64(Ctx *c, PrimTemp &t, const u64 *key, int cb, u32 *ord, size_t n) {
   auto flags = rocprim::make_transform_iterator(rocprim::counting_iterator<size_t>(0), RunHead{key, n, cb});
   PRIM_TWO_PHASE(c, t, rocprim::exclusive_scan(tmp, bytes, flags, ord, (u32)0, n + 1, rocprim::plus<u32>(), c->stream));
+  return 0;
+}
+// The same scan with the scatter in its own pass (packed entries): the output "iterator" hands out a proxy whose assignment of ord at position i does what
+// seg_scatter_packed_kernel does with ord[] — rows[i] = block number; at a run's head dVal[ord].a / .b and dFirst[ord], and the end of the run before it,
+// dVal[ord - 1].c; at i == n the end of the last run and the number of runs (*total). ord[] is never stored. Runs beyond `cap` are counted but not written
+// (the caller's check then fails the command). The scan assigns every position once.
+struct RunScatterArgs { const u64 *key; size_t n; int cb; u32 *rows; Val16 *dVal; u32 *dFirst; u32 cap; u32 *total; };
+struct RunScatterOut {
+  RunScatterArgs a; size_t at;
+  struct Ref {                                               // (holds the arguments by value: it may outlive the iterator temporary that made it)
+    RunScatterArgs z; size_t i;
+    __device__ const Ref &operator=(u32 ord) const {
+      if (i < z.n) {
+        const u64 k = z.key[i]; const u32 code = (u32)(k & (((u64)1 << z.cb) - 1));
+        z.rows[i] = code;
+        if (i == 0 || (k >> z.cb) != (z.key[i - 1] >> z.cb)) {
+          if (ord < z.cap) { z.dVal[ord].a = k >> z.cb; z.dVal[ord].b = (u32)i; z.dFirst[ord] = code; }
+          if (i > 0 && ord - 1 < z.cap) z.dVal[ord - 1].c = (u32)i;
+        }
+      } else if (i == z.n) {
+        if (ord >= 1 && ord - 1 < z.cap) z.dVal[ord - 1].c = (u32)z.n;
+        *z.total = ord;
+      }
+      return *this;
+    }
+  };
+  using iterator_category = std::random_access_iterator_tag; using value_type = u32; using difference_type = std::ptrdiff_t; using pointer = void; using reference = Ref;
+  __host__ __device__ Ref operator*() const { return Ref{a, at}; }
+  __host__ __device__ Ref operator[](difference_type d) const { return Ref{a, at + (size_t)d}; }
+  __host__ __device__ RunScatterOut operator+(difference_type d) const { RunScatterOut r = *this; r.at = at + (size_t)d; return r; }
+  __host__ __device__ RunScatterOut operator-(difference_type d) const { RunScatterOut r = *this; r.at = at - (size_t)d; return r; }
+  __host__ __device__ RunScatterOut &operator+=(difference_type d) { at += (size_t)d; return *this; }
+  __host__ __device__ RunScatterOut &operator++() { ++at; return *this; }
+  __host__ __device__ difference_type operator-(const RunScatterOut &b) const { return (difference_type)at - (difference_type)b.at; }
+};
+int prim_run_scatter_u64(Ctx *c, PrimTemp &t, const u64 *key, int cb, size_t n, u32 *rows, Val16 *dVal, u32 *dFirst, u32 cap, u32 *total) {
+  auto flags = rocprim::make_transform_iterator(rocprim::counting_iterator<size_t>(0), RunHead{key, n, cb});
+  RunScatterOut out{RunScatterArgs{key, n, cb, rows, dVal, dFirst, cap, total}, 0};
+  PRIM_TWO_PHASE(c, t, rocprim::exclusive_scan(tmp, bytes, flags, out, (u32)0, n + 1, rocprim::plus<u32>(), c->stream));
   return 0;
 }
 int prim_exclusive_scan_u32_u64(Ctx *c, PrimTemp &t, const u32 *in, u64 *out, size_t n) {

@@ -18,6 +18,8 @@ int prim_sort_pairs_u32_u32(Ctx *c, PrimTemp &t, const u32 *kin, u32 *kout, cons
 int prim_sort_keys_u32(Ctx *c, PrimTemp &t, const u32 *kin, u32 *kout, size_t n, int beginBit, int endBit);
 int prim_sort_keys_u64(Ctx *c, PrimTemp &t, const u64 *kin, u64 *kout, size_t n, int beginBit, int endBit);
 struct Val16 { u64 a; u32 b, c; };                          // a 16-byte payload that rides through a sort (stage_b.hip: a distinct hash with its list's start and end)
+// the run ordinals never stored: rows[], dVal[] (up to cap runs) and dFirst[] written in the scan's own pass, the number of runs to *total (prim.hip RunScatterOut)
+int prim_run_scatter_u64(Ctx *c, PrimTemp &t, const u64 *key, int cb, size_t n, u32 *rows, Val16 *dVal, u32 *dFirst, u32 cap, u32 *total);
 int prim_sort_pairs_u32_v16(Ctx *c, PrimTemp &t, const u32 *kin, u32 *kout, const Val16 *vin, Val16 *vout, size_t n, int beginBit, int endBit);
 // per-segment sort of 64-bit keys (segments = [begin[i], end[i]) ), keys must be distinct per segment
 int prim_seg_sort_keys_u64(Ctx *c, PrimTemp &t, const u64 *kin, u64 *kout, u32 n, u32 nSeg, const u32 *begin, const u32 *end, int beginBit, int endBit);

@@ -114,11 +114,13 @@ __global__ void zero_runs_kernel(const u32 *__restrict__ rec, const u64 *__restr
 __global__ void classify_kernel(const u64 *__restrict__ startRec, u32 nBlocks, h10x_block *__restrict__ blocks,
                                 u32 *__restrict__ slots, u32 maxSlots, int packedOK,
                                 u32 *__restrict__ list0, u32 *__restrict__ list1, u32 *__restrict__ list2, u32 *__restrict__ listF,
-                                u32 *__restrict__ counts /* 4: <=4096, 8192, 16384 slots, global path */, int hashLast) {
+                                u32 *__restrict__ counts /* 4: <=4096, 8192, 16384 slots, global path */, int hashLast,
+                                u32 *__restrict__ nHash /* nBlocks + 1, zeroed here: the mosh kernels write the hashed blocks' counts only */) {
   const u32 c = blockIdx.x * blockDim.x + threadIdx.x;
   const int lane = threadIdx.x & (WAVE - 1);
   int cls = -1; u32 s = 0;
   if (c < nBlocks) {
+    nHash[c] = 0; if (c == 0) nHash[nBlocks] = 0;
     h10x_block b; memset(&b, 0, sizeof b);
     if (c > 0) {
       const u64 nr = startRec[c + 1] - startRec[c];
@@ -434,21 +436,26 @@ __global__ void set_nhash_kernel(h10x_block *__restrict__ blocks, const u32 *__r
 }
 
 struct SrcPtr { const u64 *hash; const u32 *read; };
-__global__ void count_overflow_kernel(const u32 *__restrict__ nHash, u32 nBlocks, u32 *__restrict__ count) {
+// the blocks whose LDS set overflowed, counted; on the same walk the largest entry count of a block (an overflowed block reads as the largest value:
+// "unknown" until repaired) and blocks[].nHash — a reduction and a kernel of their own before. count and maxHash start at zero (Ctx::zeros)
+__global__ void count_overflow_kernel(const u32 *__restrict__ nHash, u32 nBlocks, u32 *__restrict__ count, u32 *__restrict__ maxHash, h10x_block *__restrict__ blocks) {
   const u32 c = blockIdx.x * blockDim.x + threadIdx.x;
-  const u64 bal = __ballot(c < nBlocks && nHash[c] == NHASH_OVERFLOW);
-  if ((threadIdx.x & (WAVE - 1)) == 0 && bal) atomicAdd(count, (u32)__popcll(bal));
+  u32 n = 0;
+  if (c < nBlocks) { n = nHash[c]; blocks[c].nHash = n; }
+  const u64 bal = __ballot(c < nBlocks && n == NHASH_OVERFLOW);
+  for (int s = 32; s; s >>= 1) n = max(n, (u32)__shfl_xor((int)n, s));
+  if ((threadIdx.x & (WAVE - 1)) == 0) { if (bal) atomicAdd(count, (u32)__popcll(bal)); if (n) atomicMax(maxHash, n); }
 }
 
 __global__ void compact_entries_kernel(const u64 *__restrict__ stHash, const u32 *__restrict__ stRead, const u64 *__restrict__ capOff,
-                                       const SrcPtr *__restrict__ fb /* per block, null hash = staging */,
+                                       const SrcPtr *__restrict__ fb /* per block, null hash = staging; null: every block comes from the staging area */,
                                        const u32 *__restrict__ nHash, const u64 *__restrict__ blockOff, u32 nBlocks,
                                        u64 keyInv, int keyShift, int codeBits /* > 0: packed entries (Ctx::entCodeBits), entCode unused */,
                                        u64 *__restrict__ entHash, u32 *__restrict__ entCode, u32 *__restrict__ entRead) {
   for (u32 c = blockIdx.x + 1; c < nBlocks; c += gridDim.x) {
     const u32 n = nHash[c]; if (!n) continue;
     const u64 *sh; const u32 *sr;
-    if (fb[c].hash) { sh = fb[c].hash; sr = fb[c].read; } else { sh = stHash + capOff[c]; sr = stRead + capOff[c]; }
+    if (fb && fb[c].hash) { sh = fb[c].hash; sr = fb[c].read; } else { sh = stHash + capOff[c]; sr = stRead + capOff[c]; }
     const u64 o = blockOff[c];
     if (codeBits) for (u32 i = threadIdx.x; i < n; i += blockDim.x) { entHash[o + i] = (((sh[i] >> keyShift) * keyInv) << codeBits) | c; entRead[o + i] = sr[i]; }
     else for (u32 i = threadIdx.x; i < n; i += blockDim.x) { entHash[o + i] = (sh[i] >> keyShift) * keyInv; entCode[o + i] = c; entRead[o + i] = sr[i]; }   // hash / w (Ctx::keyInv)
@@ -603,17 +610,17 @@ int stageA_run(Ctx *c, const u32 *dRec, u64 nRec, DevBuf<u64> &entHash, DevBuf<u
   u32 maxSlots = 16384;                                      // LDS table classes: 4096 / 8192 / 16384 slots = 32 / 64 / 128 KB
   if (c->optMaxSlots > 0) maxSlots = (u32)c->optMaxSlots;
   const int packedOK = (2 * k + 16 <= 64) ? 1 : 0;
-  DevBuf<u32> slots, list0, list1, list2, listF, counts, nHash;
+  DevBuf<u32> slots, list0, list1, list2, listF, nHash;
   H10X_HIP(c, slots.alloc(nBlocks)); H10X_HIP(c, list0.alloc(nBlocks)); H10X_HIP(c, list1.alloc(nBlocks)); H10X_HIP(c, list2.alloc(nBlocks));
-  H10X_HIP(c, listF.alloc(nBlocks)); H10X_HIP(c, counts.alloc(4)); H10X_HIP(c, nHash.alloc((size_t)nBlocks + 1));
-  H10X_HIP(c, hipMemsetAsync(counts.p, 0, 16, st));
-  H10X_HIP(c, hipMemsetAsync(nHash.p, 0, ((size_t)nBlocks + 1) * 4, st));
+  H10X_HIP(c, listF.alloc(nBlocks)); H10X_HIP(c, nHash.alloc((size_t)nBlocks + 1));
+  u32 *const zeroed = c->zeros(8); if (!zeroed) return -1;   // the counters of this stage, zero on hand-out: [0..3] class sizes, [4] overflowed blocks, [5] largest entry count of a block
+  u32 *const counts = zeroed, *const nOverflow = zeroed + 4, *const dMaxHash = zeroed + 5;
   classify_kernel<<<divUp(nBlocks, 256), 256, 0, st>>>(startRec.p, nBlocks, c->blocks.p, slots.p, maxSlots, packedOK,
-                                                      list0.p, list1.p, list2.p, listF.p, counts.p, hashLast ? 1 : 0);
+                                                      list0.p, list1.p, list2.p, listF.p, counts, hashLast ? 1 : 0, nHash.p);
   DevBuf<u64> capOff; H10X_HIP(c, capOff.alloc((size_t)nBlocks + 1));
   H10X_TRY(prim_exclusive_scan_u32_u64(c, pt, slots.p, capOff.p, nBlocks));
   u32 hc[4]; u64 capTotal = 0; u32 lastSlots = 0;
-  H10X_TRY(c->readback(hc, counts.p, 16));
+  H10X_TRY(c->readback(hc, counts, 16));
   H10X_TRY(c->readback(&capTotal, capOff.p + (nBlocks - 1), 8));
   H10X_TRY(c->readback(&lastSlots, slots.p + (nBlocks - 1), 4));
   H10X_TRY(c->syncReadbacks());
@@ -655,17 +662,14 @@ int stageA_run(Ctx *c, const u32 *dRec, u64 nRec, DevBuf<u64> &entHash, DevBuf<u
 
   // ---- global path: class F plus any block whose LDS set overflowed. The usual case — no such block — is recognised
   // from one counter that comes back together with the entry total (no copy of the per-block arrays, no extra round trip).
-  DevBuf<u32> nOverflow; H10X_HIP(c, nOverflow.alloc(1)); H10X_HIP(c, hipMemsetAsync(nOverflow.p, 0, 4, st));
-  count_overflow_kernel<<<divUp(nBlocks, 256), 256, 0, st>>>(nHash.p, nBlocks, nOverflow.p);
+  count_overflow_kernel<<<divUp(nBlocks, 256), 256, 0, st>>>(nHash.p, nBlocks, nOverflow, dMaxHash, c->blocks.p);
   H10X_HIP(c, c->blockOff.alloc((size_t)nBlocks + 1));
   H10X_TRY(prim_exclusive_scan_u32_u64(c, pt, nHash.p, c->blockOff.p, (size_t)nBlocks + 1));
   u64 H = 0, lastStart = 0; u32 hOverflow = 0, hMaxHash = 0xFFFFFFFFu;
-  DevBuf<u32> dMaxHash; H10X_HIP(c, dMaxHash.alloc(1));
-  H10X_TRY(prim_reduce_max_u32(c, pt, nHash.p, dMaxHash.p, nBlocks));       // an overflowed block reads as the largest value: "unknown" until repaired
-  H10X_TRY(c->readback(&hMaxHash, dMaxHash.p, 4));
+  H10X_TRY(c->readback(&hMaxHash, dMaxHash, 4));
   H10X_TRY(c->readback(&H, c->blockOff.p + nBlocks, 8));
   H10X_TRY(c->readback(&lastStart, startRec.p + (nBlocks - 1), 8));
-  H10X_TRY(c->readback(&hOverflow, nOverflow.p, 4));
+  H10X_TRY(c->readback(&hOverflow, nOverflow, 4));
   H10X_TRY(c->syncReadbacks());
   const bool anyFallback = hc[3] || hOverflow;
   std::vector<u32> hNHash, hListF(hc[3]);
@@ -720,9 +724,9 @@ int stageA_run(Ctx *c, const u32 *dRec, u64 nRec, DevBuf<u64> &entHash, DevBuf<u
 
   // ---- gather into one (block-ordered) entry list
   c->tstart(T_COMPACT);
-  DevBuf<SrcPtr> dFb; H10X_HIP(c, dFb.alloc(nBlocks));
-  if (hFb.empty()) H10X_HIP(c, hipMemsetAsync(dFb.p, 0, (size_t)nBlocks * sizeof(SrcPtr), st));       // every block comes from the staging area
-  else {
+  DevBuf<SrcPtr> dFb;                                        // stays null without a fallback block: every block comes from the staging area
+  if (!hFb.empty()) {
+    H10X_HIP(c, dFb.alloc(nBlocks));
     H10X_HIP(c, hipMemcpyAsync(dFb.p, hFb.data(), (size_t)nBlocks * sizeof(SrcPtr), hipMemcpyHostToDevice, st));
     H10X_TRY(prim_exclusive_scan_u32_u64(c, pt, nHash.p, c->blockOff.p, (size_t)nBlocks + 1));          // again, with the repaired counts
     H10X_HIP(c, hipMemcpyAsync(&H, c->blockOff.p + nBlocks, 8, hipMemcpyDeviceToHost, st));
@@ -732,7 +736,7 @@ int stageA_run(Ctx *c, const u32 *dRec, u64 nRec, DevBuf<u64> &entHash, DevBuf<u
   c->nEntries = H;
   if (!hNHash.empty()) { hMaxHash = 0; for (u32 b = 0; b < nBlocks; ++b) hMaxHash = hNHash[b] > hMaxHash ? hNHash[b] : hMaxHash; }   // fallback path: the repaired counts
   c->maxBlockHashes = hMaxHash;
-  set_nhash_kernel<<<divUp(nBlocks, 256), 256, 0, st>>>(c->blocks.p, nHash.p, nBlocks);
+  if (!hNHash.empty()) set_nhash_kernel<<<divUp(nBlocks, 256), 256, 0, st>>>(c->blocks.p, nHash.p, nBlocks);   // the repaired counts (count_overflow_kernel wrote the others)
   H10X_HIP(c, entHash.alloc(H)); H10X_HIP(c, entRead.alloc(H));
   {                                                          // sort key = hash / w (common.hpp, Ctx::keyInv)
     u64 m = (u64)c->prm.w; int s = 0; while (!(m & 1)) { m >>= 1; ++s; }

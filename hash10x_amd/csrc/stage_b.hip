@@ -236,10 +236,10 @@ __global__ void block_class_kernel(const u64 *__restrict__ blockOff, u32 nBlocks
     if (cls == k) lists[(size_t)k * nBlocks + base + (u32)__popcll(bal & ((1ULL << lane) - 1))] = c;
   }
 }
-int stageB_blockClassLists(Ctx *c, DevBuf<u32> &lists, DevBuf<u32> &counts) {
-  H10X_HIP(c, lists.alloc((size_t)3 * c->nBlocks)); H10X_HIP(c, counts.alloc(4));
-  H10X_HIP(c, hipMemsetAsync(counts.p, 0, 16, c->stream));
-  if (c->nBlocks) block_class_kernel<<<divUp(c->nBlocks, 256), 256, 0, c->stream>>>(c->blockOff.p, c->nBlocks, lists.p, counts.p);
+int stageB_blockClassLists(Ctx *c, DevBuf<u32> &lists, u32 *&counts) {
+  H10X_HIP(c, lists.alloc((size_t)3 * c->nBlocks));
+  counts = c->zeros(4); if (!counts) return -1;
+  if (c->nBlocks) block_class_kernel<<<divUp(c->nBlocks, 256), 256, 0, c->stream>>>(c->blockOff.p, c->nBlocks, lists.p, counts);
   return 0;
 }
 
@@ -428,12 +428,12 @@ static int clusHashByBlocks(Ctx *c, const u64 *entHash, const u32 *entRead, cons
   if (!c->nEntries || nBlocks < 2) return 0;
   int sortBits = bitsFor(c->hashNumber) + 1 > 32 ? 32 : bitsFor(c->hashNumber) + 1;
   const int B = c->prm.B; const u64 w = (u64)c->prm.w; const int qBits = probeBits ? probeSH : c->keyBits;
-  DevBuf<u32> lists, counts;
+  DevBuf<u32> lists; u32 *counts = nullptr;
   H10X_TRY(stageB_blockClassLists(c, lists, counts));
   // workgroups per launch: the class's blocks are pulled from its list (count on the device: no round trip); enough workgroups to fill the chip
   const unsigned gridBig = hmin<u32>(nBlocks, (u32)c->numCU * 8), gridSmall = hmin<u32>(nBlocks, 65535u * 4);
 #define H10X_CH_LAUNCH(T, I, LOOK, CLS, STREAM) clushash_block_kernel<T, I, LOOK><<<(CLS == 0 ? gridSmall : gridBig), T, 0, STREAM>>>(entHash, entRead, key, c->blockOff.p, \
-    lists.p + (size_t)CLS * nBlocks, counts.p + CLS, table64, B, w, qBits, (key || replyPos) ? 0 : c->entCodeBits, sortBits, c->clusHash.p, privT, c->hashIndex.p, c->hashValue.p, replyIdx, replyPos, probeBits)
+    lists.p + (size_t)CLS * nBlocks, counts + CLS, table64, B, w, qBits, (key || replyPos) ? 0 : c->entCodeBits, sortBits, c->clusHash.p, privT, c->hashIndex.p, c->hashValue.p, replyIdx, replyPos, probeBits)
   const int side = c->maxBlockHashes > BLOCK_SORT_CAP1 ? 2 : (c->maxBlockHashes > BLOCK_SORT_CAP0 ? 1 : 0);
   ForkGuard forkGuard(c);
   if (side) H10X_TRY(c->forkStreams(side));                  // the few large blocks beside the many small ones
@@ -468,14 +468,30 @@ int stageB_run(Ctx *c, DevBuf<u64> &entHash, DevBuf<u32> &entCode, DevBuf<u32> &
   c->tstart(T_RANK);
   u32 U = 0;
   DevBuf<u64> dHash; DevBuf<u32> dFirst, segStart, iota, order, dFirstSorted; DevBuf<Val16> dVal, dValSorted;
-  {
+  // hash10x.c:149: die once hashNumber exceeds 2^(B-2) - 2; hashNumber ends at U + 1
+  const u64 maxRuns = (tableSize >> 2) - 2;
+  // Packed entries: rows[], the distinct values and the first barcodes can be written in the run scan's own pass (prim_run_scatter_u64) instead of by a second
+  // kernel over the keys and 4 H bytes of ordinals — if dVal[] / dFirst[] exist BEFORE the number of runs is known. A bound stands in for it: no more runs than
+  // entries, and no more than the table admits. 20 bytes per run of the bound are held to only while that is less than an eighth of what the context holds on the
+  // device at this point (entries, sorted keys, lists, sort scratch): otherwise the ordinals are stored and scattered from, as before.
+  const u64 runBound = hmin<u64>(H, maxRuns);
+  const bool fused = cb && H && c->optRankFused != 2 &&
+                     (c->optRankFused == 1 || runBound * (sizeof(Val16) + 4) < DevCache::live(AllocScope::device(), AllocScope::stream()) / 8);
+  if (fused) {
+    u32 *const total = c->zeros(1); if (!total) return -1;
+    H10X_HIP(c, dVal.alloc(runBound)); H10X_HIP(c, dFirst.alloc(runBound));
+    H10X_TRY(prim_run_scatter_u64(c, pt, sHash.p, cb, H, sCode.p, dVal.p, dFirst.p, (u32)runBound, total));   // (runs beyond the bound are counted, not written)
+    H10X_TRY(c->readback(&U, total, 4));
+    H10X_TRY(c->syncReadbacks());
+    if ((u64)U + 1 > maxRuns) return c->fail("hashTableSize is too small");
+    H10X_HIP(c, dFirstSorted.alloc(U)); H10X_HIP(c, dValSorted.alloc(U));
+  } else {
     DevBuf<u32> ord;
     H10X_HIP(c, ord.alloc(H + 2));                           // (+ 1: the packed scatter looks two ahead)
     H10X_TRY(prim_run_ordinals_u64(c, pt, sHash.p, cb, ord.p, H));          // (head flags formed inside the scan)
     H10X_TRY(c->readback(&U, ord.p + H, 4));
     H10X_TRY(c->syncReadbacks());
-    // hash10x.c:149: die once hashNumber exceeds 2^(B-2) - 2; hashNumber ends at U + 1
-    if ((u64)U + 1 > (tableSize >> 2) - 2) return c->fail("hashTableSize is too small");
+    if ((u64)U + 1 > maxRuns) return c->fail("hashTableSize is too small");
     H10X_HIP(c, dFirst.alloc(U)); H10X_HIP(c, dFirstSorted.alloc(U));
     if (cb) { H10X_HIP(c, dVal.alloc(U)); H10X_HIP(c, dValSorted.alloc(U)); }
     else { H10X_HIP(c, dHash.alloc(U)); H10X_HIP(c, segStart.alloc((size_t)U + 1)); H10X_HIP(c, iota.alloc(U)); H10X_HIP(c, order.alloc(U)); }

@@ -2049,8 +2049,7 @@ int stageC_clusterTail(Ctx *c, u32 codeMin, u32 codeMax, u64 *res, const u32 *li
   // (c) labels, cluster counts and the > 255 clusters cut from the msBest column: one workgroup per barcode, classes by rank count
   DevBuf<unsigned char> replayScratch;
   {
-    if (c->clusterRaw.n != 2 * (size_t)c->nBlocks) { H10X_HIP(c, c->clusterRaw.alloc(2 * (size_t)c->nBlocks)); H10X_HIP(c, hipMemsetAsync(c->clusterRaw.p, 0, 8 * (size_t)c->nBlocks, st)); }
-    H10X_HIP(c, hipMemsetAsync(c->clusterRaw.p + 2 * (size_t)codeMin, 0, 8 * (size_t)span, st));   // blocks without good hashes say nothing
+    // (clusterRaw: allocated, and zero over the range, since the classification — cluster_local_range)
     ReplayArgs ra{}; ra.raw = c->clusterRaw.p; ra.blocks = c->blocks.p; ra.blockOff = c->blockOff.p; ra.clusHash = c->clusHash.p; ra.goodPos = c->goodPos.p; ra.nGood = c->nGood.p;
     ra.res = res; ra.codeMin = codeMin; ra.span = span;
     // the barcodes with more ranks than the common class holds (nBig of them, listed by the classification): workgroups for those only,

@@ -12,19 +12,66 @@
 namespace h10x {
 
 // ------------------------------------------------------------------------------------------ depth range
-__global__ void within_kernel(const u32 *__restrict__ depth, u32 hashNumber, int lo, int hi, u8 *__restrict__ within) {
-  const u32 i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= hashNumber) return;
-  const int n = (int)depth[i];
-  if (n >= lo && n < hi) within[i] = 1;                     // only ever set (hash10x.c:535)
-}
-__global__ void within_depth_kernel(const u32 *__restrict__ depth, const u8 *__restrict__ within, u32 hashNumber, u32 *__restrict__ out,
-                                    const u64 *__restrict__ rowStart, u32 rowShift, u64 *__restrict__ rowInfo /* null, or per hash: where its barcode list starts (>> rowShift) | (depth + 1, 0 outside the range) << 32 */) {
-  const u32 i = blockIdx.x * blockDim.x + threadIdx.x;
+// One walk over the hashes: within[] takes the range [lo, hi) in (update; only ever set: hash10x.c:535 — ranges accumulate; `first`: within[] holds nothing
+// yet and counts as zero, no memset), then per hash wd = 0 outside the range(s), depth + 1 inside (one word tells both) goes to out[] and / or into rowInfo[],
+// and the workgroup's largest wd to part[blockIdx.x] — a plain store; good_totals_kernel takes the maximum of those. (An atomic maximum on one word instead, one per
+// wave: 40 k of them for 2.6 M hashes made the kernel 65 us slower than the three launches it replaces; one per workgroup, and only where it raises the word, still 20 us.)
+constexpr int FILTER_THREADS = 1024;
+__global__ __launch_bounds__(FILTER_THREADS)
+void depth_filter_kernel(const u32 *__restrict__ depth, u32 hashNumber, int lo, int hi, int update, int first, u8 *__restrict__ within,
+                         u32 *__restrict__ out /* null, or wd per hash */, const u64 *__restrict__ rowStart, u32 rowShift,
+                         u64 *__restrict__ rowInfo /* null, or per hash: where its barcode list starts (>> rowShift) | wd << 32 */, u32 *__restrict__ part) {
+  __shared__ u32 sMax[FILTER_THREADS / WAVE];
+  const u32 i = blockIdx.x * FILTER_THREADS + threadIdx.x;
+  u32 m = 0;
   if (i < hashNumber) {
-    const u32 wd = within[i] ? depth[i] + 1 : 0;             // 0 = outside the range(s); depth + 1 otherwise (one word tells both)
-    out[i] = wd; if (rowInfo) rowInfo[i] = (u64)(u32)(rowStart[i] >> rowShift) | ((u64)wd << 32);
+    const u32 d = depth[i];
+    u8 w = first ? (u8)0 : within[i];
+    if (update) { const int n = (int)d; if (n >= lo && n < hi) w = 1; within[i] = w; }
+    m = w ? d + 1 : 0;
+    if (out) out[i] = m;
+    if (rowInfo) rowInfo[i] = (u64)(u32)(rowStart[i] >> rowShift) | ((u64)m << 32);
   }
+  for (int s = 32; s; s >>= 1) m = max(m, (u32)__shfl_xor((int)m, s));
+  if ((threadIdx.x & (WAVE - 1)) == 0) sMax[threadIdx.x / WAVE] = m;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    for (int w = 1; w < FILTER_THREADS / WAVE; ++w) m = max(m, sMax[w]);
+    part[blockIdx.x] = m;
+  }
+}
+// What --cluster sizes its launches by, in one launch: tot[0] = largest wd (the maximum over depth_filter_kernel's workgroups), tot[1] = most good hashes of a
+// block, tot[2..3] = their sum (64 bits). Up to TOTALS_GROUPS workgroups each reduce a slice and leave {wd, max, sum} in `slot`; the one that draws the last
+// ticket (*ticket starts at zero: Ctx::zeros) folds the slots and stores tot with plain stores: tot needs no clearing and may outlive the command (Ctx::goodTotals).
+constexpr int TOTALS_THREADS = 1024, TOTALS_GROUPS = 64;
+__global__ __launch_bounds__(TOTALS_THREADS)
+void good_totals_kernel(const u32 *__restrict__ nGood, u32 nBlocks, const u32 *__restrict__ part, u32 nPart, u32 *slot /* 4 words per workgroup */, u32 *ticket, u32 *__restrict__ tot) {
+  __shared__ u32 sMax[TOTALS_THREADS / WAVE], sWd[TOTALS_THREADS / WAVE]; __shared__ unsigned long long sSum[TOTALS_THREADS / WAVE]; __shared__ u32 sLast;
+  u32 m = 0, wd = 0; unsigned long long s = 0;
+  const u32 stride = gridDim.x * TOTALS_THREADS;
+  for (u32 c = blockIdx.x * TOTALS_THREADS + threadIdx.x; c < nBlocks; c += stride) { const u32 n = nGood[c]; m = max(m, n); s += n; }
+  for (u32 p = blockIdx.x * TOTALS_THREADS + threadIdx.x; p < nPart; p += stride) wd = max(wd, part[p]);
+  for (int sft = 32; sft; sft >>= 1) { m = max(m, (u32)__shfl_xor((int)m, sft)); wd = max(wd, (u32)__shfl_xor((int)wd, sft)); s += __shfl_xor(s, sft); }
+  if ((threadIdx.x & (WAVE - 1)) == 0) { sMax[threadIdx.x / WAVE] = m; sWd[threadIdx.x / WAVE] = wd; sSum[threadIdx.x / WAVE] = s; }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    for (int w = 1; w < TOTALS_THREADS / WAVE; ++w) { m = max(m, sMax[w]); wd = max(wd, sWd[w]); s += sSum[w]; }
+    u32 *const mine = slot + 4 * blockIdx.x;
+    __hip_atomic_store(mine + 0, wd, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); __hip_atomic_store(mine + 1, m, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    __hip_atomic_store(mine + 2, (u32)s, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); __hip_atomic_store(mine + 3, (u32)(s >> 32), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    __threadfence();                                         // the slot is visible before the ticket is drawn
+    sLast = __hip_atomic_fetch_add(ticket, 1u, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT) == gridDim.x - 1 ? 1u : 0u;
+  }
+  __syncthreads();
+  if (!sLast || threadIdx.x != 0) return;
+  __threadfence();
+  m = 0; wd = 0; s = 0;
+  for (u32 g = 0; g < gridDim.x; ++g) {
+    const u32 *const q = slot + 4 * g;
+    wd = max(wd, __hip_atomic_load(q + 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)); m = max(m, __hip_atomic_load(q + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
+    s += (unsigned long long)__hip_atomic_load(q + 2, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) | ((unsigned long long)__hip_atomic_load(q + 3, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) << 32);
+  }
+  tot[0] = wd; tot[1] = m; tot[2] = (u32)s; tot[3] = (u32)(s >> 32);
 }
 
 // per block: keys (depth << 16 | position) of its in-range hashes, appended in any order; KT = u32 while the largest
@@ -153,42 +200,57 @@ void good_rows_kernel(const h10x_clushash *__restrict__ ch, const u64 *__restric
 int stageC_depthRange(Ctx *c, int lo, int hi) {
   hipStream_t st = c->stream; PrimTemp pt;
   if (!c->haveState) return c->fail("no hash state loaded: use readFQB or readHash first");
-  c->haveGood = false;                                       // (a call that fails half-way must not leave the lists of an earlier one standing: rows[] and the offsets are replaced below)
+  c->haveGood = false; c->goodFiguresPending = false;        // (a call that fails half-way must not leave the lists of an earlier one standing: rows[] and the offsets are replaced below)
+  ZeroScope zeroScope(c); H10X_TRY(zeroScope.rc);
   c->tstart(T_GOOD);
   const u32 U1 = c->hashNumber; const u32 nBlocks = c->nBlocks; const u64 H = c->nEntries;
-  if (!(c->haveRange && lo == c->rangeMin && hi == c->rangeMax)) {       // hash10x.c:530
-    if (!c->haveRange) { H10X_HIP(c, c->within.alloc(U1)); H10X_HIP(c, hipMemsetAsync(c->within.p, 0, U1, st)); }
-    within_kernel<<<divUp(U1, 256), 256, 0, st>>>(c->hashDepth.p, U1, lo, hi, c->within.p);
-    c->haveRange = true; c->rangeMin = lo; c->rangeMax = hi;
-    if (hi > 0 && (u32)hi > c->rangeHiMax) c->rangeHiMax = (u32)hi;
-  }
+  const bool newRange = !(c->haveRange && lo == c->rangeMin && hi == c->rangeMax);       // hash10x.c:530: the same range again changes nothing in within[]
+  const bool firstRange = !c->haveRange;                     // within[] holds nothing yet: depth_filter_kernel starts it from zero (no clear)
+  if (newRange && firstRange) H10X_HIP(c, c->within.alloc(U1));
+  const unsigned filterGrid = divUp(U1, FILTER_THREADS);
+  DevBuf<u32> wdPart; H10X_HIP(c, wdPart.alloc(filterGrid));  // per workgroup of the filter: largest in-range depth + 1
+  if (!c->goodTotals.p) H10X_HIP(c, c->goodTotals.alloc(4));
+  // the totals' launch: its workgroups, their slots, and a ticket word per launch (the device-wide sort path makes one ahead of time for the depth figure alone)
+  const unsigned totalsGrid = hmax<u32>(1u, hmin<u32>((u32)TOTALS_GROUPS, divUp(hmax<u32>(nBlocks, filterGrid), TOTALS_THREADS)));
+  DevBuf<u32> totSlots, earlyTot; H10X_HIP(c, totSlots.alloc(4 * (size_t)TOTALS_GROUPS));
+  u32 *const tickets = c->zeros(2); if (!tickets) return -1;
+  auto noteRange = [&]() { c->haveRange = true; c->rangeMin = lo; c->rangeMax = hi; if (hi > 0 && (u32)hi > c->rangeHiMax) c->rangeHiMax = (u32)hi; };
   // sharded: the barcode lists of the in-range hashes come from their owners first (they depend on the ranges alone), so that
-  // the good lists below can point into them
+  // the good lists below can point into them — within[] is brought up to date in a launch of its own in front of the exchange
   XGuard xGuard(c);                                          // (the lists may still be arriving on the exchange stream when this function leaves early)
-  if (c->sharded) { c->tstop(T_GOOD); H10X_TRY(shard_exchangeRows(c)); c->tstart(T_GOOD); }
+  bool updated = !newRange;
+  if (c->sharded) {
+    if (newRange) {
+      depth_filter_kernel<<<filterGrid, FILTER_THREADS, 0, st>>>(c->hashDepth.p, U1, lo, hi, 1, firstRange ? 1 : 0, c->within.p, nullptr, nullptr, 0u, nullptr, wdPart.p);
+      noteRange(); updated = true;
+    }
+    c->tstop(T_GOOD); H10X_TRY(shard_exchangeRows(c)); c->tstart(T_GOOD);
+  }
   // goodHashesBuild (hash10x.c:738-766)
-  DevBuf<u64> key, keyS; DevBuf<u32> key32, keyS32, off32, segEnd, wdepth, red;
-  H10X_HIP(c, off32.alloc((size_t)nBlocks + 1));
-  H10X_HIP(c, segEnd.alloc(nBlocks)); H10X_HIP(c, wdepth.alloc(U1)); H10X_HIP(c, red.alloc(2));
+  DevBuf<u64> key, keyS; DevBuf<u32> key32, keyS32, off32, segEnd, wdepth;
   H10X_HIP(c, c->nGood.alloc(nBlocks)); H10X_HIP(c, c->goodPos.alloc(H)); H10X_HIP(c, c->goodEntries.alloc(nBlocks)); H10X_HIP(c, c->goodRow.alloc(H));
   // no in-range depth exceeds this, known without a round trip: the data set's barcode count (Ctx::depthBound) or the ranges' limit
-  const u32 goodDepthBound = hmin<u32>(c->depthBound, c->rangeHiMax ? c->rangeHiMax - 1 : 0);
+  const u32 hiMax = (!updated && hi > 0 && (u32)hi > c->rangeHiMax) ? (u32)hi : c->rangeHiMax;      // (rangeHiMax as it stands once this range is in)
+  const u32 goodDepthBound = hmin<u32>(c->depthBound, hiMax ? hiMax - 1 : 0);
   const bool narrow = goodDepthBound <= 65535u;
   const bool byBlocks = narrow && c->maxBlockHashes <= BLOCK_SORT_MAX;       // every block's list is built and sorted by one workgroup
-  DevBuf<u64> rowInfo; if (byBlocks) H10X_HIP(c, rowInfo.alloc(U1));
-  within_depth_kernel<<<divUp(U1, 256), 256, 0, st>>>(c->hashDepth.p, c->within.p, U1, wdepth.p, c->rowStart.p, (u32)c->rowShift, rowInfo.p);
-  H10X_TRY(prim_reduce_max_u32(c, pt, wdepth.p, red.p, U1));
+  DevBuf<u64> rowInfo;
+  if (byBlocks) H10X_HIP(c, rowInfo.alloc(U1));              // (wdepth[] and off32[] serve the device-wide sort path only)
+  else { H10X_HIP(c, wdepth.alloc(U1)); H10X_HIP(c, off32.alloc((size_t)nBlocks + 1)); H10X_HIP(c, segEnd.alloc(nBlocks)); }
+  depth_filter_kernel<<<filterGrid, FILTER_THREADS, 0, st>>>(c->hashDepth.p, U1, lo, hi, updated ? 0 : 1, !updated && firstRange ? 1 : 0, c->within.p, wdepth.p,
+                                                     c->rowStart.p, (u32)c->rowShift, rowInfo.p, wdPart.p);
+  if (!updated) noteRange();
   if (byBlocks) {
     int db = 1; while (db < 16 && (goodDepthBound >> db)) ++db;
     const int sortBits = db + 1;                                              // one bit more than the largest depth: padding keys sort last
-    DevBuf<u32> lists, counts;
+    DevBuf<u32> lists; u32 *counts = nullptr;
     H10X_TRY(stageB_blockClassLists(c, lists, counts));
     const unsigned gridBig = hmin<u32>(nBlocks, (u32)c->numCU * 8), gridSmall = hmin<u32>(nBlocks, 65535u * 4);
     const int side = c->maxBlockHashes > BLOCK_SORT_CAP1 ? 2 : (c->maxBlockHashes > BLOCK_SORT_CAP0 ? 1 : 0);
     ForkGuard forkGuard(c);
     if (side) H10X_TRY(c->forkStreams(side));
 #define H10X_GOOD_LAUNCH(T, I, CLS, STREAM)                                                                                         \
-    { const u32 *const L = lists.p + (size_t)CLS * nBlocks, *const N = counts.p + CLS; const unsigned grid = CLS == 0 ? gridSmall : gridBig; \
+    { const u32 *const L = lists.p + (size_t)CLS * nBlocks, *const N = counts + CLS; const unsigned grid = CLS == 0 ? gridSmall : gridBig; \
       good_block_kernel<T, I><<<grid, T, 0, STREAM>>>(c->clusHash.p, c->blockOff.p, c->blocks.p, L, N, rowInfo.p, sortBits, c->goodPos.p, c->nGood.p, c->goodEntries.p, c->goodRow.p); }
     H10X_GOOD_LAUNCH(H10X_BS_T0, H10X_BS_I0, 0, st)
     if (side >= 1) H10X_GOOD_LAUNCH(H10X_BS_T1, H10X_BS_I1, 1, c->aux[0])
@@ -204,16 +266,15 @@ int stageC_depthRange(Ctx *c, int lo, int hi) {
                                                                              key32.p, c->nGood.p, segEnd.p, c->goodEntries.p);
   else good_keys_kernel<u64><<<hmin<u32>(nBlocks, 16384), 256, 0, st>>>(c->clusHash.p, c->blockOff.p, c->blocks.p, nBlocks, wdepth.p,
                                                                       key.p, c->nGood.p, segEnd.p, c->goodEntries.p);
-  H10X_TRY(prim_reduce_max_u32(c, pt, c->nGood.p, red.p + 1, nBlocks));
-  DevBuf<u64> redSum; H10X_HIP(c, redSum.alloc(1));
-  H10X_TRY(prim_reduce_sum_u32_u64(c, pt, c->nGood.p, redSum.p, nBlocks));
-  u32 hr[2]; u64 sumGood = 0;
-  H10X_TRY(c->readback(hr, red.p, 8));
-  H10X_TRY(c->readback(&sumGood, redSum.p, 8));
-  H10X_TRY(c->syncReadbacks());
-  hr[0] = hr[0] ? hr[0] - 1 : 0;                              // wdepth holds depth + 1
-  c->maxGoodDepth = hr[0]; c->maxGood = hr[1]; c->meanGood = nBlocks > 1 ? (u32)(sumGood / (nBlocks - 1)) : 0;
-  offsets32c_kernel<<<divUp((u64)nBlocks + 1, 256), 256, 0, st>>>(c->blockOff.p, nBlocks + 1, off32.p);
+  u32 hWd = 0;                                               // the sort below is made over the bits of the largest in-range depth: that path fetches it here
+  if (H && !byBlocks) {
+    H10X_HIP(c, earlyTot.alloc(4));                          // (the depth figure alone, ahead of time, into a record of its own: Ctx::goodTotals is written once, at the end)
+    good_totals_kernel<<<totalsGrid, TOTALS_THREADS, 0, st>>>(c->nGood.p, 0u, wdPart.p, filterGrid, totSlots.p, tickets + 1, earlyTot.p);
+    H10X_TRY(c->readback(&hWd, earlyTot.p, 4));
+    H10X_TRY(c->syncReadbacks());
+    offsets32c_kernel<<<divUp((u64)nBlocks + 1, 256), 256, 0, st>>>(c->blockOff.p, nBlocks + 1, off32.p);
+  }
+  const u32 hr[1] = {hWd ? hWd - 1 : 0};                      // (depth + 1)
   // ascending (depth, position): qsort by depth, stable => ties by position (hash10x.c:726-730,758)
   if (H && !byBlocks) {
     if (narrow) {
@@ -227,10 +288,29 @@ int stageC_depthRange(Ctx *c, int lo, int hi) {
   // list descriptors per good hash, in rank order: written by good_block_kernel; the device-wide sort path adds them here
   if (!byBlocks && nBlocks) good_rows_kernel<<<hmin<u32>(nBlocks, 65535u * 4), 256, 0, st>>>(c->clusHash.p, c->blockOff.p, c->nGood.p, c->goodPos.p, nBlocks, c->hashDepth.p, c->rowStart.p,
                                                                                            (u32)c->rowShift, c->goodRow.p);
-  H10X_HIP(c, hipGetLastError());                            // (no round trip here: --cluster, the next command, starts with one)
+  // the figures --cluster sizes its launches by stay on the device (Ctx::goodTotals) until a command asks for them: an unsharded --hashDepthRange
+  // ends without draining the queue, and the next command's launches queue up behind this one's
+  good_totals_kernel<<<totalsGrid, TOTALS_THREADS, 0, st>>>(c->nGood.p, nBlocks, wdPart.p, filterGrid, totSlots.p, tickets, c->goodTotals.p);
+  H10X_HIP(c, hipGetLastError());
   H10X_TRY(c->xJoin());                                      // sharded: the in-range lists have arrived before anything queued from here on runs (and before the next collective)
+  c->goodFiguresPending = true;
+  if (c->sharded) H10X_TRY(c->needGoodFigures());            // (sharded contexts keep the round trip here)
   c->haveGood = true;
   c->tstop(T_GOOD);
+  return 0;
+}
+
+// maxGoodDepth, maxGood and meanGood of the last --hashDepthRange: fetched from the device the first time they are wanted
+int Ctx::needGoodFigures() {
+  if (!goodFiguresPending) return 0;
+  u32 t[4] = {0, 0, 0, 0};
+  H10X_TRY(readback(t, goodTotals.p, 16));
+  H10X_TRY(syncReadbacks());
+  maxGoodDepth = t[0] ? t[0] - 1 : 0;                        // goodTotals[0] holds depth + 1
+  maxGood = t[1];
+  const u64 sumGood = (u64)t[2] | ((u64)t[3] << 32);
+  meanGood = nBlocks > 1 ? (u32)(sumGood / (nBlocks - 1)) : 0;
+  goodFiguresPending = false;
   return 0;
 }
 

@@ -36,8 +36,10 @@ __host__ __device__ inline bool translatedFits(u32 S, u32 S2, u32 est, u32 entri
 __global__ void cluster_classify_kernel(const h10x_block *__restrict__ blocks, const u32 *__restrict__ nGood, const u32 *__restrict__ entries, u32 codeMin, u32 codeMax,
                                         u32 nBlocks /* LDS entries of first[] (ranked, translated: barcodes of the data set) */, int ranked /* 1 ranked, 3 translated */, u32 hashMinSlots, u32 maxTrRanks, u32 firstCap, u32 bmWords, u32 waves0, size_t budget0, size_t budgetSmall, size_t budgetBig, u32 bigRanks, u32 estDiv /* translated placement: a block's barcodes are taken to be this fraction of its list entries */,
                                         u32 *__restrict__ list0, u32 *__restrict__ list1, u32 *__restrict__ list2, u32 *__restrict__ list3,
-                                        u32 *__restrict__ listBig /* blocks with more ranks than the small replay class holds: counts[9] */, u32 *__restrict__ counts, unsigned long long *__restrict__ work) {
+                                        u32 *__restrict__ listBig /* blocks with more ranks than the small replay class holds: counts[9] */, u32 *__restrict__ counts, unsigned long long *__restrict__ work,
+                                        u32 *__restrict__ raw /* Ctx::clusterRaw: the two words of every block of the range start at zero (blocks without good hashes say nothing) */) {
   const u32 c = codeMin + blockIdx.x * blockDim.x + threadIdx.x;
+  if (c < codeMax) { raw[2 * (size_t)c] = 0; raw[2 * (size_t)c + 1] = 0; }
   const int lane = threadIdx.x & (WAVE - 1);
   const u32 n = c < codeMax ? nGood[c] : 0;
   int cls = -1; u32 nRead = 0;
@@ -101,12 +103,15 @@ static int cluster_local_range(Ctx *c, int codeMin, int codeMax, int threshold, 
   const u32 nGlobal = c->sharded ? c->nBlocksGlobal : c->nBlocks;
   c->tstart(T_CLUSTER);
   const u32 span = (u32)(codeMax - codeMin);
-  DevBuf<u32> list0, list1, list2, list3, listBig; DevBuf<u64> zeroed; DevBuf<u64> term;
+  DevBuf<u32> list0, list1, list2, list3, listBig; DevBuf<u64> term;
   H10X_HIP(c, list0.alloc(span)); H10X_HIP(c, list1.alloc(span)); H10X_HIP(c, list2.alloc(span)); H10X_HIP(c, list3.alloc(span)); H10X_HIP(c, listBig.alloc(span));
-  // every small counter of the command in one buffer, cleared by one memset: counts[0..3] class sizes, [4] [6] [7] work
+  // every small counter of the command in one range of the zeroed arena (Ctx::zeros): counts[0..3] class sizes, [4] [6] [7] work
   // queue positions, [8] largest nRead, [10] [11] overflowed blocks (lists A, B); stats[0..7] the work counters
-  H10X_HIP(c, zeroed.alloc(8 + 8 + 2)); H10X_HIP(c, term.alloc(c->nEntries));   // (+ work of the half-CU and the whole-CU classes)
-  H10X_HIP(c, hipMemsetAsync(zeroed.p, 0, (8 + 8 + 2) * 8, st));
+  ZeroScope zeroScope(c); H10X_TRY(zeroScope.rc);
+  struct { u64 *p; } zeroed{(u64 *)c->zeros(2 * (8 + 8 + 2))}; if (!zeroed.p) return -1;
+  H10X_HIP(c, term.alloc(c->nEntries));                      // (+ work of the half-CU and the whole-CU classes)
+  // the --verbose figures of every block: cleared as a whole when first used on these blocks, per range by the classification below
+  if (c->clusterRaw.n != 2 * (size_t)c->nBlocks) { c->haveClusterRaw = false; H10X_HIP(c, c->clusterRaw.alloc(2 * (size_t)c->nBlocks)); H10X_HIP(c, hipMemsetAsync(c->clusterRaw.p, 0, 8 * (size_t)c->nBlocks, st)); }
   struct { u32 *p; } counts{(u32 *)zeroed.p}; struct { u64 *p; } stats{zeroed.p + 8};   // counts[12] [13]: most ranks of a block in the half-CU classes / the whole-CU class (sizes the handle slots)
   const size_t budgetSmall = c->optClusterLds > 0 ? (size_t)c->optClusterLds : 80 * 1024 - 1024;
   const size_t budgetBig = c->optClusterLds > 0 ? (size_t)c->optClusterLds : 160 * 1024 - 1024;
@@ -143,7 +148,7 @@ static int cluster_local_range(Ctx *c, int codeMin, int codeMax, int threshold, 
     cluster_classify_kernel<<<divUp(span, 256), 256, 0, st>>>(c->blocks.p, c->nGood.p, c->goodEntries.p, (u32)codeMin, (u32)codeMax,
                                                             firstMode == 1 || firstMode >= 3 ? nGlobal : nFirstLds, firstMode == 1 ? 1 : (firstMode == 4 ? 3 : 0), hashMinSlots, maxTrRanks, firstCap,
                                                             bmWords, (u32)threads0 / WAVE, budget0, budgetSmall, budgetBig, c->optBigRanks > 0 ? (u32)c->optBigRanks : c->meanGood + c->meanGood / 2, c->optTrEstDiv > 0 ? (u32)c->optTrEstDiv : 6u,
-                                                            list0.p, list1.p, list2.p, list3.p, listBig.p, counts.p, (unsigned long long *)(zeroed.p + 16));
+                                                            list0.p, list1.p, list2.p, list3.p, listBig.p, counts.p, (unsigned long long *)(zeroed.p + 16), c->clusterRaw.p);
     H10X_TRY(c->readback(hc, counts.p, 56));
     H10X_TRY(c->readback(hw, zeroed.p + 16, 16));
     H10X_TRY(c->syncReadbacks());
@@ -313,6 +318,7 @@ static int cluster_local_range(Ctx *c, int codeMin, int codeMax, int threshold, 
   }
   // labels from the msBest column, then the ordered sums beside the read merges
   H10X_TRY(stageC_clusterTail(c, (u32)codeMin, (u32)codeMax, term.p, listBig.p, hc[9], hc[8]));
+  c->haveClusterRaw = true;
   c->tstop(T_CLUSTER_K);
   u64 hs[8];
   H10X_TRY(c->readback(hs, stats.p, 64));
@@ -333,6 +339,7 @@ static int cluster_local_range(Ctx *c, int codeMin, int codeMax, int threshold, 
 int stageC_cluster(Ctx *c, int codeMin, int codeMax, int threshold) {
   if (!c->haveGood) return c->fail("!! you must set hashDepthRange before cluster");          // hash10x.c:1258
   if (threshold < 1) return c->fail("clusterThreshold %d must be >= 1 (the reference reads an uninitialised msBest otherwise)", threshold);
+  H10X_TRY(c->needGoodFigures());                                                               // maxGoodDepth, maxGood, meanGood: still on the device after an unsharded --hashDepthRange
   if (c->maxGoodDepth > RES_COUNT_MAX) return c->fail("a hash of the depth range lies in %u barcodes: beyond %u, the limit of this build", c->maxGoodDepth, RES_COUNT_MAX);
   const u32 nGlobal = c->sharded ? c->nBlocksGlobal : c->nBlocks;
   if (!codeMin) codeMin = 1;                                                                    // hash10x.c:1243-1244

@@ -1,6 +1,6 @@
-"""Are the kernels of csrc/stage_c*.hip the same, instruction for instruction, as those of another revision? (no GPU needed)
+"""Are the kernels of csrc/stage_a.hip, stage_b.hip and stage_c*.hip the same, instruction for instruction, as those of another revision? (no GPU needed)
    python scratch/kdiff.py <rev>          e.g. the commit before a change that only moves code between files
-Builds the device assembly of every stage_c*.hip of <rev> and of the working tree with the Makefile's flags for those objects, cuts it into
+Builds the device assembly of every stage_[abc]*.hip of <rev> and of the working tree with the Makefile's flags for those objects, cuts it into
 functions, drops comments, takes the numbers off the local labels and compares, per kernel, the instruction list and the .amdhsa_ descriptor
 lines (registers, LDS, scratch, waves). Kernels only the working tree has are listed; exit status 1 if a kernel of <rev> differs or is missing."""
 import glob, os, re, subprocess, sys, tempfile
@@ -14,9 +14,9 @@ def compile_line(csrc, src):
     return [w for w in cmd[:cmd.index("-o")] if w != "-c"] + ["--cuda-device-only", "-S"]
 
 def kernels(csrc, out):
-    """{demangled name: (instruction lines, descriptor lines)} over every stage_c*.hip of the directory"""
+    """{demangled name: (instruction lines, descriptor lines)} over every stage_[abc]*.hip of the directory"""
     found = {}
-    for src in sorted(glob.glob(os.path.join(csrc, "stage_c*.hip"))):
+    for src in sorted(glob.glob(os.path.join(csrc, "stage_[abc]*.hip"))):
         asm = os.path.join(out, os.path.basename(src) + ".s")
         r = subprocess.run(compile_line(csrc, src) + ["-o", asm], cwd=csrc, stderr=subprocess.PIPE)
         if r.returncode: sys.exit("%s does not compile:\n%s" % (src, r.stderr.decode()))
