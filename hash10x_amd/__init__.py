@@ -249,6 +249,15 @@ def load_native():
     hip.h10x_list_share_get.argtypes = [vp, vp, vp, vp, cu64]
     hip.h10x_list_share_get_device.argtypes = [vp, vp, vp, vp, cu64]
     host.h10x_session_seqBlocks.argtypes = [vp, ci, cs, cs, vp, ci]
+    # row links (csrc/stage_q.hip)
+    hip.h10x_row_links_begin.argtypes = [vp, ctypes.c_uint32]
+    hip.h10x_row_links_add.argtypes = [vp, vp, vp, cu64]
+    hip.h10x_row_links_add_kept.argtypes = [vp]
+    hip.h10x_row_links_finish.argtypes = [vp, ctypes.c_int64, ctypes.c_int64, ctypes.c_int32, vp]
+    hip.h10x_row_links_get.argtypes = [vp, vp, vp, vp, cu64]
+    hip.h10x_row_links_get_device.argtypes = [vp, vp, vp, vp, cu64]
+    hip.h10x_row_links_get_range.argtypes = [vp, cu64, cu64, vp, vp]
+    host.h10x_session_seqLinks.argtypes = [vp, ci, ci, ci, ci, cs, cs, vp, ci]
     # mosh sets (csrc/stage_g.hip, host/mosh_host.c)
     pvp, ci32, cu32 = ctypes.POINTER(vp), ctypes.c_int32, ctypes.c_uint32
     hip.h10x_factors_from_seed.restype = None; hip.h10x_factors_from_seed.argtypes = [ci32, ctypes.POINTER(cu64), ctypes.POINTER(cu64)]
@@ -1154,6 +1163,74 @@ class Hash10x:
         the file `out`."""
         self._with_file(out, lambda f: self._host.h10x_session_seqBlocks(self._s, int(min_share), os.fsencode(seqfile), os.fsencode(path), f, 1 if verbose else 0))
 
+    # ---- row links (h10x_row_links_*, csrc/stage_q.hip) ----
+    def _row_links_ctx(self, cmd):
+        """the session's context (it comes with the first state; the row layer itself reads none)"""
+        if not self._ctx():
+            raise Hash10xError("%s: no hash state loaded: use readFQB or readHash first" % cmd)
+        return self._ctx()
+
+    def _row_links_finish(self, ctx, min_blocks, max_lists, siblings):
+        z = np.zeros(1, dtype=_ROW_LINKS_INFO)
+        self._chk_ctx(self._hip.h10x_row_links_finish(ctx, int(min_blocks), int(max_lists), 1 if siblings else 0, z.ctypes.data))
+        info = {k: int(z[k][0]) for k in _ROW_LINKS_INFO.names}
+        m = info["links"]
+        off = np.zeros(info["lists"] + 1, dtype=np.uint64)
+        other, shared = np.zeros(max(m, 1), dtype=np.uint32), np.zeros(max(m, 1), dtype=np.uint32)
+        self._chk_ctx(self._hip.h10x_row_links_get(ctx, off.ctypes.data, other.ctypes.data, shared.ctypes.data, m))
+        return info, (off, other[:m], shared[:m])
+
+    def row_links(self, offsets, block, min_blocks, max_lists=0, siblings=False, n_blocks=None):
+        """Which lists of block numbers share blocks. The lists come in CSR form (offsets[n + 1], block[]), each strictly ascending, every block
+        below n_blocks (default: the state's). A block that stands in more than max_lists lists is left out (0: none is); with siblings
+        lists 2s and 2s + 1 are never linked. Returns (offsets uint64[n + 1], other uint32[], shared uint32[]): per list e the lists f > e
+        that share at least min_blocks blocks with it, ascending, with the number shared. The figures of the run (lists, rowEntries,
+        blocksUsed, skippedBlocks, pairs, links, maxShared, batches, windows, wideBatches) are kept in self.row_links_info."""
+        ctx = self._row_links_ctx("rowLinks")
+        o = np.ascontiguousarray(offsets, dtype=np.uint64); b = np.ascontiguousarray(block, dtype=np.uint32)
+        if len(o) < 1 or int(o[-1]) > len(b):
+            raise Hash10xError("rowLinks: offsets must hold n + 1 entries and end within the blocks")
+        self._chk_ctx(self._hip.h10x_row_links_begin(ctx, int(self.sizes()["nBlocks"] if n_blocks is None else n_blocks)))
+        self._chk_ctx(self._hip.h10x_row_links_add(ctx, o.ctypes.data, b.ctypes.data, len(o) - 1))
+        self.row_links_info, out = self._row_links_finish(ctx, min_blocks, max_lists, siblings)
+        return out
+
+    @staticmethod
+    def _cut_ends(seqs, end_len):
+        """the two ends of every sequence, as sequences: the first and the last min(len, end_len) bases; end_len 0: the whole and none"""
+        codes, start = Hash10x._flatten_seqs(seqs)
+        ends = []
+        for a, b in zip(start[:-1], start[1:]):
+            a, b = int(a), int(b)
+            m = min(b - a, int(end_len)) if end_len else b - a
+            ends += [codes[a:a + m], codes[b - m:b] if end_len else codes[:0]]
+        return ends
+
+    def seq_links(self, seqs, min_share, min_blocks, end_len, max_ends=0):
+        """Which ends of the sequences share blocks (after --clusterSplit and a new range: molecules). Sequence s gives end 2s, its first
+        min(len, end_len) bases, and end 2s + 1, its last (end_len 0: the whole sequence and an empty end). The row of an end is its
+        seq_blocks row at min_share; the rows go from seq_blocks to the join on the device. Returns (offsets uint64[2 n + 1], other, shared)
+        as row_links with siblings on and max_lists = max_ends. The figures are kept in self.seq_links_info."""
+        ctx = self._seq_ctx("seqLinks")
+        if int(end_len) < 0 or int(max_ends) < 0:
+            raise Hash10xError("!! seqLinks %s %d must be >= 0" % (("endLen", int(end_len)) if int(end_len) < 0 else ("maxEnds", int(max_ends))))
+        codes, start = self._flatten_seqs(self._cut_ends(seqs, end_len))
+        n = len(start) - 1
+        z = np.zeros(1, dtype=_LIST_SHARE_INFO)
+        if self._hip.h10x_seq_blocks_run(ctx, int(min_share), codes.ctypes.data, start.ctypes.data, n, None, z.ctypes.data):
+            raise Hash10xError(self._hip.h10x_last_error(ctx).decode(errors="replace").replace("seqBlocks", "seqLinks"))
+        self._chk_ctx(self._hip.h10x_row_links_begin(ctx, int(z["nBlocks"][0])))
+        self._chk_ctx(self._hip.h10x_row_links_add_kept(ctx))
+        self.seq_links_info, out = self._row_links_finish(ctx, min_blocks, max_ends, True)
+        return out
+
+    def write_seq_links(self, min_share, min_blocks, end_len, max_ends, seqfile, path, out=None, verbose=False):
+        """--seqLinks <min_share> <min_blocks> <end_len> <max_ends> <seqfile> <path>: the links between the ends of the sequences of a FASTA /
+        FASTQ file (gzip or plain) written as a .sl file (read_seq_links reads it); one line of counts, and with verbose one SEQ_LINKS line
+        per link, are appended to the file `out`."""
+        self._with_file(out, lambda f: self._host.h10x_session_seqLinks(self._s, int(min_share), int(min_blocks), int(end_len), int(max_ends), os.fsencode(seqfile),
+                                                                        os.fsencode(path), f, 1 if verbose else 0))
+
     def export_within(self):
         """hashWithinRange[0 .. hashNumber) as uint8 (fails before --hashDepthRange)."""
         z = self.sizes()
@@ -1165,6 +1242,8 @@ class Hash10x:
 _SEQ_FIGURES = np.dtype([("moshes", "<u4"), ("found", "<u4"), ("query", "<u4"), ("reserved", "<u4"), ("entries", "<u8")])
 _LIST_SHARE_INFO = np.dtype([("rows", "<u8"), ("listEntries", "<u8"), ("listHashes", "<u8"), ("maxCount", "<u4"), ("batches", "<u4"), ("windows", "<u4"),
                              ("wideBatches", "<u4"), ("nBlocks", "<u4"), ("lists", "<u4")])
+_ROW_LINKS_INFO = np.dtype([("lists", "<u8"), ("rowEntries", "<u8"), ("blocksUsed", "<u8"), ("skippedBlocks", "<u8"), ("pairs", "<u8"), ("links", "<u8"),
+                            ("maxShared", "<u4"), ("batches", "<u4"), ("windows", "<u4"), ("wideBatches", "<u4")])
 _SEQ_CODE = np.zeros(256, dtype=np.uint8)
 for _i, _c in enumerate("ACGT"):
     _SEQ_CODE[ord(_c)] = _SEQ_CODE[ord(_c.lower())] = _i
@@ -1241,6 +1320,75 @@ def read_seq_blocks(path):
     names = [blob[int(a):int(b) - 1].decode(errors="replace") for a, b in zip(name_off[:-1], name_off[1:])]
     info = {"version": version, "nBlocks": n_blocks, "minShare": min_share, "nSeq": n_seq, "rows": rows, "nameBytes": name_bytes}
     return info, off, blk, cnt, table, names
+
+
+_SL_RECORD = np.dtype([("len", "<u8"), ("headRows", "<u4"), ("tailRows", "<u4")])
+
+
+def read_seq_links(path):
+    """A --seqLinks file (magic "10XL", u32 version 1, u32 nBlocks, u32 minShare, u32 minBlocks, u32 endLen, u32 maxEnds, u32 0, u64 nSeq, u64 links,
+    u64 skippedBlocks, u64 nameBytes; nSeq records {u64 len, u32 headRows, u32 tailRows}; 2 nSeq + 1 u64 offsets; links pairs {u32 end, u32
+    shared}; nSeq + 1 u64 name offsets; the names, NUL-terminated; little-endian; needs no device): (info, offsets, other, shared, table, names).
+    The row of end e (2s = the head of sequence s, 2s + 1 its tail) is [offsets[e], offsets[e + 1]). Raises Hash10xError for a file that is not
+    one or does not hold together: the sizes against the file's length, both offset arrays, every end below 2 nSeq and above its row's own,
+    ascending within a row, no link between the two ends of one sequence, shared >= minBlocks."""
+    with open(path, "rb") as f:
+        data = f.read()
+    if len(data) < 64 or data[:4] != b"10XL":
+        raise Hash10xError("%s: not a seq links file (magic 10XL)" % path)
+    version, n_blocks, min_share, min_blocks, end_len, max_ends, zero = (int(v) for v in np.frombuffer(data, dtype="<u4", count=7, offset=4))
+    n_seq, links, skipped, name_bytes = (int(v) for v in np.frombuffer(data, dtype="<u8", count=4, offset=32))
+    if version != 1:
+        raise Hash10xError("%s: seq links version %d, this reader knows 1" % (path, version))
+    n_ends = 2 * n_seq
+    need = 64 + 16 * n_seq + 8 * (n_ends + 1) + 8 * links + 8 * (n_seq + 1) + name_bytes
+    if len(data) != need:
+        raise Hash10xError("%s: %d bytes, %d sequences, %d links and %d name bytes need %d" % (path, len(data), n_seq, links, name_bytes, need))
+    if zero:
+        raise Hash10xError("%s: the reserved word of the header is not 0" % path)
+    at = 64
+    table = np.frombuffer(data, dtype=_SL_RECORD, count=n_seq, offset=at).copy(); at += 16 * n_seq
+    off = np.frombuffer(data, dtype="<u8", count=n_ends + 1, offset=at).copy(); at += 8 * (n_ends + 1)
+    pairs = np.frombuffer(data, dtype="<u4", count=2 * links, offset=at).reshape(-1, 2); at += 8 * links
+    name_off = np.frombuffer(data, dtype="<u8", count=n_seq + 1, offset=at).copy(); at += 8 * (n_seq + 1)
+    blob = data[at:]
+    if off[0] != 0 or int(off[-1]) != links or np.any(off[1:] < off[:-1]):
+        raise Hash10xError("%s: the offsets do not ascend from 0 to the %d links" % (path, links))
+    if name_off[0] != 0 or int(name_off[-1]) != name_bytes or np.any(name_off[1:] <= name_off[:-1]):
+        raise Hash10xError("%s: the name offsets do not ascend from 0 to the %d name bytes" % (path, name_bytes))
+    if any(blob[int(e) - 1] != 0 for e in name_off[1:]):
+        raise Hash10xError("%s: a name does not end in NUL" % path)
+    other, shared = pairs[:, 0].copy(), pairs[:, 1].copy()
+    if links:
+        own = np.repeat(np.arange(n_ends, dtype=np.int64), np.diff(off.astype(np.int64)))
+        if int(other.max()) >= n_ends:
+            raise Hash10xError("%s: a link's end is beyond the %d ends" % (path, n_ends))
+        if np.any(other.astype(np.int64) <= own):
+            raise Hash10xError("%s: a link's end is not above its row's own end" % path)
+        if np.any((other.astype(np.int64) >> 1) == (own >> 1)):
+            raise Hash10xError("%s: a link joins the two ends of one sequence" % path)
+        if np.any((own[1:] == own[:-1]) & (other[1:] <= other[:-1])):
+            raise Hash10xError("%s: the ends of a row do not ascend" % path)
+        if int(shared.min()) < max(min_blocks, 1):
+            raise Hash10xError("%s: a link shares fewer than minBlocks %d" % (path, min_blocks))
+    names = [blob[int(a):int(b) - 1].decode(errors="replace") for a, b in zip(name_off[:-1], name_off[1:])]
+    info = {"version": version, "nBlocks": n_blocks, "minShare": min_share, "minBlocks": min_blocks, "endLen": end_len, "maxEnds": max_ends, "nSeq": n_seq,
+            "links": links, "skippedBlocks": skipped, "nameBytes": name_bytes}
+    return info, off, other, shared, table, names
+
+
+def symmetric_links(offsets, other, shared):
+    """The upper-triangle rows of row_links / seq_links / read_seq_links as full rows: (offsets uint64[n + 1], other uint32[], shared uint32[])
+    in which list e stands in the row of f wherever f stands in the row of e, every row ascending."""
+    offsets = np.asarray(offsets, dtype=np.int64)
+    n = len(offsets) - 1
+    e = np.repeat(np.arange(n, dtype=np.int64), np.diff(offsets))
+    f = np.asarray(other, dtype=np.int64)
+    a, b, c = np.concatenate([e, f]), np.concatenate([f, e]), np.concatenate([np.asarray(shared, dtype=np.uint32)] * 2)
+    order = np.lexsort((b, a))
+    off = np.zeros(n + 1, dtype=np.uint64)
+    off[1:] = np.cumsum(np.bincount(a, minlength=n)[:n])
+    return off, b[order].astype(np.uint32), c[order]
 
 
 _SHARE_COMPONENTS_INFO = np.dtype([("rows", "<u8"), ("listEntries", "<u8"), ("nBlocks", "<u4"), ("minShare", "<u4"), ("nComponents", "<u4"), ("largest", "<u4"),

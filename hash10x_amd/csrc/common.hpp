@@ -276,6 +276,11 @@ struct Ctx {
   // (block, count) of list q at [sbOffsets[q], sbOffsets[q + 1]). Both kept until the next run, a new depth range, --clusterSplit or a new state
   DevBuf<u32> sqHash; DevBuf<u64> sqOffsets; std::vector<u64> sqHostOff; u64 sqEntries = 0; u32 sqSeqs = 0; bool haveSeqHashes = false;
   DevBuf<u32> sbBlock, sbCount; DevBuf<u64> sbOffsets; u64 sbRows = 0; u32 sbLists = 0; bool haveSeqBlocks = false;
+  // row links (stage_q.hip). Between h10x_row_links_begin and the next begin: rqKeys = the rqEntries row entries of the rqLists lists added so far as keys
+  // block << 32 | list, in (list, block) order, every block below rqBlocks. After h10x_row_links_finish: the links (other list, shared blocks) of list e at
+  // [rlOffsets[e], rlOffsets[e + 1]). Both kept until the next begin, a new depth range, --clusterSplit or a new state
+  DevBuf<u64> rqKeys; u64 rqEntries = 0, rqLists = 0; u32 rqBlocks = 0; bool rqOpen = false;
+  DevBuf<u32> rlOther, rlShared; DevBuf<u64> rlOffsets; u64 rlLinks = 0; u32 rlLists = 0; bool haveRowLinks = false;
   int64_t optSeqSlab = 0;     // bases per device batch of the sequence layer (0 = the mosh sets' default, 2^26); results do not depend on it
   // the -r value prm.factor1 was drawn from (option "seqhash_seed"): a mosh set made from the state carries the hasher's second multiplier too (stage_o.hip)
   int32_t seed = 0; bool haveSeed = false;
@@ -557,6 +562,14 @@ int stageP_listShare(Ctx *c, int64_t minShare, const u64 *offsets, const u32 *ha
 int stageP_seqBlocks(Ctx *c, int64_t minShare, const u8 *codes, const u64 *seqStart, u32 nSeq, h10x_seq_figures *fig, h10x_list_share_info *info);
 int stageP_get(Ctx *c, u64 *offsets, u32 *block, u32 *count, u64 cap, int toDevice);
 void stageP_release(Ctx *c);
+// row links (stage_q.hip): lists of block numbers accumulated on the device, and the pairs of lists that share blocks
+int stageQ_begin(Ctx *c, u32 nBlocks);
+int stageQ_add(Ctx *c, const u64 *offsets, const u32 *block, u64 nLists);
+int stageQ_addKept(Ctx *c);
+int stageQ_finish(Ctx *c, int64_t minBlocks, int64_t maxLists, int siblings, h10x_row_links_info *info);
+int stageQ_get(Ctx *c, u64 *offsets, u32 *other, u32 *shared, u64 cap, int toDevice);
+int stageQ_getRange(Ctx *c, u64 first, u64 count, u32 *other, u32 *shared);
+void stageQ_release(Ctx *c);
 int stageJ_censusBegin(Ctx *c, u64 hint);
 int stageJ_censusAdd(Ctx *c, const u32 *dRec, u64 n);
 int stageJ_censusClose(Ctx *c, int64_t thresh, h10x_census_t *out);

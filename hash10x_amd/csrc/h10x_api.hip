@@ -238,7 +238,7 @@ const char *h10x_last_error(const h10x_ctx *h) { return h ? h->c.err.c_str() : "
 
 static void reset_state(Ctx &c) {
   c.haveState = false; c.haveRange = false; c.haveGood = false; c.goodFiguresPending = false; c.rangeMin = c.rangeMax = 0; c.depthBound = 0xFFFFFFFFu; c.rangeHiMax = 0;
-  release_share_results(&c); stageP_release(&c);
+  release_share_results(&c); stageP_release(&c); stageQ_release(&c);
   c.within.release(); c.goodPos.release(); c.nGood.release(); c.goodEntries.release(); c.goodRow.release();
   // the tables of the state being replaced go back to the block cache NOW, not when their successors are swapped in: the second --readFQB of a
   // context then finds every block of the first one parked and allocates nothing (kept until the swap, rows[] and clusHash had no twin in the
@@ -411,6 +411,7 @@ int h10x_depth_range(h10x_ctx *h, int32_t lo, int32_t hi) {
   H10X_TRY(enter(h->c));
   release_share_results(&h->c);   // a kept share graph, kept components and kept hash copies are of the lists this call replaces
   stageP_release(&h->c);          // (so are the query lists and rows of sequences)
+  stageQ_release(&h->c);          // (and the row links made of them)
   return stageC_depthRange(&h->c, lo, hi);
 }
 
@@ -424,7 +425,7 @@ int h10x_cluster_split(h10x_ctx *h) {
   if (!h) return -1;
   H10X_TRY(enter(h->c));
   release_share_results(&h->c);   // (and of the blocks this call renumbers)
-  stageP_release(&h->c);
+  stageP_release(&h->c); stageQ_release(&h->c);
   return stageC_split(&h->c);
 }
 
@@ -726,6 +727,25 @@ int h10x_list_share_get(h10x_ctx *h, uint64_t *offsets, uint32_t *block, uint32_
 }
 int h10x_list_share_get_device(h10x_ctx *h, uint64_t *devOffsets, uint32_t *devBlock, uint32_t *devCount, uint64_t cap) {
   if (!h) return -1; H10X_TRY(enter(h->c)); return stageP_get(&h->c, (u64 *)devOffsets, devBlock, devCount, cap, 1);
+}
+
+// ---- row links (stage_q.hip) ----
+int h10x_row_links_begin(h10x_ctx *h, uint32_t nBlocks) { if (!h) return -1; H10X_TRY(enter(h->c)); return stageQ_begin(&h->c, nBlocks); }
+int h10x_row_links_add(h10x_ctx *h, const uint64_t *offsets, const uint32_t *block, uint64_t nLists) {
+  if (!h) return -1; H10X_TRY(enter(h->c)); return stageQ_add(&h->c, (const u64 *)offsets, block, nLists);
+}
+int h10x_row_links_add_kept(h10x_ctx *h) { if (!h) return -1; H10X_TRY(enter(h->c)); return stageQ_addKept(&h->c); }
+int h10x_row_links_finish(h10x_ctx *h, int64_t minBlocks, int64_t maxLists, int32_t siblings, h10x_row_links_info *info) {
+  if (!h || !info) return -1; H10X_TRY(enter(h->c)); return stageQ_finish(&h->c, minBlocks, maxLists, siblings, info);
+}
+int h10x_row_links_get(h10x_ctx *h, uint64_t *offsets, uint32_t *other, uint32_t *shared, uint64_t cap) {
+  if (!h) return -1; H10X_TRY(enter(h->c)); return stageQ_get(&h->c, (u64 *)offsets, other, shared, cap, 0);
+}
+int h10x_row_links_get_device(h10x_ctx *h, uint64_t *devOffsets, uint32_t *devOther, uint32_t *devShared, uint64_t cap) {
+  if (!h) return -1; H10X_TRY(enter(h->c)); return stageQ_get(&h->c, (u64 *)devOffsets, devOther, devShared, cap, 1);
+}
+int h10x_row_links_get_range(h10x_ctx *h, uint64_t first, uint64_t count, uint32_t *other, uint32_t *shared) {
+  if (!h) return -1; H10X_TRY(enter(h->c)); return stageQ_getRange(&h->c, first, count, other, shared);
 }
 
 int h10x_timing_enable(h10x_ctx *h, int on) { if (!h) return -1; h->c.timing = on != 0; return 0; }

@@ -2078,3 +2078,156 @@ int h10x_session_seqBlocks(h10x_session *s, int minShare, const char *seqPath, c
                    (unsigned long long)t.query, (unsigned long long)t.rows, (unsigned long long)t.withRows, t.maxCount);
   return 0;
 }
+
+/* ---- --seqLinks <minShare> <minBlocks> <endLen> <maxEnds> <seqfile> <out.sl>: which sequence ends share molecules (h10x_row_links_*). The sequence file is
+   read in slabs; the host cuts each sequence's two ends, a slab of ends runs through h10x_seq_blocks_run and its rows go from device memory to the
+   accumulator (h10x_row_links_add_kept): the rows never reach the host, which keeps per sequence its length, the two row counts and the name. The links
+   come back in pieces and are written to <out.sl>.part, renamed when whole. ---- */
+int h10x_host_write_seq_links(const char *path, const h10x_seq_links_head *h, h10x_seq_links_piece_fn piece, void *user, uint64_t pieceLinks, FILE *verbose,
+                              h10x_seq_links_totals *totals, char *err, int errlen) {
+  h10x_seq_links_totals t; memset(&t, 0, sizeof t);
+  const uint64_t nEnds = 2 * h->nSeq, nameBytes = h->nSeq ? h->nameOff[h->nSeq] : 0;
+  if (!pieceLinks) pieceLinks = (uint64_t)1 << 20;
+  const uint64_t cap = h->links < pieceLinks ? h->links : pieceLinks;
+  uint32_t *other = 0, *shared = 0, *pair = 0; unsigned char *seen = 0; FILE *f = 0; int rc = 0;
+  const size_t plen = strlen(path);
+  char *part = (char *)malloc(plen + 6);
+  if (!part) { snprintf(err, (size_t)errlen, "out of host memory"); return -1; }
+  memcpy(part, path, plen); memcpy(part + plen, ".part", 6);
+  if (h->offsets[0] != 0 || h->offsets[nEnds] != h->links) { snprintf(err, (size_t)errlen, "seqLinks: the offsets do not end at the %llu links", (unsigned long long)h->links); free(part); return -1; }
+  if (!(f = fopen(part, "wb"))) { snprintf(err, (size_t)errlen, "failed to open output file %s", path); free(part); return -1; }
+  other = (uint32_t *)malloc((size_t)(cap + 1) * 4); shared = (uint32_t *)malloc((size_t)(cap + 1) * 4); pair = (uint32_t *)malloc((size_t)(cap + 1) * 8);
+  seen = (unsigned char *)calloc((size_t)h->nSeq + 1, 1);
+  if (!other || !shared || !pair || !seen) goto no_memory;
+  {
+    const uint32_t version = 1, zero = 0; unsigned char head[64];
+    memcpy(head, "10XL", 4); memcpy(head + 4, &version, 4); memcpy(head + 8, &h->nBlocks, 4); memcpy(head + 12, &h->minShare, 4); memcpy(head + 16, &h->minBlocks, 4);
+    memcpy(head + 20, &h->endLen, 4); memcpy(head + 24, &h->maxEnds, 4); memcpy(head + 28, &zero, 4);
+    memcpy(head + 32, &h->nSeq, 8); memcpy(head + 40, &h->links, 8); memcpy(head + 48, &h->skippedBlocks, 8); memcpy(head + 56, &nameBytes, 8);
+    if (fwrite(head, 1, sizeof head, f) != sizeof head) goto cannot_write;
+    if (h->nSeq && fwrite(h->table, sizeof(h10x_seq_links_rec), (size_t)h->nSeq, f) != (size_t)h->nSeq) goto cannot_write;
+    if (fwrite(h->offsets, 8, (size_t)nEnds + 1, f) != (size_t)nEnds + 1) goto cannot_write;
+  }
+  {
+    uint64_t e = 0;                                                    /* the end whose row holds the link at hand */
+    for (uint64_t first = 0; first < h->links; first += cap) {
+      const uint64_t m = h->links - first < cap ? h->links - first : cap;
+      if (piece(user, first, m, other, shared) < 0) { rc = -2; goto done; }   /* the callback's own error stands */
+      for (uint64_t i = 0; i < m; ++i) {
+        while (h->offsets[e + 1] <= first + i) ++e;
+        const uint64_t g = other[i];
+        if (g >= nEnds || g <= e) { snprintf(err, (size_t)errlen, "seqLinks: link %llu of end %llu names end %llu", (unsigned long long)(first + i), (unsigned long long)e, (unsigned long long)g); rc = -1; goto done; }
+        pair[2 * i] = other[i]; pair[2 * i + 1] = shared[i];
+        seen[e >> 1] = 1; seen[g >> 1] = 1;
+        if (shared[i] > t.maxShared) t.maxShared = shared[i];
+        if (verbose) fprintf(verbose, "SEQ_LINKS  %s %c %s %c shared %u\n", h->names + h->nameOff[e >> 1], e & 1 ? 'T' : 'H', h->names + h->nameOff[g >> 1],
+                             g & 1 ? 'T' : 'H', shared[i]);
+      }
+      if (fwrite(pair, 8, (size_t)m, f) != (size_t)m) goto cannot_write;
+      ++t.pieces;
+    }
+    for (uint64_t q = 0; q < h->nSeq; ++q) t.withLinks += seen[q];
+    t.nSeq = h->nSeq; t.links = h->links;
+    const uint64_t zero = 0;
+    if (fwrite(h->nSeq ? h->nameOff : &zero, 8, (size_t)h->nSeq + 1, f) != (size_t)h->nSeq + 1 || (nameBytes && fwrite(h->names, 1, (size_t)nameBytes, f) != (size_t)nameBytes))
+      goto cannot_write;
+    const int closed = fclose(f); f = 0;
+    if (closed) goto cannot_write;
+    if (rename(part, path)) goto cannot_write;
+  }
+  if (totals) *totals = t;
+  goto done;
+no_memory:
+  snprintf(err, (size_t)errlen, "out of host memory for the links of %llu sequences", (unsigned long long)h->nSeq); rc = -1; goto done;
+cannot_write:
+  snprintf(err, (size_t)errlen, "failed to write %s", path); rc = -1;
+done:
+  if (f) fclose(f);
+  if (rc) remove(part);
+  free(part); free(other); free(shared); free(pair); free(seen);
+  return rc;
+}
+
+static int sl_piece_from_device(void *user, uint64_t first, uint64_t count, uint32_t *other, uint32_t *shared) {
+  h10x_session *s = (h10x_session *)user;
+  return h10x_row_links_get_range(s->ctx, first, count, other, shared) ? fail_ctx(s) : 0;
+}
+
+int h10x_session_seqLinks(h10x_session *s, int minShare, int minBlocks, int endLen, int maxEnds, const char *seqPath, const char *outPath, FILE *out, int verbose) {
+  if (!s->ctx) return fail(s, "!! you must set hashDepthRange before seqLinks");        /* nothing loaded: no range either */
+  h10x_shard_info_t sh; if (h10x_shard_info(s->ctx, &sh)) return fail_ctx(s);
+  if (sh.nranks > 1) return fail(s, "seqLinks does not run on a sharded session (--gpus > 1)");
+  h10x_list_share_info li;
+  if (h10x_seq_blocks_run(s->ctx, minShare < 1 ? 1 : minShare, 0, 0, 0, 0, &li)) {      /* the state's refusals, before any file is touched */
+    if (strstr(h10x_last_error(s->ctx), "!! you must set hashDepthRange before")) return fail(s, "!! you must set hashDepthRange before seqLinks");
+    return fail_ctx(s);
+  }
+  if (minShare < 1) return fail(s, "!! seqLinks minShare %d must be >= 1", minShare);
+  if (minBlocks < 1) return fail(s, "!! seqLinks minBlocks %d must be >= 1", minBlocks);
+  if (endLen < 0) return fail(s, "!! seqLinks endLen %d must be >= 0", endLen);
+  if (maxEnds < 0) return fail(s, "!! seqLinks maxEnds %d must be >= 0", maxEnds);
+  char msg[512] = ""; int fatal = 0, rc = 0;
+  uint64_t slab = 0; { const int v = h10x_session_get(s, "seq_slab"); slab = v > 0 ? (uint64_t)v : 0; }
+  h10x_seqreader *r = h10x_seq_open(seqPath, msg, (int)sizeof msg, &fatal);
+  if (!r) return fail(s, "%s%sfailed to open sequence file %s", msg, msg[0] ? "\n" : "", seqPath);
+  h10x_seq_links_rec *table = 0; uint64_t *nameOff = 0, *endStart = 0, *rowOff = 0, *offsets = 0; char *names = 0; uint8_t *endCodes = 0;
+  size_t capTable = 0, capNameOff = 0, capNames = 0, capEndStart = 0, capRowOff = 0, capCodes = 0;
+  uint64_t nSeq = 0, nameBytes = 0;
+  char *part = (char *)malloc(strlen(outPath) + 6);                                       /* an output path that cannot be opened fails before the work, not after it */
+  if (!part) { rc = fail(s, "out of host memory"); goto done; }
+  strcpy(part, outPath); strcat(part, ".part");
+  { FILE *probe = fopen(part, "wb"); if (!probe) { rc = fail(s, "failed to open output file %s", outPath); free(part); part = 0; goto done; } fclose(probe); }
+  if (h10x_row_links_begin(s->ctx, li.nBlocks)) { rc = fail_ctx(s); goto done; }
+  if (sb_grow((void **)&nameOff, &capNameOff, 1, 8)) { rc = fail(s, "out of host memory"); goto done; }
+  nameOff[0] = 0;
+  for (;;) {
+    const uint8_t *codes; const uint64_t *seqStart, *nOff; const char *nm; uint32_t n = 0;
+    const int got = h10x_seq_next_named(r, slab, &codes, &seqStart, &n, &nm, &nOff);
+    if (got < 0) { rc = fail(s, "%s", h10x_seq_error(r)); goto done; }
+    if (!got) break;
+    if (nSeq + n >= ((uint64_t)1 << 31)) { rc = fail(s, "seqLinks: 2^31 or more sequences"); goto done; }
+    uint64_t bases = 0;
+    for (uint32_t q = 0; q < n; ++q) { const uint64_t len = seqStart[q + 1] - seqStart[q]; bases += endLen && len > (uint64_t)endLen ? 2 * (uint64_t)endLen : endLen ? 2 * len : len; }
+    if (sb_grow((void **)&table, &capTable, (size_t)(nSeq + n), sizeof *table) || sb_grow((void **)&nameOff, &capNameOff, (size_t)(nSeq + n + 1), 8) ||
+        sb_grow((void **)&endStart, &capEndStart, 2 * (size_t)n + 1, 8) || sb_grow((void **)&rowOff, &capRowOff, 2 * (size_t)n + 1, 8) ||
+        sb_grow((void **)&endCodes, &capCodes, (size_t)bases + 1, 1)) { rc = fail(s, "out of host memory for %u sequences", n); goto done; }
+    uint64_t at = 0; endStart[0] = 0;
+    for (uint32_t q = 0; q < n; ++q) {
+      const uint64_t a = seqStart[q], len = seqStart[q + 1] - a, m = endLen && len > (uint64_t)endLen ? (uint64_t)endLen : len;
+      memcpy(endCodes + at, codes + a, (size_t)m); at += m; endStart[2 * q + 1] = at;                 /* the head: the first m bases */
+      if (endLen) { memcpy(endCodes + at, codes + a + len - m, (size_t)m); at += m; }                 /* the tail: the last m; none at endLen 0 */
+      endStart[2 * q + 2] = at;
+    }
+    if (h10x_seq_blocks_run(s->ctx, minShare, endCodes, endStart, 2 * n, 0, &li)) { rc = fail_ctx(s); goto done; }
+    if (h10x_list_share_get(s->ctx, rowOff, 0, 0, 0)) { rc = fail_ctx(s); goto done; }
+    if (h10x_row_links_add_kept(s->ctx)) { rc = fail_ctx(s); goto done; }
+    for (uint32_t q = 0; q < n; ++q) {
+      h10x_seq_links_rec rec = {seqStart[q + 1] - seqStart[q], (uint32_t)(rowOff[2 * q + 1] - rowOff[2 * q]), (uint32_t)(rowOff[2 * q + 2] - rowOff[2 * q + 1])};
+      table[nSeq + q] = rec;
+      const char *name = nm + nOff[q]; const size_t nl = strlen(name) + 1;
+      if (sb_grow((void **)&names, &capNames, (size_t)nameBytes + nl, 1)) { rc = fail(s, "out of host memory for the names"); goto done; }
+      memcpy(names + nameBytes, name, nl); nameBytes += nl; nameOff[nSeq + q + 1] = nameBytes;
+    }
+    nSeq += n;
+  }
+  {
+    h10x_row_links_info info;
+    if (h10x_row_links_finish(s->ctx, minBlocks, maxEnds, 1, &info)) { rc = fail_ctx(s); goto done; }
+    offsets = (uint64_t *)malloc((2 * (size_t)nSeq + 1) * 8);
+    if (!offsets) { rc = fail(s, "out of host memory for the offsets of %llu sequences", (unsigned long long)nSeq); goto done; }
+    if (h10x_row_links_get(s->ctx, offsets, 0, 0, 0)) { rc = fail_ctx(s); goto done; }
+    h10x_seq_links_head head = {li.nBlocks, (uint32_t)minShare, (uint32_t)minBlocks, (uint32_t)endLen, (uint32_t)maxEnds, nSeq, info.links, info.skippedBlocks,
+                                table, offsets, names, nameOff};
+    h10x_seq_links_totals t;
+    const int w = h10x_host_write_seq_links(outPath, &head, sl_piece_from_device, s, 0, verbose ? out : 0, &t, s->err, (int)sizeof s->err);
+    if (w) { rc = -1; goto done; }                                                        /* (-2: the callback has set the session's text) */
+    if (out) fprintf(out, "  seq links at minShare %d, minBlocks %d, ends %d, maxEnds %d: %llu sequences, %llu row entries, %llu blocks used, %llu blocks skipped, %llu pairs, %llu links, %llu sequences with links, max shared %u\n",
+                     minShare, minBlocks, endLen, maxEnds, (unsigned long long)nSeq, (unsigned long long)info.rowEntries, (unsigned long long)info.blocksUsed,
+                     (unsigned long long)info.skippedBlocks, (unsigned long long)info.pairs, (unsigned long long)info.links, (unsigned long long)t.withLinks, t.maxShared);
+  }
+done:
+  if (rc && part) remove(part);
+  free(part);
+  h10x_seq_close(r); free(table); free(nameOff); free(endStart); free(rowOff); free(offsets); free(names); free(endCodes);
+  return rc;
+}

@@ -175,6 +175,38 @@ int  h10x_host_write_seq_blocks(const char *path, uint32_t nBlocks, uint32_t min
                                 h10x_seq_blocks_totals *totals, char *err, int errlen);
 int  h10x_session_seqBlocks(h10x_session *s, int minShare, const char *seqPath, const char *outPath, FILE *out, int verbose);
 
+/* --seqLinks <minShare> <minBlocks> <endLen> <maxEnds> <seqfile> <out.sl> (addition; include/h10x.h "row links"): which ends of the sequences of a FASTA /
+   FASTQ file are covered by the same blocks: after --clusterSplit and a new range, by the same molecules. Sequence s (0-based, file order) gives end 2s, its
+   first min(len, endLen) bases, and end 2s + 1, its last min(len, endLen) bases, each hashed as a sequence of its own; endLen 0 makes end 2s the whole
+   sequence and end 2s + 1 empty. The row of an end is its --seqBlocks row at minShare; ends e < f are linked when they share at least minBlocks blocks that
+   stand in at most maxEnds ends (0 = no cap); the two ends of one sequence are never linked. The file is read in slabs of "seq_slab" bases; a slab of ends
+   runs through h10x_seq_blocks_run and h10x_row_links_add_kept, so the rows never reach the host: the device holds 8 bytes per row entry of the whole
+   file, the host per sequence its length, its two row counts and its name. h10x_row_links_finish runs once at the end and the links come back in pieces.
+   The file is written as <out.sl>.part and renamed when whole. Little-endian: "10XL", u32 version 1, u32 nBlocks, u32 minShare, u32 minBlocks, u32 endLen,
+   u32 maxEnds, u32 0, u64 nSeq, u64 links, u64 skippedBlocks, u64 nameBytes; nSeq records {u64 len, u32 headRows, u32 tailRows}; 2 nSeq + 1 u64 offsets;
+   links pairs {u32 end, u32 shared}: the row of end e at [offsets[e], offsets[e + 1]), ends f > e ascending; nSeq + 1 u64 name offsets; the names,
+   NUL-terminated, cut at the first blank or tab.
+   out gets one line of counts; verbose != 0 adds one line per link, "SEQ_LINKS  <nameA> <H|T> <nameB> <H|T> shared c". Soft errors as --seqBlocks: no state
+   or no range ("!! you must set hashDepthRange before seqLinks"), "!! seqLinks minShare 0 must be >= 1" and likewise minBlocks (>= 1), endLen and maxEnds
+   (>= 0); a sequence file or an output path that cannot be opened fails without "!!"; 2^31 or more sequences are refused. In every failure no file is
+   written and no .part is left behind.
+   h10x_host_write_seq_links is the writer alone: the tables come ready in the head, the links through a callback that fills other[] / shared[] with links
+   [first, first + count) (0 = done, < 0 = failed), at most pieceLinks at a time (0 = 2^20). It returns -2 when the callback failed (err untouched), -1
+   with err set for its own failures. */
+typedef struct { uint64_t len; uint32_t headRows, tailRows; } h10x_seq_links_rec;
+typedef struct {
+  uint32_t nBlocks, minShare, minBlocks, endLen, maxEnds;
+  uint64_t nSeq, links, skippedBlocks;
+  const h10x_seq_links_rec *table;           /* nSeq */
+  const uint64_t *offsets;                   /* 2 nSeq + 1, from 0 to links */
+  const char *names; const uint64_t *nameOff;   /* nSeq + 1: sequence s is called names + nameOff[s], nameOff[nSeq] = the bytes of all names */
+} h10x_seq_links_head;
+typedef struct { uint64_t nSeq, links, withLinks, pieces; uint32_t maxShared, reserved; } h10x_seq_links_totals;
+typedef int (*h10x_seq_links_piece_fn)(void *user, uint64_t first, uint64_t count, uint32_t *other, uint32_t *shared);
+int  h10x_host_write_seq_links(const char *path, const h10x_seq_links_head *head, h10x_seq_links_piece_fn piece, void *user, uint64_t pieceLinks, FILE *verbose,
+                               h10x_seq_links_totals *totals, char *err, int errlen);
+int  h10x_session_seqLinks(h10x_session *s, int minShare, int minBlocks, int endLen, int maxEnds, const char *seqPath, const char *outPath, FILE *out, int verbose);
+
 /* --writeMosh <bits> <copy1min> <copy2min> <copyMmin> <out.mosh> (addition; include/h10x.h "the state as a mosh set"): the in-range hashes of the state as
    an MSHSTv1 file that moshutils, moshasm and moshmap read: the state's hash values, depths saturated to 16 bits, copy classes from depth by the three
    thresholds of moshutils -s and, where a --hashCopies result is kept, corrected by linkage. bits = the table bits of the set, 0 = the state's -B. The file

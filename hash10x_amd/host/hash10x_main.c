@@ -9,7 +9,7 @@
  * print "FATAL ERROR: <the reference's message>" and exit(-1) like die() (utils.c:18-29). The dispatch itself is a
  * table of commands, not the reference's if-chain.
  * --interactive reads further commands from stdin, one line each, as the reference does (hash10x.c:1281-1300).
- * Additions: --device <n>, --gpus <n>, --sortFQB, --codeCensus, --fixFQB, --fixFQBThresh, --moleculeMap, --splitFQB, --shareGraph, --shareComponents, --hashCopies, --writeMosh, --seqBlocks; the resource line also carries wall-clock seconds.
+ * Additions: --device <n>, --gpus <n>, --sortFQB, --codeCensus, --fixFQB, --fixFQBThresh, --moleculeMap, --splitFQB, --shareGraph, --shareComponents, --hashCopies, --writeMosh, --seqBlocks, --seqLinks; the resource line also carries wall-clock seconds.
  */
 #define _GNU_SOURCE
 #include <stdio.h>
@@ -158,6 +158,7 @@ static void usage(void) {
   fprintf(stderr, "   --hashCopies <minShare> <hc output>: for every hash in the depth range the linkage groups of the blocks that hold it: distinct blocks, groups, largest, second (needs hashDepthRange)\n");
   fprintf(stderr, "   --writeMosh <bits> <copy1min> <copy2min> <copyMmin> <mosh output>: the hashes in the depth range as a mosh set for moshutils / moshasm / moshmap: depths cut to 16 bits, copy classes from depth, corrected by a kept --hashCopies result (bits 0: as -B; needs hashDepthRange)\n");
   fprintf(stderr, "   --seqBlocks <minShare> <sequence file> <sb output>: for every sequence of a fasta/fastq file (gzip or plain) the blocks that stand at least minShare times in the barcode lists of its hashes in the depth range, with the counts (needs hashDepthRange; after --clusterSplit: the molecules; --verbose: a SEQ_BLOCKS line per sequence)\n");
+  fprintf(stderr, "   --seqLinks <minShare> <minBlocks> <endLen> <maxEnds> <sequence file> <sl output>: which ends of the sequences (the first and last endLen bases; 0: whole sequences) share at least minBlocks blocks of their --seqBlocks rows at minShare, leaving out blocks that stand in more than maxEnds ends (0: none) (needs hashDepthRange; after --clusterSplit: the molecules; --verbose: a SEQ_LINKS line per link)\n");
   fprintf(stderr, "   --cribBuild <genome1.fa> <genome2.fa>: match to genomic hashes\n");
   fprintf(stderr, "   --clusterReport <codeMin> <codeMax>\n");
   fprintf(stderr, "   --cribSummary\n");
@@ -316,6 +317,9 @@ static void cmd_writeMosh(char **a) { one_gpu("--writeMosh"); nb_done(h10x_sessi
 /* from a sequence to its blocks: the census needs every barcode's lists on one GPU */
 static void cmd_seqBlocks(char **a) { one_gpu("--seqBlocks"); nb_done(h10x_session_seqBlocks(team.s[0], atoi(a[0]), a[1], a[2], outFile, isVerbose)); }
 
+/* which sequence ends share blocks: the rows are those of --seqBlocks, so one GPU */
+static void cmd_seqLinks(char **a) { one_gpu("--seqLinks"); nb_done(h10x_session_seqLinks(team.s[0], atoi(a[0]), atoi(a[1]), atoi(a[2]), atoi(a[3]), a[4], a[5], outFile, isVerbose)); }
+
 typedef struct { const char *name; int nArgs; void (*run)(char **args); const char *param; } Command;
 static const Command commands[] = {
   {"-k", 1, 0, "k"}, {"-w", 1, 0, "w"}, {"-r", 1, 0, "r"}, {"-B", 1, 0, "B"}, {"-N", 1, 0, "N"}, {"-c", 1, 0, "c"},
@@ -327,7 +331,7 @@ static const Command commands[] = {
   {"--hashDepthRange", 2, cmd_hashDepthRange, 0}, {"--cluster", 2, cmd_cluster, 0}, {"--clusterSplit", 0, cmd_clusterSplit, 0},
   {"--codeCensus", 3, cmd_codeCensus, 0}, {"--fixFQB", 3, cmd_fixFQB, 0}, {"--fixFQBThresh", 3, cmd_fixFQBThresh, 0},
   {"--moleculeMap", 1, cmd_moleculeMap, 0}, {"--splitFQB", 2, cmd_splitFQB, 0}, {"--shareGraph", 2, cmd_shareGraph, 0}, {"--shareComponents", 2, cmd_shareComponents, 0},
-  {"--hashCopies", 2, cmd_hashCopies, 0}, {"--writeMosh", 5, cmd_writeMosh, 0}, {"--seqBlocks", 3, cmd_seqBlocks, 0},
+  {"--hashCopies", 2, cmd_hashCopies, 0}, {"--writeMosh", 5, cmd_writeMosh, 0}, {"--seqBlocks", 3, cmd_seqBlocks, 0}, {"--seqLinks", 6, cmd_seqLinks, 0},
   {"--sortFQB", 2, cmd_sortFQB, 0}, {"--cribBuild", 2, cmd_cribBuild, 0}, {"--clusterReport", 2, cmd_clusterReport, 0},
   {"--cribSummary", 0, cmd_cribSummary, 0}, {"--hashStats", 0, cmd_hashStats, 0}, {"--codeStats", 0, cmd_codeStats, 0},
   {"--hashInfo", 3, cmd_hashInfo, 0}, {"--hashExplore", 1, cmd_hashExplore, 0}, {"--doubleShared", 2, cmd_doubleShared, 0},

@@ -25,7 +25,7 @@ extern "C" {
 /* 2 (round 5): h10x_warm, h10x_alloc_stats, h10x_pinned_*, h10x_ingest_fqb_async / _wait, H10X_TABLE_CLUSTER_RAW, the exchange counters of
    h10x_counters; option "cluster_dbg_skip" gone.
    3: h10x_counters.shard_reply_path, options "shard_reply_sort" 2 .. 4 and "shard_owner_cut". Entry points added since (the census, share graph, components,
-   hash copies, mosh sets, readsets, reference maps, h10x_mosh_from_state, h10x_seq_hashes / h10x_list_share_* / h10x_seq_blocks_run) change no existing struct or table and leave the version alone.
+   hash copies, mosh sets, readsets, reference maps, h10x_mosh_from_state, h10x_seq_hashes / h10x_list_share_* / h10x_seq_blocks_run, h10x_row_links_*) change no existing struct or table and leave the version alone.
    libh10x_host.so and the Python loader refuse a libh10x_hip.so of another version. */
 #define H10X_ABI_VERSION 3
 
@@ -643,6 +643,45 @@ int  h10x_seq_blocks_run(h10x_ctx *ctx, int64_t minShare, const uint8_t *codes, 
                          h10x_list_share_info *info);
 int  h10x_list_share_get(h10x_ctx *ctx, uint64_t *offsets, uint32_t *block, uint32_t *count, uint64_t cap);
 int  h10x_list_share_get_device(h10x_ctx *ctx, uint64_t *dev_offsets, uint32_t *dev_block, uint32_t *dev_count, uint64_t cap);
+
+/* ---- row links (csrc/stage_q.hip): which lists of block numbers share blocks; with the --seqBlocks rows of sequence ends as the lists, which
+   contig or long-read ends are covered by the same molecules (--seqLinks) ----
+   Input: lists of block numbers in CSR form (offsets[nLists + 1] from 0, block[]), each strictly ascending, every block < nBlocks. They are
+   accumulated on the device, numbered 0, 1, .. in the order they are added, however they are cut into calls.
+   ends(d) = the number of lists that hold block d. A block is used when maxLists == 0 or ends(d) <= maxLists (the multiplicity cap of the
+   linked-read scaffolders: a block in every list would cost ends(d)^2 pairs and says nothing). For lists e < f, shared(e, f) = the number of
+   used blocks in both. With siblings != 0 lists 2s and 2s + 1 (the two ends of sequence s) are never linked. The result at minBlocks = M >= 1 is,
+   per list e, the row {(f, shared(e, f)) : f > e, shared >= M} ascending in f, in CSR form like the share graph: the upper triangle only.
+   h10x_row_links_begin starts an accumulator for blocks < nBlocks and drops an earlier one with its links.
+   h10x_row_links_add appends nLists host rows. A list that does not ascend strictly or holds an entry >= nBlocks is refused ("!! rowLinks list Q
+     entry E: block X is not ascending" / "... is not below N", Q counted over all lists added) and the call appends nothing.
+   h10x_row_links_add_kept appends the rows kept by the last h10x_list_share_run / h10x_seq_blocks_run straight from device memory (their blocks
+     ascend and are below the state's nBlocks, which must not exceed the accumulator's); it needs a state with a range in force and kept rows.
+   h10x_row_links_finish: every row entry is a key block << listBits | list; a sort makes a block's run the ascending list of its ends; per row
+     entry, in (list, block) order, the later members of its block's run are its partners, and the exclusive sum of their numbers places every
+     unit (no atomics); one lane per pair writes the key (e - first list of batch) << listBits | f, 32-bit where it fits; a sort and a run pass keep
+     the runs of length >= M. Batches are cut by list against "neighbour_budget" (pairs), a list above it runs alone in windows of f; both are
+     counted in h10x_neighbour_stats. info: lists, rowEntries, blocksUsed and skippedBlocks (blocks with ends(d) >= 1, by the cap), pairs = the
+     keys gathered, links = the result's entries, maxShared (0 without links), batches, windows, wideBatches = the batches that took 64-bit keys.
+     It may be called again with other arguments: the accumulator stays. minBlocks < 1: "!! seqLinks minBlocks 0 must be >= 1"; more than
+     2^32 - 1 lists (or 2^32 - 2 row entries) are refused.
+   h10x_row_links_get / _get_device copy the kept links out as h10x_share_graph_get does: offsets[lists + 1] and the first min(cap, links) entries.
+   The result depends on none of the cut into add calls, "neighbour_budget", "seq_slab", the order in which anything lands, or the run: two
+   calls give the same bytes. The accumulator and the kept links are released by the next begin (also a refused one), h10x_depth_range,
+   h10x_cluster_split, a new state and h10x_destroy. These calls neither release nor change a kept share graph, components, --hashCopies result
+   or the lists and rows of h10x_seq_blocks_run. begin, add and finish need a context, not a state; all are refused on a sharded context. */
+typedef struct {
+  uint64_t lists, rowEntries, blocksUsed, skippedBlocks, pairs, links;
+  uint32_t maxShared, batches, windows, wideBatches;
+} h10x_row_links_info;
+int  h10x_row_links_begin(h10x_ctx *ctx, uint32_t nBlocks);
+int  h10x_row_links_add(h10x_ctx *ctx, const uint64_t *offsets, const uint32_t *block, uint64_t nLists);
+int  h10x_row_links_add_kept(h10x_ctx *ctx);
+int  h10x_row_links_finish(h10x_ctx *ctx, int64_t minBlocks, int64_t maxLists, int32_t siblings, h10x_row_links_info *info);
+int  h10x_row_links_get(h10x_ctx *ctx, uint64_t *offsets, uint32_t *other, uint32_t *shared, uint64_t cap);
+int  h10x_row_links_get_device(h10x_ctx *ctx, uint64_t *dev_offsets, uint32_t *dev_other, uint32_t *dev_shared, uint64_t cap);
+/* links [first, first + count) of the kept result to host memory (either array may be NULL): a writer takes the links in pieces */
+int  h10x_row_links_get_range(h10x_ctx *ctx, uint64_t first, uint64_t count, uint32_t *other, uint32_t *shared);
 
 /* ---- readsets (csrc/stage_h.hip): the Readset object of the reference's moshasm (moshasm.c) over a mosh set ----
    Long reads kept as their mosh hits only: per read the set indices hit, in position order (top bit = the forward hash was strictly
