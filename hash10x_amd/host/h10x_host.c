@@ -1,6 +1,8 @@
-/* h10x_host.c — see h10x_host.h. Plain C; links libh10x_hip.so. No compute here: files, Array bookkeeping, text. */
+/* h10x_host.c — see h10x_host.h. Plain C; links libh10x_hip.so. No compute here: the session, the commands' device walks, Array bookkeeping, text, and the
+   reference's own files (.hash, .fqb records). The writers of the project's formats, which need no device, are in files_host.c; what a command writes goes
+   through its OutFile, so an output stands under its name only when it is whole. */
 #define _GNU_SOURCE
-#include "h10x_host.h"
+#include "files_host.h"
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -782,7 +784,6 @@ int h10x_session_codeStats(h10x_session *s, FILE *f) {         /* codeSizeHist: 
  * looked up on the device (h10x_crib_genome / h10x_crib_finish) and the per-cluster figures are reduced there
  * (h10x_cluster_report); what is left here is the FASTA reader and the text.
  * ------------------------------------------------------------------------------------------------------------------- */
-static const char *const cribTypeName[5] = {"err", "htA", "htB", "hom", "mul"};     /* hash10x.c:417 */
 
 /* One genome as readSequence() + dna2indexConv deliver it to cribAddGenome (readseq.c:66-152, 513-522, hash10x.c:432):
    '>' anywhere starts a record, blanks / tabs / newlines are skipped, ACGT in either case are 0..3, N is 0, any other
@@ -1240,43 +1241,25 @@ done:
 /* ---- --moleculeMap, --splitFQB: the molecule of every read pair of the sorted file, and the file in molecule order (include/h10x.h "the molecule of every
    read pair"; what --clusterReport counts and --clusterSplit renumbers, hash10x.c:897-920, 979-989, written per record). The two small formats are written
    by plain functions over arrays, which never touch the GPU. ---- */
-static int put_err(char *err, int errlen, const char *fmt, const char *path) { if (err) snprintf(err, (size_t)errlen, fmt, path); return -1; }
-int h10x_host_write_molmap(const char *path, const uint32_t *mol, const uint32_t *slot, const h10x_molmap_info *info, char *err, int errlen) {
-  FILE *f = fopen(path, "wb");
-  if (!f) return put_err(err, errlen, "failed to open output file %s", path);
-  unsigned char head[32]; const uint32_t version = 1;
-  memcpy(head, "10XM", 4); memcpy(head + 4, &version, 4); memcpy(head + 8, &info->nRecords, 8); memcpy(head + 16, &info->nBlocks, 4);
-  memcpy(head + 20, &info->nMolecules, 4); memcpy(head + 24, &info->nClustered, 8);
-  int ok = fwrite(head, 1, 32, f) == 32;
-  enum { RUN = 1 << 16 };
-  uint32_t *pair = (uint32_t *)malloc((size_t)RUN * 8);
-  if (!pair) { fclose(f); return put_err(err, errlen, "out of host memory writing %s", path); }
-  for (uint64_t at = 0; ok && at < info->nRecords; at += RUN) {
-    const uint64_t m = info->nRecords - at < RUN ? info->nRecords - at : RUN;
-    for (uint64_t i = 0; i < m; ++i) { pair[2 * i] = mol[at + i]; pair[2 * i + 1] = slot[at + i]; }
-    ok = fwrite(pair, 8, m, f) == m;
-  }
-  free(pair);
-  if (fclose(f)) ok = 0;
-  return ok ? 0 : put_err(err, errlen, "failed to write %s", path);
+/* what the commands on a whole state ask first: a state, on one GPU. NO_RANGE: the command needs a depth range, and says that where nothing is loaded either. */
+enum { NO_STATE = 0, NO_RANGE = 1 };
+/* room for `rows` entries in two u32 arrays whose old content is not needed */
+static int rows_room(h10x_session *s, uint32_t **a, uint32_t **b, size_t *cap, uint64_t rows) {
+  if (rows <= *cap) return 0;
+  free(*a); free(*b);
+  *cap = (size_t)(rows + rows / 2);
+  *a = (uint32_t *)malloc(*cap * 4); *b = (uint32_t *)malloc(*cap * 4);
+  if (*a && *b) return 0;
+  *cap = 0; return fail(s, "out of host memory for %llu rows", (unsigned long long)rows);
 }
-int h10x_host_write_split_index(const char *path, const uint64_t *start, uint32_t nBlocks, uint32_t nMolecules, char *err, int errlen) {
-  FILE *f = fopen(path, "wb");
-  if (!f) return put_err(err, errlen, "failed to open output file %s", path);
-  unsigned char head[16]; const uint32_t version = 1; const uint64_t n = (uint64_t)nBlocks + nMolecules + 1;
-  memcpy(head, "10XS", 4); memcpy(head + 4, &version, 4); memcpy(head + 8, &nBlocks, 4); memcpy(head + 12, &nMolecules, 4);
-  int ok = fwrite(head, 1, 16, f) == 16 && fwrite(start, 8, n, f) == n;
-  if (fclose(f)) ok = 0;
-  return ok ? 0 : put_err(err, errlen, "failed to write %s", path);
-}
-static int one_rank(h10x_session *s, const char *name) {
-  if (!s->ctx) return fail(s, "%s: no hash state loaded: use readFQB or readHash first", name);
+static int whole_state(h10x_session *s, const char *name, int without) {
+  if (!s->ctx) return without == NO_RANGE ? fail(s, "!! you must set hashDepthRange before %s", name) : fail(s, "%s: no hash state loaded: use readFQB or readHash first", name);
   h10x_shard_info_t z; if (h10x_shard_info(s->ctx, &z)) return fail_ctx(s);
   if (z.nranks > 1) return fail(s, "%s does not run on a sharded session (--gpus > 1)", name);
   return 0;
 }
 int h10x_session_moleculeMap(h10x_session *s, const char *outPath, FILE *out) {
-  if (one_rank(s, "moleculeMap")) return -1;
+  if (whole_state(s, "moleculeMap", NO_STATE)) return -1;
   h10x_molmap_info info; memset(&info, 0, sizeof info);
   if (h10x_molecule_map(s->ctx, 0, 0, 0, &info)) return fail_ctx(s);                   /* the refusals and R */
   const size_t n = info.nRecords ? (size_t)info.nRecords : 1;
@@ -1292,7 +1275,7 @@ int h10x_session_moleculeMap(h10x_session *s, const char *outPath, FILE *out) {
 }
 /* the whole image at once, as --sortFQB */
 int h10x_session_splitFQB(h10x_session *s, const char *inPath, const char *outPath, FILE *out) {
-  if (one_rank(s, "splitFQB")) return -1;
+  if (whole_state(s, "splitFQB", NO_STATE)) return -1;
   h10x_molmap_info info; memset(&info, 0, sizeof info);
   if (h10x_molecule_map(s->ctx, 0, 0, 0, &info)) return fail_ctx(s);
   FILE *f = fopen(inPath, "rb");
@@ -1321,56 +1304,6 @@ done:
 /* ---- --codeCensus, --fixFQB, --fixFQBThresh: the barcode step between fq2b and --sortFQB on the packed file (fq2b.c:71-104 and the README's
    goodcodes pipeline, README.md:44; README.md:57-62 wishes for `fq2b -10xThresh`). The records pass through the device in batches of
    "fqb_slab" records: the host holds one batch of input and one of output, never the file. ---- */
-static void pack_init(uint8_t *sym) { memset(sym, 0, 256); sym['c'] = sym['C'] = 1; sym['g'] = sym['G'] = 2; sym['t'] = sym['T'] = 3; }   /* a, A, N, anything else: 0 (fq2b.c:27-28) */
-/* the whitelist text as fq2b-amd reads it (read10xWhitelist, fq2b.c:71-94): blank-separated words of 16 characters in line order; never touches the GPU */
-int h10x_host_whitelist_read(const char *path, uint32_t **codes, uint64_t *n, char *err, int errlen) {
-  uint8_t sym[256]; pack_init(sym);
-  *codes = 0; *n = 0;
-  FILE *f = fopen(path, "r");
-  if (!f) { if (err) snprintf(err, (size_t)errlen, "failed to open 10x whitelist file %s\n", path); return -1; }
-  size_t cap = 1 << 16, m = 0; uint32_t *c = (uint32_t *)malloc(cap * 4);
-  char word[64]; int rc = 0;
-  while (c && fscanf(f, "%63s", word) == 1) {
-    if (strlen(word) != 16) { if (err) snprintf(err, (size_t)errlen, "bad barcode line %d in %s: %s", (int)m + 1, path, word); rc = -1; break; }
-    if (m == cap) { cap *= 2; uint32_t *c2 = (uint32_t *)realloc(c, cap * 4); if (!c2) { free(c); c = 0; break; } c = c2; }
-    uint32_t v = 0; for (int i = 0; i < 16; ++i) v = (v << 2) | sym[(unsigned char)word[i]];
-    c[m++] = v;
-  }
-  fclose(f);
-  if (!c) { if (err) snprintf(err, (size_t)errlen, "out of host memory for the whitelist"); return -1; }
-  if (rc) { free(c); return rc; }
-  *codes = c; *n = m;
-  return 0;
-}
-void h10x_host_whitelist_free(uint32_t *codes) { free(codes); }
-int h10x_host_whitelist_write(const char *path, const uint32_t *codes, uint64_t n, char *err, int errlen) {
-  FILE *f = fopen(path, "w");
-  if (!f) { if (err) snprintf(err, (size_t)errlen, "failed to open output file %s", path); return -1; }
-  char line[17]; line[16] = '\n';
-  for (uint64_t i = 0; i < n; ++i) {
-    for (int b = 0; b < 16; ++b) line[15 - b] = "ACGT"[(codes[i] >> (2 * b)) & 3];     /* uSeq (fq2b.c:44-50) */
-    if (fwrite(line, 1, 17, f) != 17) { fclose(f); if (err) snprintf(err, (size_t)errlen, "failed to write %s", path); return -1; }
-  }
-  if (fclose(f)) { if (err) snprintf(err, (size_t)errlen, "failed to write %s", path); return -1; }
-  return 0;
-}
-/* the line a barcode is looked up under: the LAST line that holds it (later lines overwrite earlier ones in the reference's byte table, fq2b.c:89), 0 = absent */
-static int cmp_u64(const void *a, const void *b) { const uint64_t x = *(const uint64_t *)a, y = *(const uint64_t *)b; return x < y ? -1 : x > y; }
-int h10x_host_whitelist_lines(const uint32_t *codes, uint64_t n, const uint32_t *query, uint64_t nq, uint32_t *lines) {
-  uint64_t *k = (uint64_t *)malloc((n ? n : 1) * 8);
-  if (!k) return -1;
-  for (uint64_t i = 0; i < n; ++i) k[i] = (uint64_t)codes[i] << 32 | (uint32_t)(i + 1);
-  qsort(k, n, 8, cmp_u64);
-  for (uint64_t q = 0; q < nq; ++q) {                                                 /* the last entry of the barcode's run = its largest line */
-    const uint64_t top = (uint64_t)query[q] << 32 | 0xFFFFFFFFu;
-    uint64_t lo = 0, hi = n;
-    while (lo < hi) { const uint64_t mid = lo + (hi - lo) / 2; if (k[mid] <= top) lo = mid + 1; else hi = mid; }
-    lines[q] = lo && (uint32_t)(k[lo - 1] >> 32) == query[q] ? (uint32_t)k[lo - 1] : 0;
-  }
-  free(k);
-  return 0;
-}
-
 static uint64_t session_slab(const h10x_session *s) { const int v = h10x_session_get(s, "fqb_slab"); return v > 0 ? (uint64_t)v : (uint64_t)1 << 20; }
 typedef struct { FILE *f; const char *path; uint64_t n; } FqbFile;
 static int fqb_open(h10x_session *s, const char *path, FqbFile *in) {
@@ -1715,9 +1648,8 @@ static int ce_by_count(const void *a, const void *b) {          /* compareCount 
   return x->code > y->code ? -1 : x->code < y->code;
 }
 int h10x_session_codeExplore(h10x_session *s, int code, FILE *out, FILE *err) {
-  if (!s->ctx) return fail(s, "!! you must set hashDepthRange before codeExplore");   /* nothing loaded: no range either */
+  if (whole_state(s, "codeExplore", NO_RANGE)) return -1;
   h10x_shard_info_t z; if (h10x_shard_info(s->ctx, &z)) return fail_ctx(s);
-  if (z.nranks > 1) return fail(s, "codeExplore does not run on a sharded session (--gpus > 1)");
   h10x_code_explore_rep rep;
   if (h10x_code_explore(s->ctx, code, s->ct, &rep)) return fail_ctx(s);
   if (!rep.nGood) return 0;                                       /* hash10x.c:1361 */
@@ -1757,54 +1689,38 @@ done:
   return rc;
 }
 
-/* ---- --shareGraph <minShare> <out.sg>: the graph of all blocks (h10x_share_graph_run) written range by range, so that neither the host nor the
-   device ever holds all rows: the header and the offsets are left blank first and filled in at the end. ---- */
+/* ---- --shareGraph <minShare> <out.sg>: the graph of all blocks (h10x_share_graph_run), range by range, so that neither the host nor the device ever holds
+   all rows: the walk is here, the file is h10x_host_write_share_graph's, which asks for one range after the other. ---- */
+typedef struct { h10x_session *s; int minShare; uint64_t *off; uint32_t *blk, *cnt; size_t capRows; uint64_t listEntries; uint32_t maxCount; } SgFeed;
+static int sg_range_from_device(void *user, uint32_t c0, uint32_t c1, h10x_share_graph_range *r) {
+  SgFeed *z = (SgFeed *)user; h10x_session *s = z->s; h10x_share_graph_info info;
+  if (h10x_share_graph_run(s->ctx, z->minShare, c0, c1, &info)) return fail_ctx(s);
+  if (rows_room(s, &z->blk, &z->cnt, &z->capRows, info.rows)) return -1;
+  if (h10x_share_graph_get(s->ctx, z->off, z->blk, z->cnt, info.rows)) return fail_ctx(s);
+  r->part = z->off; r->blk = z->blk; r->cnt = z->cnt; r->rows = info.rows;
+  z->listEntries += info.listEntries; if (info.maxCount > z->maxCount) z->maxCount = info.maxCount;
+  return 0;
+}
 int h10x_session_shareGraph(h10x_session *s, int minShare, const char *outPath, FILE *out) {
-  if (!s->ctx) return fail(s, "!! you must set hashDepthRange before shareGraph");    /* nothing loaded: no range either */
-  h10x_shard_info_t z; if (h10x_shard_info(s->ctx, &z)) return fail_ctx(s);
-  if (z.nranks > 1) return fail(s, "shareGraph does not run on a sharded session (--gpus > 1)");
+  if (whole_state(s, "shareGraph", NO_RANGE)) return -1;
   h10x_share_graph_info info;
   if (h10x_share_graph_run(s->ctx, minShare, 1, 1, &info)) return fail_ctx(s);          /* the refusals, before the file is touched */
-  const uint32_t nBlocks = info.nBlocks, step = s->sgBlocks > 0 ? (uint32_t)s->sgBlocks : 8192u;
-  int rc = 0; FILE *f = 0; uint64_t *offsets = 0, *part = 0; uint32_t *blk = 0, *cnt = 0, *pair = 0; uint64_t cap = 0;
-  uint64_t rows = 0, listEntries = 0; uint32_t maxCount = 0;
-  const uint32_t version = 1, T = (uint32_t)minShare; unsigned char head[24];
-  offsets = (uint64_t *)calloc((size_t)nBlocks + 1, 8); part = (uint64_t *)malloc(((size_t)step + 1) * 8);
-  if (!offsets || !part) { rc = fail(s, "out of host memory for the offsets of %u blocks", nBlocks); goto done; }
-  if (!(f = fopen(outPath, "wb"))) { rc = fail(s, "failed to open output file %s", outPath); goto done; }
-  memset(head, 0, sizeof head);
-  if (fwrite(head, 1, 24, f) != 24 || fwrite(offsets, 8, (size_t)nBlocks + 1, f) != (size_t)nBlocks + 1) { rc = fail(s, "failed to write %s", outPath); goto done; }
-  for (uint32_t c0 = 0; c0 < nBlocks; c0 += step) {               /* (block 0 is unused: its row is empty) */
-    const uint32_t c1 = nBlocks - c0 < step ? nBlocks : c0 + step;
-    if (h10x_share_graph_run(s->ctx, minShare, c0, c1, &info)) { rc = fail_ctx(s); goto done; }
-    if (info.rows > cap) {
-      cap = info.rows + info.rows / 2;
-      free(blk); free(cnt); free(pair);
-      blk = (uint32_t *)malloc((size_t)cap * 4); cnt = (uint32_t *)malloc((size_t)cap * 4); pair = (uint32_t *)malloc((size_t)cap * 8);
-      if (!blk || !cnt || !pair) { rc = fail(s, "out of host memory for %llu rows", (unsigned long long)cap); goto done; }
-    }
-    if (h10x_share_graph_get(s->ctx, part, blk, cnt, info.rows)) { rc = fail_ctx(s); goto done; }
-    for (uint32_t q = 0; q <= c1 - c0; ++q) offsets[c0 + q] = rows + part[q];
-    for (uint64_t i = 0; i < info.rows; ++i) { pair[2 * i] = blk[i]; pair[2 * i + 1] = cnt[i]; }
-    if (info.rows && fwrite(pair, 8, (size_t)info.rows, f) != (size_t)info.rows) { rc = fail(s, "failed to write %s", outPath); goto done; }
-    rows += info.rows; listEntries += info.listEntries; if (info.maxCount > maxCount) maxCount = info.maxCount;
-  }
-  memcpy(head, "10XG", 4); memcpy(head + 4, &version, 4); memcpy(head + 8, &nBlocks, 4); memcpy(head + 12, &T, 4); memcpy(head + 16, &rows, 8);
-  if (fseeko(f, 0, SEEK_SET) || fwrite(head, 1, 24, f) != 24 || fwrite(offsets, 8, (size_t)nBlocks + 1, f) != (size_t)nBlocks + 1) { rc = fail(s, "failed to write %s", outPath); goto done; }
-  if (out) fprintf(out, "  share graph at minShare %d: %u blocks, %llu rows, %llu list entries, max count %u\n", minShare, nBlocks,
-                   (unsigned long long)rows, (unsigned long long)listEntries, maxCount);
-done:
-  if (f && fclose(f) && !rc) rc = fail(s, "failed to write %s", outPath);
-  free(offsets); free(part); free(blk); free(cnt); free(pair);
-  return rc;
+  const uint32_t step = s->sgBlocks > 0 ? (uint32_t)s->sgBlocks : 8192u;
+  SgFeed z; memset(&z, 0, sizeof z); z.s = s; z.minShare = minShare;
+  if (!(z.off = (uint64_t *)malloc(((size_t)step + 1) * 8))) return fail(s, "out of host memory for the offsets of %u blocks", info.nBlocks);
+  uint64_t rows = 0;
+  const int w = h10x_host_write_share_graph(outPath, info.nBlocks, (uint32_t)minShare, step, sg_range_from_device, &z, &rows, s->err, (int)sizeof s->err);
+  free(z.off); free(z.blk); free(z.cnt);
+  if (w) return -1;                                                                       /* (-2: the callback has set the session's text) */
+  if (out) fprintf(out, "  share graph at minShare %d: %u blocks, %llu rows, %llu list entries, max count %u\n", minShare, info.nBlocks,
+                   (unsigned long long)rows, (unsigned long long)z.listEntries, z.maxCount);
+  return 0;
 }
 
 /* ---- --shareComponents <minShare> <out.sc>: the connected components of the share graph over all blocks (h10x_share_components_*). The blocks are walked
    in the ranges of --shareGraph; each range's rows are folded into the device's label array where the census made them, and only the labels come back. ---- */
 int h10x_session_shareComponentsRun(h10x_session *s, int minShare, h10x_share_components_info *info) {
-  if (!s->ctx) return fail(s, "!! you must set hashDepthRange before shareComponents");   /* nothing loaded: no range either */
-  h10x_shard_info_t z; if (h10x_shard_info(s->ctx, &z)) return fail_ctx(s);
-  if (z.nranks > 1) return fail(s, "shareComponents does not run on a sharded session (--gpus > 1)");
+  if (whole_state(s, "shareComponents", NO_RANGE)) return -1;
   if (h10x_share_components_begin(s->ctx, minShare)) return fail_ctx(s);                /* the refusals */
   h10x_sizes zs; if (h10x_get_sizes(s->ctx, &zs)) return fail_ctx(s);
   const uint32_t nBlocks = zs.nBlocks, step = s->sgBlocks > 0 ? (uint32_t)s->sgBlocks : 8192u;
@@ -1813,25 +1729,6 @@ int h10x_session_shareComponentsRun(h10x_session *s, int minShare, h10x_share_co
     if (h10x_share_components_add(s->ctx, c0, c1)) return fail_ctx(s);
   }
   if (h10x_share_components_finish(s->ctx, info)) return fail_ctx(s);
-  return 0;
-}
-
-int h10x_host_write_share_components(const char *path, const h10x_share_components_info *info, const uint32_t *comp, const uint32_t *rootOf,
-                                     const uint32_t *blocks, const uint64_t *records, char *err, int errlen) {
-  FILE *f = fopen(path, "wb");
-  if (!f) { snprintf(err, (size_t)errlen, "failed to open output file %s", path); return -1; }
-  const uint32_t version = 1; unsigned char head[32]; int ok = 1;
-  memcpy(head, "10XC", 4); memcpy(head + 4, &version, 4); memcpy(head + 8, &info->nBlocks, 4); memcpy(head + 12, &info->minShare, 4);
-  memcpy(head + 16, &info->nComponents, 4); memcpy(head + 20, &info->largest, 4); memcpy(head + 24, &info->rows, 8);
-  ok = fwrite(head, 1, 32, f) == 32;
-  if (ok && info->nBlocks) ok = fwrite(comp, 4, info->nBlocks, f) == info->nBlocks;
-  for (uint32_t k = 0; ok && k <= info->nComponents; ++k) {
-    unsigned char e[16];
-    memcpy(e, rootOf + k, 4); memcpy(e + 4, blocks + k, 4); memcpy(e + 8, records + k, 8);
-    ok = fwrite(e, 1, 16, f) == 16;
-  }
-  if (fclose(f)) ok = 0;
-  if (!ok) { snprintf(err, (size_t)errlen, "failed to write %s", path); return -1; }
   return 0;
 }
 
@@ -1855,34 +1752,9 @@ done:
 /* ---- --hashCopies <minShare> <out.hc>: per in-range hash the linkage groups of its own blocks (h10x_hash_copies_*). The table stays on the device;
    the file is written in slabs of 2^22 hashes, so the host never holds it. ---- */
 int h10x_session_hashCopiesRun(h10x_session *s, int minShare, h10x_hash_copies_info *info) {
-  if (!s->ctx) return fail(s, "!! you must set hashDepthRange before hashCopies");      /* nothing loaded: no range either */
-  h10x_shard_info_t z; if (h10x_shard_info(s->ctx, &z)) return fail_ctx(s);
-  if (z.nranks > 1) return fail(s, "hashCopies does not run on a sharded session (--gpus > 1)");
+  if (whole_state(s, "hashCopies", NO_RANGE)) return -1;
   if (h10x_hash_copies_run(s->ctx, minShare, info)) return fail_ctx(s);
   return 0;
-}
-
-int h10x_host_write_hash_copies(const char *path, const h10x_hash_copies_info *info, h10x_hash_copies_slab_fn slab, void *user, uint64_t slabHashes,
-                                char *err, int errlen) {
-  if (!slabHashes) slabHashes = (uint64_t)1 << 22;
-  const uint64_t n = info->hashNumber, cap = n < slabHashes ? (n ? n : 1) : slabHashes;
-  uint16_t *buf = (uint16_t *)malloc((size_t)cap * 8);
-  if (!buf) { snprintf(err, (size_t)errlen, "out of host memory for a slab of %llu hashes", (unsigned long long)cap); return -1; }
-  FILE *f = fopen(path, "wb");
-  if (!f) { free(buf); snprintf(err, (size_t)errlen, "failed to open output file %s", path); return -1; }
-  const uint32_t version = 1; unsigned char head[32]; int ok = 1, rc = 0;
-  memcpy(head, "10XK", 4); memcpy(head + 4, &version, 4); memcpy(head + 8, &info->hashNumber, 4); memcpy(head + 12, &info->minShare, 4);
-  memcpy(head + 16, &info->inRange, 8); memcpy(head + 24, &info->rows, 8);
-  ok = fwrite(head, 1, 32, f) == 32;
-  for (uint64_t first = 0; ok && !rc && first < n; first += cap) {
-    const uint64_t count = n - first < cap ? n - first : cap;
-    if (slab(user, buf, first, count)) { rc = -2; break; }          /* the callback's own error stands */
-    ok = fwrite(buf, 8, (size_t)count, f) == (size_t)count;
-  }
-  if (fclose(f)) ok = 0;
-  free(buf);
-  if (!rc && !ok) { snprintf(err, (size_t)errlen, "failed to write %s", path); rc = -1; }
-  return rc;
 }
 
 static int hc_slab_from_ctx(void *user, uint16_t *out, uint64_t first, uint64_t count) { return h10x_hash_copies_get((h10x_ctx *)user, out, first, count); }
@@ -1911,128 +1783,28 @@ int h10x_session_hashCopies(h10x_session *s, int minShare, const char *outPath, 
    The set is built on the device from the context's arrays and leaves it through h10x_mosh_set_write, the table in slices. ---- */
 int h10x_session_moshSet(h10x_session *s, int bits, int copy1min, int copy2min, int copyMmin, h10x_mosh **set, h10x_state_mosh_info *info) {
   *set = 0;
-  if (!s->ctx) return fail(s, "!! you must set hashDepthRange before writeMosh");       /* nothing loaded: no range either */
-  h10x_shard_info_t z; if (h10x_shard_info(s->ctx, &z)) return fail_ctx(s);
-  if (z.nranks > 1) return fail(s, "writeMosh does not run on a sharded session (--gpus > 1)");
+  if (whole_state(s, "writeMosh", NO_RANGE)) return -1;
   if (h10x_mosh_from_state(s->ctx, bits, copy1min, copy2min, copyMmin, set, info)) return fail_ctx(s);
   return 0;
-}
-
-void h10x_host_print_state_mosh(FILE *out, const h10x_state_mosh_info *z, int withCrib) {
-  fprintf(out, "  mosh set of %llu hashes in range, bits %u: copy0 %llu copy1 %llu copy2 %llu copyM %llu", (unsigned long long)z->kept, z->bits,
-          (unsigned long long)z->copy[0], (unsigned long long)z->copy[1], (unsigned long long)z->copy[2], (unsigned long long)z->copy[3]);
-  if (z->minShare) fprintf(out, ", by linkage at minShare %u: %llu to M, %llu to 0", z->minShare, (unsigned long long)z->toM, (unsigned long long)z->to0);
-  else fprintf(out, ", by depth only");
-  if (z->saturated) fprintf(out, ", %llu depths cut to 65535", (unsigned long long)z->saturated);
-  fputc('\n', out);
-  if (withCrib)
-    for (int t = 0; t < 5; ++t)
-      fprintf(out, "WRITE_MOSH  %s copy0 %llu copy1 %llu copy2 %llu copyM %llu\n", cribTypeName[t], (unsigned long long)z->crib[t][0],
-              (unsigned long long)z->crib[t][1], (unsigned long long)z->crib[t][2], (unsigned long long)z->crib[t][3]);
 }
 
 int h10x_session_writeMosh(h10x_session *s, int bits, int copy1min, int copy2min, int copyMmin, const char *outPath, FILE *out, h10x_state_mosh_info *infoOut) {
   h10x_mosh *set = 0; h10x_state_mosh_info info;
   if (h10x_session_moshSet(s, bits, copy1min, copy2min, copyMmin, &set, &info)) return -1;
   if (infoOut) *infoOut = info;
-  int rc = 0;
-  const size_t n = strlen(outPath);
-  char *part = (char *)malloc(n + 6);                                                   /* the file appears under its name when it is whole */
-  if (!part) { rc = fail(s, "out of host memory"); goto done; }
-  memcpy(part, outPath, n); memcpy(part + n, ".part", 6);
-  { FILE *t = fopen(part, "wb"); if (!t) { rc = fail(s, "failed to open output file %s", outPath); goto done; } fclose(t); }
-  if (h10x_mosh_set_write(set, part, s->err, (int)sizeof s->err)) { remove(part); rc = -1; goto done; }
-  if (rename(part, outPath)) { remove(part); rc = fail(s, "failed to write %s", outPath); goto done; }
-  if (out) {
+  OutFile o; int rc = h10x_out_probe(&o, outPath, s->err, (int)sizeof s->err);          /* the set writer fills o.tmp: the file appears under its name when it is whole */
+  if (!rc) rc = h10x_mosh_set_write(set, o.tmp, s->err, (int)sizeof s->err) || h10x_out_commit(&o) ? -1 : 0;
+  if (!rc && out) {
     uint32_t histDim = 0;
     h10x_host_print_state_mosh(out, &info, h10x_crib_sizes(s->ctx, &histDim, 0) == 0);
   }
-done:
-  free(part);
+  h10x_out_abort(&o);
   h10x_mosh_destroy(set);
   return rc;
 }
 
 /* ---- --seqBlocks <minShare> <seqfile> <out.sb>: per sequence of a file the blocks whose barcode lists hold its in-range hashes (h10x_seq_blocks_run).
-   The writer has three parts: the rows of each slab go to <out.sb>.part as they come; the per-sequence table, the offsets and the names are kept on the
-   host and written at the end, with the header; then the file takes its name. ---- */
-static int sb_grow(void **p, size_t *cap, size_t need, size_t elt) {
-  if (need <= *cap) return 0;
-  size_t n = *cap ? *cap : 64; while (n < need) n *= 2;
-  void *q = realloc(*p, n * elt); if (!q) return -1;
-  *p = q; *cap = n;
-  return 0;
-}
-
-int h10x_host_write_seq_blocks(const char *path, uint32_t nBlocks, uint32_t minShare, h10x_seq_blocks_slab_fn next, void *user, FILE *verbose,
-                               h10x_seq_blocks_totals *totals, char *err, int errlen) {
-  typedef struct { uint64_t len; uint32_t moshes, found, query, reserved; } Rec;
-  h10x_seq_blocks_totals t; memset(&t, 0, sizeof t);
-  Rec *table = 0; uint64_t *offsets = 0, *nameOff = 0; char *names = 0; uint32_t *pair = 0;
-  size_t capTable = 0, capOff = 0, capNameOff = 0, capNames = 0, capPair = 0; uint64_t nameBytes = 0;
-  int rc = 0; FILE *f = 0;
-  const size_t plen = strlen(path);
-  char *part = (char *)malloc(plen + 6);
-  if (!part) { snprintf(err, (size_t)errlen, "out of host memory"); return -1; }
-  memcpy(part, path, plen); memcpy(part + plen, ".part", 6);
-  if (!(f = fopen(part, "wb"))) { snprintf(err, (size_t)errlen, "failed to open output file %s", path); free(part); return -1; }
-  unsigned char head[40]; memset(head, 0, sizeof head);
-  if (fwrite(head, 1, sizeof head, f) != sizeof head) goto cannot_write;
-  if (sb_grow((void **)&offsets, &capOff, 1, 8) || sb_grow((void **)&nameOff, &capNameOff, 1, 8)) goto no_memory;
-  offsets[0] = 0; nameOff[0] = 0;
-  for (;;) {
-    h10x_seq_blocks_slab b; memset(&b, 0, sizeof b);
-    const int got = next(user, &b);
-    if (got < 0) { rc = -2; goto done; }                              /* the callback's own error stands */
-    if (!got) break;
-    const uint64_t rows = b.nSeq ? b.rowOff[b.nSeq] : 0;
-    if (sb_grow((void **)&table, &capTable, (size_t)(t.nSeq + b.nSeq), sizeof(Rec)) || sb_grow((void **)&offsets, &capOff, (size_t)(t.nSeq + b.nSeq + 1), 8) ||
-        sb_grow((void **)&nameOff, &capNameOff, (size_t)(t.nSeq + b.nSeq + 1), 8) || sb_grow((void **)&pair, &capPair, (size_t)rows, 8)) goto no_memory;
-    for (uint64_t i = 0; i < rows; ++i) { pair[2 * i] = b.block[i]; pair[2 * i + 1] = b.count[i]; }
-    if (rows && fwrite(pair, 8, (size_t)rows, f) != (size_t)rows) goto cannot_write;
-    for (uint32_t q = 0; q < b.nSeq; ++q) {
-      const uint64_t at = t.nSeq + q, len = b.seqStart[q + 1] - b.seqStart[q], r0 = b.rowOff[q], r1 = b.rowOff[q + 1];
-      const h10x_seq_figures *g = b.fig + q;
-      Rec rec = {len, g->moshes, g->found, g->query, 0};
-      table[at] = rec;
-      offsets[at + 1] = t.rows + r1;
-      const char *name = b.names + b.nameOff[q]; const size_t nl = strlen(name) + 1;
-      if (sb_grow((void **)&names, &capNames, (size_t)nameBytes + nl, 1)) goto no_memory;
-      memcpy(names + nameBytes, name, nl); nameBytes += nl; nameOff[at + 1] = nameBytes;
-      uint32_t best = 0, bestCount = 0;
-      for (uint64_t i = r0; i < r1; ++i) if (b.count[i] > bestCount) { bestCount = b.count[i]; best = b.block[i]; }
-      if (verbose) fprintf(verbose, "SEQ_BLOCKS  %s len %llu moshes %u found %u query %u rows %llu best %u count %u\n", name, (unsigned long long)len,
-                           g->moshes, g->found, g->query, (unsigned long long)(r1 - r0), best, bestCount);
-      t.bases += len; t.moshes += g->moshes; t.found += g->found; t.query += g->query;
-      if (r1 > r0) ++t.withRows;
-      if (bestCount > t.maxCount) t.maxCount = bestCount;
-    }
-    t.nSeq += b.nSeq; t.rows += rows;
-  }
-  {
-    const uint32_t version = 1;
-    if ((t.nSeq && fwrite(table, sizeof(Rec), (size_t)t.nSeq, f) != (size_t)t.nSeq) || fwrite(offsets, 8, (size_t)t.nSeq + 1, f) != (size_t)t.nSeq + 1 ||
-        fwrite(nameOff, 8, (size_t)t.nSeq + 1, f) != (size_t)t.nSeq + 1 || (nameBytes && fwrite(names, 1, (size_t)nameBytes, f) != (size_t)nameBytes)) goto cannot_write;
-    memcpy(head, "10XQ", 4); memcpy(head + 4, &version, 4); memcpy(head + 8, &nBlocks, 4); memcpy(head + 12, &minShare, 4);
-    memcpy(head + 16, &t.nSeq, 8); memcpy(head + 24, &t.rows, 8); memcpy(head + 32, &nameBytes, 8);
-    if (fseeko(f, 0, SEEK_SET) || fwrite(head, 1, sizeof head, f) != sizeof head) goto cannot_write;
-    const int closed = fclose(f); f = 0;
-    if (closed) goto cannot_write;
-    if (rename(part, path)) goto cannot_write;
-  }
-  if (totals) *totals = t;
-  goto done;
-no_memory:
-  snprintf(err, (size_t)errlen, "out of host memory for the table of %llu sequences", (unsigned long long)t.nSeq); rc = -1; goto done;
-cannot_write:
-  snprintf(err, (size_t)errlen, "failed to write %s", path); rc = -1;
-done:
-  if (f) fclose(f);
-  if (rc) remove(part);
-  free(part); free(table); free(offsets); free(nameOff); free(names); free(pair);
-  return rc;
-}
-
+   The slabs come from the sequence file through the device; h10x_host_write_seq_blocks (files_host.c) asks for one after the other and writes the file. ---- */
 typedef struct {
   h10x_session *s; h10x_seqreader *r; int minShare; uint64_t slab;
   h10x_seq_figures *fig; uint64_t *rowOff; uint32_t *block, *count; size_t capSeq, capOff, capRows;
@@ -2044,25 +1816,18 @@ static int sb_next_from_file(void *user, h10x_seq_blocks_slab *b) {
   const int got = h10x_seq_next_named(z->r, z->slab, &codes, &seqStart, &nSeq, &names, &nameOff);
   if (got < 0) return fail(s, "%s", h10x_seq_error(z->r));
   if (!got) return 0;
-  if (sb_grow((void **)&z->fig, &z->capSeq, (size_t)nSeq + 1, sizeof *z->fig)) return fail(s, "out of host memory for %u sequences", nSeq);
-  if (sb_grow((void **)&z->rowOff, &z->capOff, (size_t)nSeq + 1, 8)) return fail(s, "out of host memory for %u sequences", nSeq);
+  if (h10x_grow((void **)&z->fig, &z->capSeq, (size_t)nSeq + 1, sizeof *z->fig)) return fail(s, "out of host memory for %u sequences", nSeq);
+  if (h10x_grow((void **)&z->rowOff, &z->capOff, (size_t)nSeq + 1, 8)) return fail(s, "out of host memory for %u sequences", nSeq);
   h10x_list_share_info info;
   if (h10x_seq_blocks_run(s->ctx, z->minShare, codes, seqStart, nSeq, z->fig, &info)) return fail_ctx(s);
-  if (info.rows > z->capRows) {
-    free(z->block); free(z->count);
-    z->capRows = (size_t)(info.rows + info.rows / 2);
-    z->block = (uint32_t *)malloc(z->capRows * 4); z->count = (uint32_t *)malloc(z->capRows * 4);
-    if (!z->block || !z->count) { z->capRows = 0; return fail(s, "out of host memory for %llu rows", (unsigned long long)info.rows); }
-  }
+  if (rows_room(s, &z->block, &z->count, &z->capRows, info.rows)) return -1;
   if (h10x_list_share_get(s->ctx, z->rowOff, z->block, z->count, info.rows)) return fail_ctx(s);
   b->nSeq = nSeq; b->seqStart = seqStart; b->fig = z->fig; b->rowOff = z->rowOff; b->block = z->block; b->count = z->count; b->names = names; b->nameOff = nameOff;
   return 1;
 }
 
 int h10x_session_seqBlocks(h10x_session *s, int minShare, const char *seqPath, const char *outPath, FILE *out, int verbose) {
-  if (!s->ctx) return fail(s, "!! you must set hashDepthRange before seqBlocks");       /* nothing loaded: no range either */
-  h10x_shard_info_t sh; if (h10x_shard_info(s->ctx, &sh)) return fail_ctx(s);
-  if (sh.nranks > 1) return fail(s, "seqBlocks does not run on a sharded session (--gpus > 1)");
+  if (whole_state(s, "seqBlocks", NO_RANGE)) return -1;
   h10x_list_share_info info;
   if (h10x_seq_blocks_run(s->ctx, minShare, 0, 0, 0, 0, &info)) return fail_ctx(s);     /* the refusals, before any file is touched */
   char msg[512] = ""; int fatal = 0;
@@ -2082,81 +1847,14 @@ int h10x_session_seqBlocks(h10x_session *s, int minShare, const char *seqPath, c
 /* ---- --seqLinks <minShare> <minBlocks> <endLen> <maxEnds> <seqfile> <out.sl>: which sequence ends share molecules (h10x_row_links_*). The sequence file is
    read in slabs; the host cuts each sequence's two ends, a slab of ends runs through h10x_seq_blocks_run and its rows go from device memory to the
    accumulator (h10x_row_links_add_kept): the rows never reach the host, which keeps per sequence its length, the two row counts and the name. The links
-   come back in pieces and are written to <out.sl>.part, renamed when whole. ---- */
-int h10x_host_write_seq_links(const char *path, const h10x_seq_links_head *h, h10x_seq_links_piece_fn piece, void *user, uint64_t pieceLinks, FILE *verbose,
-                              h10x_seq_links_totals *totals, char *err, int errlen) {
-  h10x_seq_links_totals t; memset(&t, 0, sizeof t);
-  const uint64_t nEnds = 2 * h->nSeq, nameBytes = h->nSeq ? h->nameOff[h->nSeq] : 0;
-  if (!pieceLinks) pieceLinks = (uint64_t)1 << 20;
-  const uint64_t cap = h->links < pieceLinks ? h->links : pieceLinks;
-  uint32_t *other = 0, *shared = 0, *pair = 0; unsigned char *seen = 0; FILE *f = 0; int rc = 0;
-  const size_t plen = strlen(path);
-  char *part = (char *)malloc(plen + 6);
-  if (!part) { snprintf(err, (size_t)errlen, "out of host memory"); return -1; }
-  memcpy(part, path, plen); memcpy(part + plen, ".part", 6);
-  if (h->offsets[0] != 0 || h->offsets[nEnds] != h->links) { snprintf(err, (size_t)errlen, "seqLinks: the offsets do not end at the %llu links", (unsigned long long)h->links); free(part); return -1; }
-  if (!(f = fopen(part, "wb"))) { snprintf(err, (size_t)errlen, "failed to open output file %s", path); free(part); return -1; }
-  other = (uint32_t *)malloc((size_t)(cap + 1) * 4); shared = (uint32_t *)malloc((size_t)(cap + 1) * 4); pair = (uint32_t *)malloc((size_t)(cap + 1) * 8);
-  seen = (unsigned char *)calloc((size_t)h->nSeq + 1, 1);
-  if (!other || !shared || !pair || !seen) goto no_memory;
-  {
-    const uint32_t version = 1, zero = 0; unsigned char head[64];
-    memcpy(head, "10XL", 4); memcpy(head + 4, &version, 4); memcpy(head + 8, &h->nBlocks, 4); memcpy(head + 12, &h->minShare, 4); memcpy(head + 16, &h->minBlocks, 4);
-    memcpy(head + 20, &h->endLen, 4); memcpy(head + 24, &h->maxEnds, 4); memcpy(head + 28, &zero, 4);
-    memcpy(head + 32, &h->nSeq, 8); memcpy(head + 40, &h->links, 8); memcpy(head + 48, &h->skippedBlocks, 8); memcpy(head + 56, &nameBytes, 8);
-    if (fwrite(head, 1, sizeof head, f) != sizeof head) goto cannot_write;
-    if (h->nSeq && fwrite(h->table, sizeof(h10x_seq_links_rec), (size_t)h->nSeq, f) != (size_t)h->nSeq) goto cannot_write;
-    if (fwrite(h->offsets, 8, (size_t)nEnds + 1, f) != (size_t)nEnds + 1) goto cannot_write;
-  }
-  {
-    uint64_t e = 0;                                                    /* the end whose row holds the link at hand */
-    for (uint64_t first = 0; first < h->links; first += cap) {
-      const uint64_t m = h->links - first < cap ? h->links - first : cap;
-      if (piece(user, first, m, other, shared) < 0) { rc = -2; goto done; }   /* the callback's own error stands */
-      for (uint64_t i = 0; i < m; ++i) {
-        while (h->offsets[e + 1] <= first + i) ++e;
-        const uint64_t g = other[i];
-        if (g >= nEnds || g <= e) { snprintf(err, (size_t)errlen, "seqLinks: link %llu of end %llu names end %llu", (unsigned long long)(first + i), (unsigned long long)e, (unsigned long long)g); rc = -1; goto done; }
-        pair[2 * i] = other[i]; pair[2 * i + 1] = shared[i];
-        seen[e >> 1] = 1; seen[g >> 1] = 1;
-        if (shared[i] > t.maxShared) t.maxShared = shared[i];
-        if (verbose) fprintf(verbose, "SEQ_LINKS  %s %c %s %c shared %u\n", h->names + h->nameOff[e >> 1], e & 1 ? 'T' : 'H', h->names + h->nameOff[g >> 1],
-                             g & 1 ? 'T' : 'H', shared[i]);
-      }
-      if (fwrite(pair, 8, (size_t)m, f) != (size_t)m) goto cannot_write;
-      ++t.pieces;
-    }
-    for (uint64_t q = 0; q < h->nSeq; ++q) t.withLinks += seen[q];
-    t.nSeq = h->nSeq; t.links = h->links;
-    const uint64_t zero = 0;
-    if (fwrite(h->nSeq ? h->nameOff : &zero, 8, (size_t)h->nSeq + 1, f) != (size_t)h->nSeq + 1 || (nameBytes && fwrite(h->names, 1, (size_t)nameBytes, f) != (size_t)nameBytes))
-      goto cannot_write;
-    const int closed = fclose(f); f = 0;
-    if (closed) goto cannot_write;
-    if (rename(part, path)) goto cannot_write;
-  }
-  if (totals) *totals = t;
-  goto done;
-no_memory:
-  snprintf(err, (size_t)errlen, "out of host memory for the links of %llu sequences", (unsigned long long)h->nSeq); rc = -1; goto done;
-cannot_write:
-  snprintf(err, (size_t)errlen, "failed to write %s", path); rc = -1;
-done:
-  if (f) fclose(f);
-  if (rc) remove(part);
-  free(part); free(other); free(shared); free(pair); free(seen);
-  return rc;
-}
-
+   come back in pieces, which h10x_host_write_seq_links (files_host.c) asks for and writes. ---- */
 static int sl_piece_from_device(void *user, uint64_t first, uint64_t count, uint32_t *other, uint32_t *shared) {
   h10x_session *s = (h10x_session *)user;
   return h10x_row_links_get_range(s->ctx, first, count, other, shared) ? fail_ctx(s) : 0;
 }
 
 int h10x_session_seqLinks(h10x_session *s, int minShare, int minBlocks, int endLen, int maxEnds, const char *seqPath, const char *outPath, FILE *out, int verbose) {
-  if (!s->ctx) return fail(s, "!! you must set hashDepthRange before seqLinks");        /* nothing loaded: no range either */
-  h10x_shard_info_t sh; if (h10x_shard_info(s->ctx, &sh)) return fail_ctx(s);
-  if (sh.nranks > 1) return fail(s, "seqLinks does not run on a sharded session (--gpus > 1)");
+  if (whole_state(s, "seqLinks", NO_RANGE)) return -1;
   h10x_list_share_info li;
   if (h10x_seq_blocks_run(s->ctx, minShare < 1 ? 1 : minShare, 0, 0, 0, 0, &li)) {      /* the state's refusals, before any file is touched */
     if (strstr(h10x_last_error(s->ctx), "!! you must set hashDepthRange before")) return fail(s, "!! you must set hashDepthRange before seqLinks");
@@ -2170,16 +1868,12 @@ int h10x_session_seqLinks(h10x_session *s, int minShare, int minBlocks, int endL
   uint64_t slab = 0; { const int v = h10x_session_get(s, "seq_slab"); slab = v > 0 ? (uint64_t)v : 0; }
   h10x_seqreader *r = h10x_seq_open(seqPath, msg, (int)sizeof msg, &fatal);
   if (!r) return fail(s, "%s%sfailed to open sequence file %s", msg, msg[0] ? "\n" : "", seqPath);
-  h10x_seq_links_rec *table = 0; uint64_t *nameOff = 0, *endStart = 0, *rowOff = 0, *offsets = 0; char *names = 0; uint8_t *endCodes = 0;
-  size_t capTable = 0, capNameOff = 0, capNames = 0, capEndStart = 0, capRowOff = 0, capCodes = 0;
-  uint64_t nSeq = 0, nameBytes = 0;
-  char *part = (char *)malloc(strlen(outPath) + 6);                                       /* an output path that cannot be opened fails before the work, not after it */
-  if (!part) { rc = fail(s, "out of host memory"); goto done; }
-  strcpy(part, outPath); strcat(part, ".part");
-  { FILE *probe = fopen(part, "wb"); if (!probe) { rc = fail(s, "failed to open output file %s", outPath); free(part); part = 0; goto done; } fclose(probe); }
+  h10x_seq_links_rec *table = 0; uint64_t *endStart = 0, *rowOff = 0, *offsets = 0; uint8_t *endCodes = 0; NameTable names; memset(&names, 0, sizeof names);
+  size_t capTable = 0, capEndStart = 0, capRowOff = 0, capCodes = 0;
+  uint64_t nSeq = 0;
+  OutFile probe;                                                                          /* an output path that cannot be opened fails before the work, not after it */
+  if (h10x_out_probe(&probe, outPath, s->err, (int)sizeof s->err)) { rc = -1; goto done; }
   if (h10x_row_links_begin(s->ctx, li.nBlocks)) { rc = fail_ctx(s); goto done; }
-  if (sb_grow((void **)&nameOff, &capNameOff, 1, 8)) { rc = fail(s, "out of host memory"); goto done; }
-  nameOff[0] = 0;
   for (;;) {
     const uint8_t *codes; const uint64_t *seqStart, *nOff; const char *nm; uint32_t n = 0;
     const int got = h10x_seq_next_named(r, slab, &codes, &seqStart, &n, &nm, &nOff);
@@ -2188,9 +1882,9 @@ int h10x_session_seqLinks(h10x_session *s, int minShare, int minBlocks, int endL
     if (nSeq + n >= ((uint64_t)1 << 31)) { rc = fail(s, "seqLinks: 2^31 or more sequences"); goto done; }
     uint64_t bases = 0;
     for (uint32_t q = 0; q < n; ++q) { const uint64_t len = seqStart[q + 1] - seqStart[q]; bases += endLen && len > (uint64_t)endLen ? 2 * (uint64_t)endLen : endLen ? 2 * len : len; }
-    if (sb_grow((void **)&table, &capTable, (size_t)(nSeq + n), sizeof *table) || sb_grow((void **)&nameOff, &capNameOff, (size_t)(nSeq + n + 1), 8) ||
-        sb_grow((void **)&endStart, &capEndStart, 2 * (size_t)n + 1, 8) || sb_grow((void **)&rowOff, &capRowOff, 2 * (size_t)n + 1, 8) ||
-        sb_grow((void **)&endCodes, &capCodes, (size_t)bases + 1, 1)) { rc = fail(s, "out of host memory for %u sequences", n); goto done; }
+    if (h10x_grow((void **)&table, &capTable, (size_t)(nSeq + n), sizeof *table) ||
+        h10x_grow((void **)&endStart, &capEndStart, 2 * (size_t)n + 1, 8) || h10x_grow((void **)&rowOff, &capRowOff, 2 * (size_t)n + 1, 8) ||
+        h10x_grow((void **)&endCodes, &capCodes, (size_t)bases + 1, 1)) { rc = fail(s, "out of host memory for %u sequences", n); goto done; }
     uint64_t at = 0; endStart[0] = 0;
     for (uint32_t q = 0; q < n; ++q) {
       const uint64_t a = seqStart[q], len = seqStart[q + 1] - a, m = endLen && len > (uint64_t)endLen ? (uint64_t)endLen : len;
@@ -2204,9 +1898,7 @@ int h10x_session_seqLinks(h10x_session *s, int minShare, int minBlocks, int endL
     for (uint32_t q = 0; q < n; ++q) {
       h10x_seq_links_rec rec = {seqStart[q + 1] - seqStart[q], (uint32_t)(rowOff[2 * q + 1] - rowOff[2 * q]), (uint32_t)(rowOff[2 * q + 2] - rowOff[2 * q + 1])};
       table[nSeq + q] = rec;
-      const char *name = nm + nOff[q]; const size_t nl = strlen(name) + 1;
-      if (sb_grow((void **)&names, &capNames, (size_t)nameBytes + nl, 1)) { rc = fail(s, "out of host memory for the names"); goto done; }
-      memcpy(names + nameBytes, name, nl); nameBytes += nl; nameOff[nSeq + q + 1] = nameBytes;
+      if (h10x_names_add(&names, nm + nOff[q])) { rc = fail(s, "out of host memory for the names"); goto done; }
     }
     nSeq += n;
   }
@@ -2217,7 +1909,7 @@ int h10x_session_seqLinks(h10x_session *s, int minShare, int minBlocks, int endL
     if (!offsets) { rc = fail(s, "out of host memory for the offsets of %llu sequences", (unsigned long long)nSeq); goto done; }
     if (h10x_row_links_get(s->ctx, offsets, 0, 0, 0)) { rc = fail_ctx(s); goto done; }
     h10x_seq_links_head head = {li.nBlocks, (uint32_t)minShare, (uint32_t)minBlocks, (uint32_t)endLen, (uint32_t)maxEnds, nSeq, info.links, info.skippedBlocks,
-                                table, offsets, names, nameOff};
+                                table, offsets, names.bytes, names.off};
     h10x_seq_links_totals t;
     const int w = h10x_host_write_seq_links(outPath, &head, sl_piece_from_device, s, 0, verbose ? out : 0, &t, s->err, (int)sizeof s->err);
     if (w) { rc = -1; goto done; }                                                        /* (-2: the callback has set the session's text) */
@@ -2226,8 +1918,7 @@ int h10x_session_seqLinks(h10x_session *s, int minShare, int minBlocks, int endL
                      (unsigned long long)info.skippedBlocks, (unsigned long long)info.pairs, (unsigned long long)info.links, (unsigned long long)t.withLinks, t.maxShared);
   }
 done:
-  if (rc && part) remove(part);
-  free(part);
-  h10x_seq_close(r); free(table); free(nameOff); free(endStart); free(rowOff); free(offsets); free(names); free(endCodes);
+  h10x_out_abort(&probe);                                                                 /* (after the writer's commit nothing is left to remove) */
+  h10x_seq_close(r); free(table); free(endStart); free(rowOff); free(offsets); h10x_names_free(&names); free(endCodes);
   return rc;
 }

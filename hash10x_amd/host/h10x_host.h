@@ -5,6 +5,9 @@
  * clusterBlocks, array.c:144-170) that decides bytes of the .hash file. Each function is one
  * command of the reference's argv loop (hash10x.c:1200-1269); hash10x_main.c is that loop.
  * All compute goes through libh10x_hip.so — there is no CPU path here.
+ *
+ * The h10x_host_write_* functions and the whitelist functions write and read the project's own formats from host arrays and
+ * callbacks; they live in files_host.c, which needs no device library. Each writes <path>.part and renames it when it is whole.
  */
 #ifndef H10X_HOST_H
 #define H10X_HOST_H
@@ -91,7 +94,7 @@ int  h10x_session_fixFQBThresh(h10x_session *s, int thresh, const char *inPath, 
 /* the whitelist text without a device: the reader of fq2b-amd (blank-separated words of 16 characters; anything but ACGTacgt packs as A;
    codes in line order, to be freed with h10x_host_whitelist_free; -1 with "bad barcode line %d in %s: %s" or "failed to open 10x
    whitelist file %s" in err), the writer (one 16-letter line per code), and the line a barcode is looked up under — the LAST line
-   that holds it, 0 = absent — which is what the device's set keeps (h10x_whitelist_set) */
+   that holds it, 0 = absent — which is what the device's set keeps (h10x_whitelist_set). The writer writes <path>.part and renames it when whole. */
 int  h10x_host_whitelist_read(const char *path, uint32_t **codes, uint64_t *n, char *err, int errlen);
 void h10x_host_whitelist_free(uint32_t *codes);
 int  h10x_host_whitelist_write(const char *path, const uint32_t *codes, uint64_t n, char *err, int errlen);
@@ -104,7 +107,8 @@ int  h10x_host_whitelist_lines(const uint32_t *codes, uint64_t n, const uint32_t
    "10XS", u32 version 1, u32 nBlocks, u32 nMolecules, then nBlocks + nMolecules + 1 u64 starts: the records of post-split block m are [start[m],
    start[m + 1]). A file with fewer records than the state was read from fails; records beyond them (a -N cut) are left out, with one line to out
    saying how many. Both fail without a state, on a sharded session and after --clusterSplit. All values little-endian. out may be NULL.
-   h10x_host_write_molmap / _split_index write the two formats from arrays and never touch the GPU (-1 with the message in err). */
+   h10x_host_write_molmap / _split_index write the two formats from arrays and never touch the GPU (-1 with the message in err). The .mol file and the
+   .idx file are each written as <name>.part and renamed when whole: a failure leaves neither the file nor a .part. */
 int  h10x_session_moleculeMap(h10x_session *s, const char *outPath, FILE *out);
 int  h10x_session_splitFQB(h10x_session *s, const char *inPath, const char *outPath, FILE *out);
 int  h10x_host_write_molmap(const char *path, const uint32_t *mol, const uint32_t *slot, const h10x_molmap_info *info, char *err, int errlen);
@@ -115,8 +119,16 @@ int  h10x_host_write_split_index(const char *path, const uint64_t *start, uint32
    then rows pairs {u32 block, u32 count}: the row of block c is pairs [offsets[c], offsets[c + 1]), ascending in block. The blocks are walked in
    ranges of "share_graph_blocks" (h10x_session_set; 0 = 8192) and the file is written range by range, so neither the host nor the device holds all
    rows; the result does not depend on it. One line of counts to out (may be NULL). Fails with "!! ..." (the command then does nothing) before
-   --hashDepthRange, after --clusterSplit until a new range is set, and for minShare < 1; single-GPU sessions only. */
+   --hashDepthRange, after --clusterSplit until a new range is set, and for minShare < 1; single-GPU sessions only. The file is written as <out.sg>.part
+   and renamed when whole: in every failure no file is written and no .part is left behind.
+   h10x_host_write_share_graph is the writer alone (no device): it asks the callback for the block ranges [c0, c1) of rangeBlocks blocks (0 = 8192) in
+   ascending order; the callback yields the range's rows {blk, cnt} and part[0 .. c1 - c0], the row offsets of its blocks from 0 (0 = done, else failed).
+   It returns -2 when the callback failed (err untouched), -1 with err set for its own failures; *rows (may be NULL) = all rows. */
+typedef struct { const uint64_t *part; const uint32_t *blk, *cnt; uint64_t rows; } h10x_share_graph_range;
+typedef int (*h10x_share_graph_range_fn)(void *user, uint32_t c0, uint32_t c1, h10x_share_graph_range *range);
 int  h10x_session_shareGraph(h10x_session *s, int minShare, const char *outPath, FILE *out);
+int  h10x_host_write_share_graph(const char *path, uint32_t nBlocks, uint32_t minShare, uint32_t rangeBlocks, h10x_share_graph_range_fn range, void *user,
+                                 uint64_t *rows, char *err, int errlen);
 
 /* --shareComponents <minShare> <out.sc> (addition; include/h10x.h "the components of the share graph"): the connected components of the share graph at
    minShare over all blocks — which blocks (after --clusterSplit: molecules) hang together through shared good hashes. The file, little-endian: magic
@@ -126,7 +138,7 @@ int  h10x_session_shareGraph(h10x_session *s, int minShare, const char *outPath,
    be NULL). Fails with "!! ..." (the command then does nothing, no file is written) before --hashDepthRange, after --clusterSplit until a new range is
    set, and for minShare < 1; single-GPU sessions only.
    h10x_session_shareComponentsRun is the walk alone: the result stays in the context for h10x_share_components_get.
-   h10x_host_write_share_components writes the file from host arrays (no device). */
+   h10x_host_write_share_components writes the file from host arrays (no device), as <out.sc>.part, renamed when whole: a failure leaves neither. */
 int  h10x_session_shareComponents(h10x_session *s, int minShare, const char *outPath, FILE *out);
 int  h10x_session_shareComponentsRun(h10x_session *s, int minShare, h10x_share_components_info *info);
 int  h10x_host_write_share_components(const char *path, const h10x_share_components_info *info, const uint32_t *comp, const uint32_t *rootOf,
@@ -141,7 +153,8 @@ int  h10x_host_write_share_components(const char *path, const h10x_share_compone
    single-GPU sessions only.
    h10x_session_hashCopiesRun is the run alone: the result stays in the context for h10x_hash_copies_get.
    h10x_host_write_hash_copies writes the file from a callback that fills records [first, first + count) (no device); slabHashes = 0: 2^22. It returns
-   -2 when the callback failed (err untouched), -1 with err set for its own failures. */
+   -2 when the callback failed (err untouched), -1 with err set for its own failures. The file is written as <out.hc>.part and renamed when whole: in
+   every failure no file is written and no .part is left behind. */
 typedef int (*h10x_hash_copies_slab_fn)(void *user, uint16_t *out, uint64_t first, uint64_t count);
 int  h10x_session_hashCopies(h10x_session *s, int minShare, const char *outPath, FILE *out);
 int  h10x_session_hashCopiesRun(h10x_session *s, int minShare, h10x_hash_copies_info *info);

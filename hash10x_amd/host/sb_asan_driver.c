@@ -1,4 +1,4 @@
-/* The .sb writer of h10x_host.c (h10x_host_write_seq_blocks) behind a main of its own, for the AddressSanitizer + UBSan build
+/* The .sb writer of files_host.c (h10x_host_write_seq_blocks) behind a main of its own, for the AddressSanitizer + UBSan build
    (tests/test_seq_blocks_cpu.py): it needs no device.   sb_asan_driver <out.sb> <nSeq> <seqsPerSlab>
    Sequence q is called "s<q>", has q % 5 + 1 bases and q % 4 rows {block q + i + 1, count 2 q + i + 1}; its figures are moshes q % 11, found q % 7,
    query q % 3. The slabs hold seqsPerSlab sequences each (0: all in one). Then the

@@ -1,4 +1,4 @@
-/* The .sl writer of h10x_host.c (h10x_host_write_seq_links) behind a main of its own, for the AddressSanitizer + UBSan build
+/* The .sl writer of files_host.c (h10x_host_write_seq_links) behind a main of its own, for the AddressSanitizer + UBSan build
    (tests/test_seq_links_cpu.py): it needs no device.   sl_asan_driver <out.sl> <nSeq> <linksPerPiece>
    Sequence q is called "s<q>", has q % 5 + 1 bases, q % 4 head rows and q % 3 tail rows. End e has e % 3 links, to ends e + 2 + k (k < e % 3) where those
    exist, with shared = e + k + 1. The links come in pieces of linksPerPiece (0: the writer's default). Then the callback fails in its last piece, and a
