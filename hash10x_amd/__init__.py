@@ -52,6 +52,10 @@ class _MoshInfo(ctypes.Structure):
                 ("factor1", ctypes.c_uint64), ("factor2", ctypes.c_uint64), ("max", ctypes.c_uint32), ("size", ctypes.c_uint32)]
 
 
+class _MoshCounters(ctypes.Structure):
+    _fields_ = [("scan_retries", ctypes.c_uint64), ("reserved", ctypes.c_uint64 * 3)]
+
+
 class _SeqhashRec(ctypes.Structure):
     _fields_ = [("k", ctypes.c_int32), ("w", ctypes.c_int32), ("mask", ctypes.c_uint64), ("shift1", ctypes.c_int32), ("shift2", ctypes.c_int32),
                 ("factor1", ctypes.c_uint64), ("factor2", ctypes.c_uint64), ("patternRC", ctypes.c_uint64 * 4)]
@@ -267,6 +271,9 @@ def load_native():
     hip.h10x_mosh_error.restype = cs; hip.h10x_mosh_error.argtypes = [vp]
     hip.h10x_mosh_info.argtypes = [vp, ctypes.POINTER(_MoshInfo)]
     hip.h10x_mosh_set_option.argtypes = [vp, cs, ctypes.c_int64]
+    hip.h10x_mosh_counters.argtypes = [vp, ctypes.POINTER(_MoshCounters)]
+    hip.h10x_get_scan_retries.argtypes = [vp, ctypes.POINTER(ctypes.c_uint64)]
+    hip.h10x_readset_chunks.argtypes = [vp, ctypes.POINTER(ctypes.c_uint32)]
     hip.h10x_mosh_add.argtypes = [vp, vp, vp, cu32, ci, cu64, ctypes.POINTER(cu64)]
     hip.h10x_mosh_scan.argtypes = [vp, vp, vp, cu32, ci, cu64, vp, vp, vp, cu64, ctypes.POINTER(cu64)]
     hip.h10x_mosh_merge.argtypes = [vp, ci32, ci32, cu64, vp, vp, vp, cu32, ctypes.POINTER(ci)]
@@ -788,6 +795,10 @@ class Hash10x:
         out["cluster_main"] = [int(x) for x in c.cluster_main]
         out["cluster_class_counts"] = [int(x) for x in c.cluster_class_counts]
         out["cluster_phase_ticks"] = [int(x) for x in c.cluster_phase_ticks]
+        n = ctypes.c_uint64(0)
+        if self._ctx():
+            self._hip.h10x_get_scan_retries(self._ctx(), ctypes.byref(n))
+        out["scan_retries"] = n.value                           # seq_hashes / seq_blocks / seq_links batches scanned a second time: the mosh list overflowed its estimate
         return out
 
     def sizes(self):
@@ -1562,7 +1573,14 @@ class MoshSet:
 
     def set_option(self, name, value):
         if self._hip.h10x_mosh_set_option(self.h, name.encode(), int(value)):
-            raise Hash10xError("unknown mosh option %s" % name)
+            raise Hash10xError("unknown mosh option %s, or a value outside its range" % name)
+
+    def counters(self):
+        """dict: scan_retries = device batches of add / scan (and of a ReadSet's or RefMap's over this set) whose list overflowed its estimated
+        size and were scanned a second time"""
+        c = _MoshCounters()
+        self._hip.h10x_mosh_counters(self.h, ctypes.byref(c))
+        return {"scan_retries": int(c.scan_retries)}
 
     @staticmethod
     def _seqs(codes, seq_start):
@@ -1733,6 +1751,9 @@ class ReadSet:
     def info(self):
         i = _ReadsetInfo()
         self._chk(self._hip.h10x_readset_info(self.h, ctypes.byref(i)))
+        n = ctypes.c_uint32(0)
+        self._hip.h10x_readset_chunks(self.h, ctypes.byref(n))
+        i.chunks = n.value                                      # chunks of queries of the overlap table as built; 0 = no table yet (set options "overlap_chunk", "overlap_chunk_reads")
         return i
 
     def add(self, codes, seq_start):

@@ -295,6 +295,7 @@ struct Ctx {
   Timer timers[T_COUNT];
   XchgStat xs[X_COUNT];
   h10x_counters ctr{};
+  u64 scanRetries = 0;                                       // batches whose mosh / hit list overflowed its estimate and were scanned a second time (stage_g.hip, stage_h.hip)
 
   // Small device counters that must start at zero (class sizes, work-queue positions, maxima, sums) come from one 16 KB arena that a library command clears
   // with ONE memset on the context's stream when it opens its ZeroScope (below): a memset of a few bytes is a dispatch of some 5 us like any other, and a step
@@ -595,6 +596,7 @@ int stageG_load(Mosh **out, int B, int k, int w, u64 factor1, u64 factor2, const
 void stageG_destroy(Mosh *m);
 const char *stageG_error(const Mosh *m);
 int stageG_setOption(Mosh *m, const char *name, int64_t v);
+void stageG_counters(const Mosh *m, h10x_mosh_counters_t *out);
 int stageG_add(Mosh *m, const u8 *codes, const u64 *seqStart, u32 nSeq, int skipOdd, u64 seqBase, u64 *nHashes);
 int stageG_scan(Mosh *m, const u8 *codes, const u64 *seqStart, u32 nSeq, int skipOdd, u64 seqBase, u64 *hash, u32 *seq, u32 *pos, u64 cap, u64 *nOut);
 int stageG_merge(Mosh *m, int k2, int w2, u64 factor12, const u64 *value2, const u16 *depth2, const u8 *info2, u32 size2, int *merged);
@@ -616,6 +618,7 @@ int stageH_oom(Mosh *m);
 Mosh *stageH_set(ReadSet *rs);
 int stageH_add(ReadSet *rs, const u8 *codes, const u64 *seqStart, u32 nSeq);
 int stageH_info(ReadSet *rs, h10x_readset_info_t *out);
+int stageH_chunks(ReadSet *rs, u32 *out);
 int stageH_export(ReadSet *rs, const h10x_read_t **reads, const u64 **hitStart, const u32 **hit, const u16 **dx);
 int stageH_overlapCap(ReadSet *rs, u32 ix, u32 *cap);
 int stageH_overlaps(ReadSet *rs, u32 ix, h10x_overlap_t *out, u32 cap, u32 *nOut, int32_t counts[3]);

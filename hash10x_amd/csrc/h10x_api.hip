@@ -78,6 +78,7 @@ int h10x_mosh_info(const h10x_mosh *s, h10x_mosh_info_t *o) {
   return 0;
 }
 int h10x_mosh_set_option(h10x_mosh *s, const char *name, int64_t v) { return s && name ? stageG_setOption(M(s), name, v) : -1; }
+int h10x_mosh_counters(const h10x_mosh *s, h10x_mosh_counters_t *out) { if (!s || !out) return -1; stageG_counters(M(s), out); return 0; }
 int h10x_mosh_add(h10x_mosh *s, const uint8_t *codes, const uint64_t *seqStart, uint32_t nSeq, int skipOdd23, uint64_t seqBase, uint64_t *nHashes) {
   return s ? stageG_add(M(s), codes, (const u64 *)seqStart, nSeq, skipOdd23, seqBase, (u64 *)nHashes) : -1;
 }
@@ -126,6 +127,7 @@ int h10x_readset_add(h10x_readset *rs, const uint8_t *codes, const uint64_t *seq
   return rs ? rsGuard(stageH_set(RS(rs)), [&] { return stageH_add(RS(rs), codes, (const u64 *)seqStart, nSeq); }) : -1;
 }
 int h10x_readset_info(h10x_readset *rs, h10x_readset_info_t *out) { return rs && out ? stageH_info(RS(rs), out) : -1; }
+int h10x_readset_chunks(h10x_readset *rs, uint32_t *n) { return rs && n ? stageH_chunks(RS(rs), n) : -1; }
 int h10x_readset_export(h10x_readset *rs, const h10x_read_t **reads, const uint64_t **hitStart, const uint32_t **hit, const uint16_t **dx) {
   return rs ? rsGuard(stageH_set(RS(rs)), [&] { return stageH_export(RS(rs), reads, (const u64 **)hitStart, hit, dx); }) : -1;
 }
@@ -948,6 +950,7 @@ int h10x_export_ngood(h10x_ctx *h, uint32_t *nGood) {
 }
 
 int h10x_get_counters(h10x_ctx *h, h10x_counters *out) { if (!h || !out) return -1; *out = h->c.ctr; return 0; }
+int h10x_get_scan_retries(h10x_ctx *h, uint64_t *out) { if (!h || !out) return -1; *out = h->c.scanRetries; return 0; }
 
 // ---- sharded contexts: where the blocks are, and copy-out by slices (no gather) ----
 int h10x_shard_info(h10x_ctx *h, h10x_shard_info_t *out) {

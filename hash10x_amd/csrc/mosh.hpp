@@ -7,6 +7,8 @@ namespace h10x {
 constexpr int MOSH_RUN = 64;                                 // k-mer start positions per lane
 constexpr int MOSH_X_SKIP = 23;                              // moshutils.c:43: barcode + spacer of the first read of a 10x pair
 constexpr u64 MOSH_SLAB_DEFAULT = (u64)1 << 26;              // bases per batch
+constexpr u64 RS_CHUNK_ENTRIES_DEFAULT = (u64)1 << 26;       // expanded (x, y) entries per chunk of queries of a readset's overlap table (stage_h.hip)
+constexpr u32 RS_CHUNK_READS_MAX = 65536;                    // queries per chunk: a read's place in its chunk travels in 16 bits
 
 struct Mosh {
   Ctx c;                                                     // stream, error text, block cache scope; c.hashIndex = index[], c.hashValue = value[]
@@ -14,6 +16,7 @@ struct Mosh {
   u32 size = 0, max = 0;                                     // ms->size (capacity of the per-index arrays: max stays below it), ms->max
   DevBuf<u16> depth; DevBuf<u8> info; DevBuf<u32> acc;
   u64 slab = MOSH_SLAB_DEFAULT;
+  u64 overlapChunk = RS_CHUNK_ENTRIES_DEFAULT; u32 overlapChunkReads = RS_CHUNK_READS_MAX;   // options "overlap_chunk", "overlap_chunk_reads": read when a readset's table is built
 };
 
 static inline int moshEnter(Mosh *m) {

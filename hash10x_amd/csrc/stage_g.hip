@@ -317,8 +317,15 @@ int stageG_load(Mosh **out, int B, int k, int w, u64 factor1, u64 factor2, const
 
 int stageG_setOption(Mosh *m, const char *name, int64_t v) {
   if (!strcmp(name, "mosh_slab")) { m->slab = v > 0 ? (u64)v : MOSH_SLAB_DEFAULT; return 0; }
+  if (!strcmp(name, "overlap_chunk")) { m->overlapChunk = v > 0 ? (u64)v : RS_CHUNK_ENTRIES_DEFAULT; return 0; }
+  if (!strcmp(name, "overlap_chunk_reads")) {                // the 16-bit xl field of rs_order_kernel (stage_h.hip) holds a read's place in its chunk
+    if (v > (int64_t)RS_CHUNK_READS_MAX) return -1;
+    m->overlapChunkReads = v > 0 ? (u32)v : RS_CHUNK_READS_MAX;
+    return 0;
+  }
   return -1;
 }
+void stageG_counters(const Mosh *m, h10x_mosh_counters_t *out) { memset(out, 0, sizeof *out); out->scan_retries = m->c.scanRetries; }
 
 // new indices [first, first + D) have their value[]: the die of moshset.c:57, then the table
 int moshPlace(Mosh *m, u32 D) {
@@ -374,6 +381,7 @@ int moshScanWith(Ctx *c, int k, int w, u64 factor1, int B, u32 *acc, u32 accSize
     if (b.listed <= cap) return 0;
     if (attempt) break;
     cap = b.listed;                                          // the estimate was too small: once more with the exact size
+    ++c->scanRetries;
     if (add) H10X_HIP(c, hipMemsetAsync(acc, 0, (size_t)accSize * 4, st));   // (acc[] is all zero between batches)
   }
   return c->fail("mosh scan: the list overflowed twice");

@@ -26,7 +26,6 @@ namespace h10x {
 
 constexpr u32 RS_TOP = 0x80000000u, RS_MASK = 0x7fffffffu;
 constexpr u32 RS_MAX_HITS = 65534;                           // the reference's u16 map of x's hits (moshasm.c:293) holds j + 1
-constexpr u64 RS_CHUNK_ENTRIES = (u64)1 << 26;               // expanded (x, y) entries per chunk of queries
 enum { BAD_REPEAT = 1, BAD_ORDER10 = 2, BAD_ORDER1 = 4, BAD_NOMATCH = 8, BAD_LOWHIT = 16, BAD_LOWCOPY1 = 32 };
 
 struct RsPair {                                              // one candidate of a query, as classified on the device
@@ -345,6 +344,7 @@ static int rsAddBatch(ReadSet *rs, const u8 *codes, const u64 *seqStart, u32 nSe
       if (n <= cap) break;
       if (attempt) return c->fail("readset scan: the list overflowed twice");
       cap = n;                                               // the estimate was too small: once more with the exact size
+      ++c->scanRetries;
       H10X_HIP(c, hipMemsetAsync(m->acc.p, 0, (size_t)m->size * 4, st));                      // (acc[] is all zero between batches)
     }
     H10X_HIP(c, hipMemcpyAsync(nMiss.data(), dMiss.p, (size_t)nSeq * 4, hipMemcpyDeviceToHost, st));
@@ -495,10 +495,11 @@ static int rsTable(ReadSet *rs) {
     return c->fail("copy-1 mosh %llx has depth 65535: it has no inverse list", (unsigned long long)v);
   }
   const int yBits = bitsFor(R);
+  const u64 chunkEntries = m->overlapChunk; const u32 chunkReads = m->overlapChunkReads;      // (at most RS_CHUNK_READS_MAX: stageG_setOption)
   u64 pairBase = 0;
   for (u32 x0 = 0; x0 < R; ) {
     u32 x1 = x0 + 1;
-    while (x1 < R && x1 - x0 < 65536 && offR[x1 + 1] - offR[x0] <= RS_CHUNK_ENTRIES) ++x1;
+    while (x1 < R && x1 - x0 < chunkReads && offR[x1 + 1] - offR[x0] <= chunkEntries) ++x1;
     const u64 E64 = offR[x1] - offR[x0];
     if (E64 >= RS_TOP) return c->fail("read %u meets %llu inverse-list entries: 2^31 or more are not supported", x0, (unsigned long long)E64);
     const u32 E = (u32)E64;
@@ -695,6 +696,7 @@ int stageH_info(ReadSet *rs, h10x_readset_info_t *out) {
   out->nReads = (u32)rs->reads.size(); out->dim = rs->dim; out->totHit = rs->totHit;
   return 0;
 }
+int stageH_chunks(ReadSet *rs, u32 *out) { *out = rs->tabled ? (u32)rs->chunks.size() : 0; return 0; }
 int stageH_export(ReadSet *rs, const h10x_read_t **reads, const u64 **hitStart, const u32 **hit, const u16 **dx) {
   H10X_TRY(moshEnter(rs->m));
   H10X_TRY(rsIndex(rs));                                     // nCopy is invBuild's

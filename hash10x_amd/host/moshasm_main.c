@@ -3,8 +3,8 @@
  * stderr and followed by a resource line. Fatal conditions print "FATAL ERROR: <message>" and exit(-1) like die() (utils.c:18-29);
  * where the reference would read freed or null memory, that is what happens here too, with a plain message. The device is opened
  * by -m / -r, not before: usage, unknown commands and bad files behave the same on a machine without a GPU.
- * Additions: --device <n>, --slab <bases> (bases per device batch; results do not depend on it); the resource line also carries
- * wall-clock seconds.
+ * Additions: --device <n>, --slab <bases> (bases per device batch; results do not depend on it), --chunk <entries> (expanded entries
+ * per chunk of queries of the overlap table; results do not depend on it); the resource line also carries wall-clock seconds.
  */
 #define _GNU_SOURCE
 #include <stdio.h>
@@ -47,6 +47,7 @@ static void usage(void) {
   fprintf(stderr, "  -o  | --output <file>              where the text goes from here on; '-' is stdout\n");
   fprintf(stderr, "  --device <n>                       HIP device (default 0); before -m / -r\n");
   fprintf(stderr, "  --slab <bases>                     bases per device batch of -f (default 2^26); results do not depend on it\n");
+  fprintf(stderr, "  --chunk <entries>                  inverse-list entries per chunk of the overlap table (default 2^26); results do not depend on it\n");
   fprintf(stderr, "  -m  | --moshset <mosh file>        the set, with copy classes (moshutils-amd -s)\n");
   fprintf(stderr, "  -f  | --seqfile <sequence file>    build the readset: FASTA / FASTQ, gzipped or not; once per -m\n");
   fprintf(stderr, "  -w  | --write <stem>               writes <stem>.mosh and <stem>.readset\n");
@@ -61,7 +62,7 @@ static void usage(void) {
 }
 
 static int device = 0;
-static uint64_t slab = 0;
+static uint64_t slab = 0, chunk = 0;
 static h10x_mosh *ms = 0;
 static h10x_readset *rs = 0;
 
@@ -77,6 +78,7 @@ static void device_set(h10x_moshfile *m) {
   if (h10x_mosh_load(&ms, m->B, m->sh.k, m->sh.w, m->sh.factor1, m->sh.factor2, m->index, m->value, m->depth, m->info, m->size, device, err, (int)sizeof err)) die("%s", err);
   h10x_moshfile_free(m);
   if (slab) h10x_mosh_set_option(ms, "mosh_slab", (int64_t)slab);
+  if (chunk) h10x_mosh_set_option(ms, "overlap_chunk", (int64_t)chunk);
 }
 static void need_rs(const char *cmd) { if (!rs) die("%s needs a readset: give -f or -r first", cmd); }
 static uint32_t read_ix(const char *s) {
@@ -114,6 +116,12 @@ int main(int argc, char *argv[]) {
       slab = strtoull(argv[-1], &end, 10);
       if (*argv[-1] == 0 || *end || slab < 1 || slab > 0xFFFFFFFFull) die("bad slab %s: 1 to 4294967295 bases", argv[-1]);
       if (ms) h10x_mosh_set_option(ms, "mosh_slab", (int64_t)slab);
+    }
+    else if (ARGMATCH("--chunk", "--chunk", 2)) {            /* read when the table is built: before the first -o1 / -o2 / -b / -c of a readset */
+      char *end = 0;
+      chunk = strtoull(argv[-1], &end, 10);
+      if (*argv[-1] == 0 || *end || chunk < 1 || chunk > 0x7FFFFFFFull) die("bad chunk %s: 1 to 2147483647 entries", argv[-1]);
+      if (ms) h10x_mosh_set_option(ms, "overlap_chunk", (int64_t)chunk);
     }
     else if (ARGMATCH("-m", "--moshset", 2)) {
       h10x_moshfile m; parse_set(argv[-1], &m); device_set(&m);

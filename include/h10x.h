@@ -25,7 +25,8 @@ extern "C" {
 /* 2 (round 5): h10x_warm, h10x_alloc_stats, h10x_pinned_*, h10x_ingest_fqb_async / _wait, H10X_TABLE_CLUSTER_RAW, the exchange counters of
    h10x_counters; option "cluster_dbg_skip" gone.
    3: h10x_counters.shard_reply_path, options "shard_reply_sort" 2 .. 4 and "shard_owner_cut". Entry points added since (the census, share graph, components,
-   hash copies, mosh sets, readsets, reference maps, h10x_mosh_from_state, h10x_seq_hashes / h10x_list_share_* / h10x_seq_blocks_run, h10x_row_links_*) change no existing struct or table and leave the version alone.
+   hash copies, mosh sets, readsets, reference maps, h10x_mosh_from_state, h10x_seq_hashes / h10x_list_share_* / h10x_seq_blocks_run, h10x_row_links_*,
+   h10x_mosh_counters, h10x_get_scan_retries, h10x_readset_chunks) change no existing struct or table and leave the version alone.
    libh10x_host.so and the Python loader refuse a libh10x_hip.so of another version. */
 #define H10X_ABI_VERSION 3
 
@@ -529,9 +530,19 @@ int  h10x_mosh_load(h10x_mosh **set, int32_t B, int32_t k, int32_t w, uint64_t f
 void h10x_mosh_destroy(h10x_mosh *set);
 const char *h10x_mosh_error(const h10x_mosh *set);
 int  h10x_mosh_info(const h10x_mosh *set, h10x_mosh_info_t *out);
-/* "mosh_slab": bases per device batch of h10x_mosh_add / h10x_mosh_scan (0 = default 2^26; a longer sequence goes alone). Results
-   do not depend on it. Unknown name: -1. */
+/* "mosh_slab": bases per device batch of h10x_mosh_add / h10x_mosh_scan (0 = default 2^26; a longer sequence goes alone).
+   "overlap_chunk", "overlap_chunk_reads": the overlap table of a readset over this set (below) is built for chunks of queries; a chunk
+   ends before the read that would take its expanded entries past overlap_chunk (0 = default 2^26; a read with more goes alone) and
+   holds at most overlap_chunk_reads reads (0 = default and upper limit 65536: a read's place in its chunk travels in 16 bits; a larger
+   value is refused with -1). Both are read when the table is built, i.e. by the first call after h10x_readset_add / _load that needs
+   it; h10x_readset_chunks reports how many chunks it took. Results depend on none of the three. Unknown name: -1. */
 int  h10x_mosh_set_option(h10x_mosh *set, const char *name, int64_t value);
+/* scan_retries = the device batches, since the set was made, whose list of moshes (h10x_mosh_add, h10x_mosh_scan, h10x_refmap_add,
+   h10x_refmap_query) or of hits (h10x_readset_add) overflowed the size estimated for it, 2 * (k-mers / w) + 65536, and were scanned a
+   second time at the exact size: long runs of N or of one base, low-complexity reads. h10x_refmap_add scans every batch twice (find-or-add,
+   then the ordered list), so such a batch counts twice there. Results do not depend on it. */
+typedef struct { uint64_t scan_retries, reserved[3]; } h10x_mosh_counters_t;
+int  h10x_mosh_counters(const h10x_mosh *set, h10x_mosh_counters_t *out);
 /* addSequence over sequences (moshutils.c:19-30, 41-45): codes = one byte per base (0..3, N -> 0), sequence s =
    codes[seqStart[s] .. seqStart[s+1]). Every mosh occurrence is found or added in file order and its depth incremented.
    skipOdd23 != 0 is -x: the 1st, 3rd, ... sequence (counting seqBase sequences before this call) starts 23 bases in; one shorter
@@ -721,6 +732,10 @@ int  h10x_readset_load(h10x_readset **rs, h10x_mosh *set, const h10x_read_t *rea
 void h10x_readset_destroy(h10x_readset *rs);                                         /* readsetDestroy (moshasm.c:75-82) */
 const char *h10x_readset_error(const h10x_readset *rs);
 int  h10x_readset_info(h10x_readset *rs, h10x_readset_info_t *out);
+/* the number of chunks of queries the overlap table was built in (options "overlap_chunk", "overlap_chunk_reads" of the set); 0 while
+   the readset has no table (before the first overlaps / mark_bad / mark_contained call, and again after h10x_readset_add). A chunk
+   of reads that meet no inverse-list entry is not counted: it holds nothing. */
+int  h10x_readset_chunks(h10x_readset *rs, uint32_t *nChunks);
 /* what readsetWrite stores (moshasm.c:84-100), nCopy as invBuild leaves it: pointers into the object, valid until the next call that
    changes it; hitStart[i] .. hitStart[i + 1] are read i's entries of hit / dx */
 int  h10x_readset_export(h10x_readset *rs, const h10x_read_t **reads, const uint64_t **hitStart, const uint32_t **hit, const uint16_t **dx);
@@ -837,6 +852,9 @@ typedef struct {
                                       that failed or did not fit (option "shard_reply_sort") */
 } h10x_counters;
 int  h10x_get_counters(h10x_ctx *ctx, h10x_counters *out);
+/* the device batches of h10x_seq_hashes / h10x_seq_blocks_run, since the context was made, whose list of moshes overflowed its estimated size
+   and were scanned a second time at the exact size (h10x_mosh_counters_t.scan_retries for a context) */
+int  h10x_get_scan_retries(h10x_ctx *ctx, uint64_t *out);
 /* test / tuning knobs (none changes a result): "stage_a_max_slots" caps the LDS hash-set slots per barcode in stage A (0 =
    default) so that the global-memory fallback can be exercised on small inputs; "chunk_size" (above); "index_no_pack" 1 = index
    build with separate key / block arrays even where the packed one-word entries fit; "index_probed_table" 0 default = the wide look-up table takes the probed entry format

@@ -344,6 +344,29 @@ def make_record(barcode_word, read1_tail_codes, read2_codes):
     return rec
 
 
+def poly_a_set(path, fa=None):
+    """gen_fqb's 6000 pairs under 50 barcodes with every 10th record rewritten (its barcode kept), in thirds: a pair of A only; read 2 half A, half random;
+    read 1 random and read 2 A only. A^k hashes to 0 and 0 is a mosh for every w: the state holds hash VALUE 0, at some index >= 1, in nearly every barcode."""
+    recs = gen_fqb(path, 6000, 50, 50000, 0.004, 21, 3.0, 150, 3000, fa=fa)
+    rs = np.random.RandomState(600)
+    for j, i in enumerate(range(0, len(recs), 10)):
+        r1, r2 = np.zeros(135, np.uint32), np.zeros(151, np.uint32)
+        if j % 3 == 1:
+            r2[75:] = rs.randint(0, 4, 76)
+        elif j % 3 == 2:
+            r1[:] = rs.randint(0, 4, 135)
+        recs[i] = make_record(int(recs[i, 0]), r1, r2)
+    recs.tofile(path)
+    return recs
+
+
+def value0_depth(hf):
+    """(index, depth) of hash value 0 in a parsed .hash, (0, 0) if it is not there"""
+    ix = np.flatnonzero(hf.hash_value[1:hf.hash_number] == 0)
+    assert len(ix) <= 1
+    return (int(ix[0]) + 1, int(hf.hash_depth[ix[0] + 1])) if len(ix) else (0, 0)
+
+
 def build_pairs65k(path):
     """Input of the > 65535-read-pairs edge (ClusterHash.read is U16: hash10x.c:37,180): seeded records of gen_fqb
     regrouped so that the file holds, between ordinary barcodes, BIG = ~84 k distinct pairs under one barcode (more than 65535

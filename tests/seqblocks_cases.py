@@ -5,6 +5,7 @@ import os
 import numpy as np
 
 import orc
+from gap_cases import scan_cap
 
 K, W, R = 21, 31, 17                                           # the session's defaults: the hasher of every state in these tests
 SMALL_RANGE = (3, 14)
@@ -50,3 +51,30 @@ def sequences(recs, step=97, joined=((0, 45), (1, 30)), tail=600, seed=5):
     one = out[0][0]
     out += [(one[:0], 0), (one[:K - 1], 0), (one[:K], 0), (one[:K + W - 2], 0)]
     return out
+
+
+def state_bytes(h, d):
+    h.write_hash(os.path.join(d, "state.hash"))
+    with open(os.path.join(d, "state.hash"), "rb") as f:
+        return f.read()
+
+
+def gapped_state(d):
+    """(Hash10x, its model, contigs, left flank, right flank): the state of orc.poly_a_set (hash value 0 is in it and in range), and contigs cut from
+    haplotype A: two flanks of 20 kb around a run of 100 kb (tests/gap_cases.py) or of 30 bases of code 0 (N or A) or 3 (T), or around 100 kb of
+    random sequence (the control)"""
+    import mosh_model as mm
+    import seqblocks_model as sbm
+    recs = orc.poly_a_set(os.path.join(d, "x.fqb"), fa=os.path.join(d, "x"))
+    h = orc.hx().Hash10x(B=20)
+    h.read_fqb(recs)
+    h.depth_range(3, 60)
+    ix, depth = orc.value0_depth(orc.HashFile(state_bytes(h, d)))
+    assert ix >= 1 and 3 <= depth < 60
+    hap = mm.parse_seq_bytes(open(os.path.join(d, "x.A.fa"), "rb").read())[0][0]
+    left, right = hap[:20000], hap[25000:45000]
+    contig = lambda mid: np.concatenate([left, mid, right]).astype(np.uint8)          # noqa: E731
+    seqs = {"N": contig(np.zeros(100000, np.uint8)), "N30": contig(np.zeros(30, np.uint8)), "T": contig(np.full(100000, 3, np.uint8)),
+            "T30": contig(np.full(30, 3, np.uint8)), "control": contig(np.random.RandomState(3).randint(0, 4, 100000))}
+    assert scan_cap([len(seqs["N"])], K, W) == 74566 < 100000 - K
+    return h, sbm.SeqBlocksModel.from_state(h), seqs, left, right

@@ -270,6 +270,36 @@ def test_big_barcode_uses_medium_lds_class_and_wide_lists(workdir):
     assert hf.blocks["nSubCluster"].sum() > 0
 
 
+# ---- hash VALUE 0 in the state: read pairs of A (or N) only. tests/test_oracle_vs_reference.py pins the oracle to the reference binary on this set ----
+POLY_A = ["-ct", 2, "--readFQB", "x.fqb", "--hashDepthRange", 3, 60, "--cluster", 1, 0]
+
+
+def _value0_in_range(hf):
+    ix, depth = orc.value0_depth(hf)
+    assert ix >= 1 and 3 <= depth < 60, (ix, depth)          # an index of its own, inside --hashDepthRange 3 60
+    assert hf.blocks["nSubCluster"].sum() > 0
+
+
+@pytest.mark.parametrize("k,opts", [(21, {}), (21, {"stage_a_max_slots": 256}), (21, {"index_no_pack": 1}), (25, {}), (21, {"cluster_first_global": 4})],
+                         ids=["default", "fallback", "no_pack", "k25", "translated"])
+def test_hash_value_0_in_the_state(workdir, k, opts):
+    """the packed (hash, read) keys of stage a, the probe tables of the index build, the good lists and the clustering with value 0 present:
+    on the LDS and the global mosh path, with packed and separate index entries, at k = 25 and with first[] translated"""
+    orc.poly_a_set(workdir.file("x.fqb"))
+    _value0_in_range(_against_oracle(workdir, "x.fqb", POLY_A, k=k, **opts))
+
+
+def test_hash_value_0_sharded(workdir):
+    """the same set over three ranks: value 0 has an owner like any other hash"""
+    recs = orc.poly_a_set(workdir.file("x.fqb"))
+    run_commands(lambda k, w, r, B: orc.Oracle(k, w, r, B), ["-B", 20] + POLY_A + ["--writeHash", "orc.hash"], workdir.path)
+    exp = open(workdir.file("orc.hash"), "rb").read()
+    _run_sharded(recs, 3, 20, 3, 60, 2, workdir.file("hip.hash"))
+    got = open(workdir.file("hip.hash"), "rb").read()
+    assert got == exp, orc.describe_diff(got, exp)
+    _value0_in_range(orc.HashFile(got))
+
+
 def test_empty_and_single_barcode_inputs(workdir):
     np.zeros(0, np.uint32).tofile(workdir.file("empty.fqb"))
     _against_oracle(workdir, "empty.fqb", ["--readFQB", "empty.fqb"])

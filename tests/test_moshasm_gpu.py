@@ -14,6 +14,7 @@ import pytest
 
 import asm_model as am
 import mosh_model as mm
+from gap_cases import scan_cap
 import orc
 
 pytestmark = pytest.mark.gpu
@@ -28,11 +29,27 @@ def run(args, cwd, timeout=600):
     return subprocess.run([EXE] + [str(a) for a in args], cwd=cwd, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=timeout)
 
 
-def strip_slab(r):
-    """stdout / stderr lines of a run that began with --slab N, without that command's own lines"""
+def strip_slab(r, n=1):
+    """stdout / stderr lines of a run that began with n commands --slab N / --chunk N, without those commands' own lines"""
     out = mm.mask_lines(r.stdout)
-    out.remove("user")
-    return out, [ln for ln in mm.mask_lines(r.stderr) if not ln.startswith("COMMAND --slab")]
+    for _ in range(n):
+        out.remove("user")
+    return out, [ln for ln in mm.mask_lines(r.stderr) if not ln.startswith(("COMMAND --slab", "COMMAND --chunk"))]
+
+
+def expected_chunks(model, entries=1 << 26, reads=65536):
+    """the chunks of queries of the overlap table (include/h10x.h, h10x_mosh_set_option): a read's entries = the depths of its distinct copy-1
+    moshes; a chunk ends before the read that takes it past `entries` or `reads`; one without entries is not counted"""
+    ms = model.ms
+    E = [sum(ms.depth[y] for y in {h & ~am.TOPBIT for h in r.hit} if ms.info[y] & 3 == 1) for r in model.reads]
+    n, x0, R = 0, 0, len(E)
+    while x0 < R:
+        x1, tot = x0 + 1, E[x0]
+        while x1 < R and x1 - x0 < reads and tot + E[x1] <= entries:
+            tot += E[x1]; x1 += 1
+        n += tot > 0
+        x0 = x1
+    return n
 
 
 # ---- (a) every golden case through the program -----------------------------------------------------------------------
@@ -105,16 +122,14 @@ def fresh(tmp_path_factory):
     return d, out, err
 
 
-@pytest.mark.parametrize("slab", [0, 4000])
-def test_fresh_readset_program(fresh, slab, tmp_path):
-    """default slab: one batch; --slab 4000: one or a few reads per batch, so most reads are the first or the last of one"""
+def _fresh_program(fresh, pre, tmp_path):
     md, mout, merr = fresh
     d = str(tmp_path)
     for n in ("hap.mosh", "reads.fa"):
         os.link(os.path.join(md, n), os.path.join(d, n))
-    r = run((["--slab", slab] if slab else []) + CHAIN, d)
+    r = run(pre + CHAIN, d)
     assert r.returncode == 0, r.stderr.decode()
-    out, err = strip_slab(r) if slab else (mm.mask_lines(r.stdout), mm.mask_lines(r.stderr))
+    out, err = strip_slab(r, len(pre) // 2)
     assert err == mm.mask_lines(merr.encode())
     assert out == mm.mask_lines(mout.encode())
     for n in FILES:
@@ -122,21 +137,52 @@ def test_fresh_readset_program(fresh, slab, tmp_path):
         assert got == exp, n
 
 
+@pytest.mark.parametrize("slab", [0, 4000])
+def test_fresh_readset_program(fresh, slab, tmp_path):
+    """default slab: one batch; --slab 4000: one or a few reads per batch, so most reads are the first or the last of one"""
+    _fresh_program(fresh, ["--slab", slab] if slab else [], tmp_path)
+
+
+def test_fresh_readset_program_chunked(fresh, tmp_path):
+    """--chunk 5000: the overlap table of the 200 reads in many chunks of queries (counted in test_fresh_readset_python_chunked)"""
+    md = fresh[0]
+    model = am.ReadsetModel.from_bytes(mm.MoshModel.from_bytes(open(os.path.join(md, "rs.mosh"), "rb").read()), open(os.path.join(md, "rs.readset"), "rb").read())
+    assert expected_chunks(model, 5000) > 3
+    _fresh_program(fresh, ["--chunk", 5000], tmp_path)
+
+
 def test_fresh_readset_python(fresh, tmp_path):
+    _fresh_python(fresh, tmp_path, {})
+
+
+@pytest.mark.parametrize("opt,value", [("overlap_chunk_reads", 2), ("overlap_chunk_reads", 64), ("overlap_chunk", 5000)])
+def test_fresh_readset_python_chunked(fresh, opt, value, tmp_path):
+    """overlaps, mark_bad, mark_contained and write over a table in many chunks: every call reads rows of chunks whose first read is not 0"""
+    _fresh_python(fresh, tmp_path, {opt: value})
+
+
+def _fresh_python(fresh, tmp_path, opts):
     import hash10x_amd
     md = fresh[0]
     d = str(tmp_path)
     ms = hash10x_amd.MoshSet.read(os.path.join(md, "hap.mosh"))
+    for name, v in opts.items():
+        ms.set_option(name, v)
+    with pytest.raises(hash10x_amd.Hash10xError):
+        ms.set_option("overlap_chunk_reads", 65537)              # a read's place in its chunk has 16 bits
     rs = hash10x_amd.ReadSet(ms)
     assert rs.add_file(os.path.join(md, "reads.fa"), slab=7000) == ""
     rs.write(os.path.join(d, "rs"))
     model = am.ReadsetModel.from_bytes(mm.MoshModel.from_bytes(open(os.path.join(md, "rs.mosh"), "rb").read()), open(os.path.join(md, "rs.readset"), "rb").read())
+    assert rs.info().chunks == 0                                 # no table yet
+    want = expected_chunks(model, opts.get("overlap_chunk", 1 << 26), opts.get("overlap_chunk_reads", 65536))
     for ix in (0, 3, 40, 111):
         o, nrep, ng, nb = rs.overlaps(ix)
         lines = []
         exp = model.find_overlaps(ix, 1, lines.append)
         assert [(int(a["iy"]), int(a["nHit"]), int(a["offset"]), int(a["isPlus"]), int(a["isBad"])) for a in o] == [tuple(e) for e in exp]
         assert lines[0].endswith("nRepeatMosh %d\tnGood %4d\tnBad %4d\n" % (nrep, ng, nb))
+    assert rs.info().chunks == want and (want > 3 if opts else want == 1)
     rs.write(os.path.join(d, "rs2"))                             # the flags the four calls set
     assert open(os.path.join(d, "rs2.readset"), "rb").read() == model.to_bytes()
     mb = model.mark_bad()
@@ -158,6 +204,70 @@ def test_fresh_readset_python(fresh, tmp_path):
     for ext in (".mosh", ".readset"):
         assert open(os.path.join(d, "rc2" + ext), "rb").read() == open(os.path.join(d, "rc" + ext), "rb").read()
     back.close(); back.ms.close(); ms.close()
+
+
+# ---- the scan's second attempt of -f: a batch of reads with more hits than the estimate its list is sized by (rsAddBatch) ---------------
+RUNS = "-m hap.mosh -f reads.fa -S -w rs -o2 7 -b -c".split()
+RUN_READS, RUN_LEN = 150, 620
+
+
+def write_run_case(d, runs):
+    """hap.mosh: a 30 kb diploid genome with A^25 at three places of each haplotype, so that hash value 0 is in the set with class M (as a copy-1
+    mosh its depth of 65535 would rightly be fatal); reads.fa: 200 reads of 1 kb, the first RUN_READS of them with a run of A or of N in the middle
+    when runs is set. Returns the reads"""
+    rs = np.random.RandomState(582)
+    haps = [h[:4000] + "A" * 25 + h[4000:15000] + "A" * 25 + h[15000:26000] + "A" * 25 + h[26000:] for h in gen_genome(rs, 30000)]
+    reads = gen_reads(rs, haps, 200, 1000, 1001, chimeras=0)
+    if runs:
+        reads = [s[:190] + "AN"[i % 2] * RUN_LEN + s[190 + RUN_LEN:] if i < RUN_READS else s for i, s in enumerate(reads)]
+    code = {c: i for i, c in enumerate("ACGT")}
+    ms = mm.MoshModel(20, 19, 31, 17)
+    ms.add([np.array([code[c] for c in h], np.uint8) for h in haps])
+    ms.set_copy(1, 2, 3)
+    assert ms.info[ms.ix[0]] & 3 == 3
+    with open(os.path.join(d, "hap.mosh"), "wb") as f:
+        f.write(ms.to_bytes())
+    with open(os.path.join(d, "reads.fa"), "w") as f:
+        f.write("".join(">r%d\n%s\n" % (i + 1, s) for i, s in enumerate(reads)))
+    return reads
+
+
+@pytest.mark.parametrize("runs", [True, False], ids=["runs", "control"])
+def test_readset_of_low_complexity_reads(runs, tmp_path):
+    """150 of 200 reads hit mosh 0 some 600 times each: the batch lists more hits than 2 * (k-mers / w) + 65536 and is scanned again, with acc[] and
+    the per-read miss counts cleared in between. Text and files equal the model's; scan_retries rises by one per overflowing batch, by none without runs"""
+    import hash10x_amd
+    dm = os.path.join(str(tmp_path), "model"); os.makedirs(dm)
+    reads = write_run_case(dm, runs)
+    st, out, err = am.run_commands(RUNS, dm)
+    assert st == 0, err
+    model = am.ReadsetModel.from_bytes(mm.MoshModel.from_bytes(open(os.path.join(dm, "rs.mosh"), "rb").read()), open(os.path.join(dm, "rs.readset"), "rb").read())
+    hits = [len(r.hit) for r in model.reads[1:]]
+    cap_all, cap_160 = scan_cap([len(s) for s in reads], 19, 31), scan_cap([len(s) for s in reads[:160]], 19, 31)
+    assert max(hits) < 65534
+    if runs:
+        assert sum(hits) > cap_all and sum(hits[:160]) > cap_160 and sum(hits[160:]) < 10000 and model.ms.depth[model.ms.ix[0]] == 65535
+    else:
+        assert sum(hits) < 10000
+    for slab in (0, 160000):                                    # one batch; the first 160 reads (all with a run), then the other 40
+        d = os.path.join(str(tmp_path), "slab%d" % slab); os.makedirs(d)
+        for n in ("hap.mosh", "reads.fa"):
+            os.link(os.path.join(dm, n), os.path.join(d, n))
+        r = run((["--slab", slab] if slab else []) + RUNS, d)
+        assert r.returncode == 0, r.stderr.decode()
+        gout, gerr = strip_slab(r, 1 if slab else 0)
+        assert gerr == mm.mask_lines(err.encode())
+        assert gout == mm.mask_lines(out.encode())
+        for n in ("rs.mosh", "rs.readset"):
+            assert am.mask_file(n, open(os.path.join(d, n), "rb").read()) == am.mask_file(n, open(os.path.join(dm, n), "rb").read()), "%s (slab %d)" % (n, slab)
+        ms = hash10x_amd.MoshSet.read(os.path.join(dm, "hap.mosh"))
+        rs = hash10x_amd.ReadSet(ms)
+        assert rs.add_file(os.path.join(dm, "reads.fa"), slab=slab) == ""
+        assert ms.counters()["scan_retries"] == (1 if runs else 0), "slab %d" % slab
+        rs.write(os.path.join(d, "py"))
+        for ext in (".mosh", ".readset"):
+            assert open(os.path.join(d, "py" + ext), "rb").read() == open(os.path.join(d, "rs" + ext), "rb").read()
+        rs.close(); ms.close()
 
 
 # ---- (c) shapes where the kernels can go wrong, hand-built as files ---------------------------------------------------------
@@ -209,6 +319,17 @@ SHAPE_CMDS = "-r in -o2 1 -S -b -S -w b -c -S -w c -o2 2".split()
 
 @pytest.mark.parametrize("name", sorted(SHAPES))
 def test_shapes(name, tmp_path):
+    _shape(name, 0, tmp_path)
+
+
+@pytest.mark.parametrize("chunk", [1, 200])
+@pytest.mark.parametrize("name", sorted(SHAPES))
+def test_shapes_chunked(name, chunk, tmp_path):
+    """--chunk 1: every read that has entries is a chunk of its own, the others make none; --chunk 200: chunk ends inside `edges` and `long_list`"""
+    _shape(name, chunk, tmp_path)
+
+
+def _shape(name, chunk, tmp_path):
     n1, reads = SHAPES[name]
     dm, dp = os.path.join(str(tmp_path), "model"), os.path.join(str(tmp_path), "prog")
     for d in (dm, dp):
@@ -226,12 +347,79 @@ def test_shapes(name, tmp_path):
     if name == "cutoff":                                        # the fixture does what it is for: 3 shared hits is an overlap, 2 is not
         o2 = [ln for ln in out.splitlines() if ln.startswith("RR")][:len(reads)]
         assert [int(ln.split("nGood")[1].split()[0]) for ln in o2] == [0, 2, 1, 1, 2, 1, 0]
-    r = run(cmds, dp)
+    r = run((["--chunk", chunk] if chunk else []) + cmds, dp)
     assert r.returncode == 0, r.stderr.decode()
-    assert mm.mask_lines(r.stderr) == mm.mask_lines(err.encode())
-    assert mm.mask_lines(r.stdout) == mm.mask_lines(out.encode())
+    gout, gerr = strip_slab(r, 1 if chunk else 0)
+    assert gerr == mm.mask_lines(err.encode())
+    assert gout == mm.mask_lines(out.encode())
     for n in ("b.mosh", "b.readset", "c.mosh", "c.readset"):
         assert open(os.path.join(dp, n), "rb").read() == open(os.path.join(dm, n), "rb").read(), n
+    if chunk:                                                   # the knob does something: the same files through the class, where the chunks can be counted
+        import hash10x_amd
+        want = expected_chunks(hand_readset(hand_set(n1), reads), chunk)
+        assert (want > 1 or (chunk == 200 and name in ("cutoff", "twice"))) and (chunk != 1 or want == sum(1 for hits in [[]] + reads if any(i <= n1 for i, _, _ in hits)))
+        back = hash10x_amd.ReadSet.read(os.path.join(dp, "in"))
+        back.ms.set_option("overlap_chunk", chunk)
+        back.mark_bad(); back.mark_contained()
+        assert back.info().chunks == want
+        back.write(os.path.join(dp, "py"))
+        for ext in (".mosh", ".readset"):
+            assert open(os.path.join(dp, "py" + ext), "rb").read() == open(os.path.join(dm, "c" + ext), "rb").read()
+        back.close(); back.ms.close()
+
+
+# ---- a readset beyond one chunk with no knob: more than 65536 reads ---------------------------------------------------------
+BIG_R = 66000
+BIG_CMDS = "-r in -o1 65535 -o1 65536 -o1 65537 -o1 66000 -o3 65535 65536 -o2 4001 -b -c -w c".split()
+
+
+@pytest.fixture(scope="module")
+def big(tmp_path_factory):
+    """66 000 reads of 4 copy-1 hits: read r holds moshes r, r + 1, r + 2, r + 3 (wrapping to 1 after 66 000), so it shares 3 hits with r - 1 and with
+    r + 1 and 2 with r - 2 and r + 2: reads 65534 .. 65537 have candidates on both sides of the boundary between the chunks, and the last read has read
+    1 and read 65 999. Every fourth read runs backwards and every 500th has a hit out of order. The model's run: computed once"""
+    d = str(tmp_path_factory.mktemp("big_model"))
+    ms = hand_set(BIG_R)
+    reads = []
+    for r in range(1, BIG_R + 1):
+        ids = [(r - 1 + j) % BIG_R + 1 for j in range(4)]
+        if r % 500 == 0:
+            ids[1], ids[2] = ids[2], ids[1]
+        reads.append([(i, r % 4 != 0, 31 + r % 5) for i in (ids if r % 4 else ids[::-1])])
+    rs = hand_readset(ms, reads)
+    for ix in range(rs.dim, len(rs.reads)):                    # the reads array grows as -f grows it
+        if ix >= rs.dim:
+            rs.dim = am.grow_dim(rs.dim, ix)
+    assert expected_chunks(rs) == 2
+    with open(os.path.join(d, "in.mosh"), "wb") as f:
+        f.write(ms.to_bytes())
+    with open(os.path.join(d, "in.readset"), "wb") as f:
+        f.write(rs.to_bytes())
+    st, out, err = am.run_commands(BIG_CMDS, d)
+    assert st == 0, err
+    for ix in (65534, 65535, 65536, 65537, BIG_R):             # at least two candidates with 3 or more shared hits besides the read itself
+        assert sum(1 for e in rs.find_overlaps(ix, 0, lambda s: None) if e[1] >= 3 and e[0] != ix) >= 2
+    return d, out, err
+
+
+def test_readset_beyond_one_chunk(big, tmp_path):
+    import hash10x_amd
+    md, mout, merr = big
+    d = str(tmp_path)
+    for n in ("in.mosh", "in.readset"):
+        os.link(os.path.join(md, n), os.path.join(d, n))
+    r = run(BIG_CMDS, d)
+    assert r.returncode == 0, r.stderr.decode()
+    assert mm.mask_lines(r.stderr) == mm.mask_lines(merr.encode())
+    assert mm.mask_lines(r.stdout) == mm.mask_lines(mout.encode())
+    for n in ("c.mosh", "c.readset"):
+        assert open(os.path.join(d, n), "rb").read() == open(os.path.join(md, n), "rb").read(), n
+    back = hash10x_amd.ReadSet.read(os.path.join(d, "in"))
+    back.mark_bad(); back.mark_contained()
+    assert back.info().chunks == 2
+    back.write(os.path.join(d, "py"))
+    assert open(os.path.join(d, "py.readset"), "rb").read() == open(os.path.join(md, "c.readset"), "rb").read()
+    back.close(); back.ms.close()
 
 
 def test_hit_limit(tmp_path):

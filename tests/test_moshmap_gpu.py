@@ -15,6 +15,7 @@ import pytest
 
 import map_model as mp
 import mosh_model as mm
+from gap_cases import GAP, gap_seqs, scan_cap, to_codes, write_fa
 import orc
 
 pytestmark = pytest.mark.gpu
@@ -165,6 +166,78 @@ def test_fresh_reference_refmap(fresh):
         hash10x_amd.RefMap.from_arrays(ms2, *[got[k] for k in ("index", "offset", "id", "depth", "rev", "loc")], n_ids=2)
     ms2.close(); rm2.close()                                   # the wrong order: the map's handle is forgotten, not released through a freed set
     rm.close(); ms.close()
+
+
+# ---- the scan's second attempt (tests/gap_cases.py): a reference sequence and a query with a 100 kb run of N, A or T ---------------------
+GAPPED = "-B 20 -f ref.fa -w r -q q.fa".split()
+
+
+def gap_case(d, fill):
+    """ref.fa: the gapped sequence and 30 kb of random sequence; q.fa: a query that holds the run, three that span a flank (one reversed, one
+    ending in the run) and one from the second reference sequence"""
+    left, gapped, right = gap_seqs(fill)
+    B = np.array(list("ACGT"))
+    other = "".join(B[np.random.RandomState(7).randint(0, 4, 30000)])
+    refs = [gapped, other]
+    qs = [gapped[15000:FLANK_END(gapped) + 6000], left[2000:9000], right[3000:15000].translate(COMP)[::-1], gapped[18000:20600], other[100:8000]]
+    write_fa(os.path.join(d, "ref.fa"), refs, ["chrG", "chrO"]); write_fa(os.path.join(d, "q.fa"), qs, ["q%d" % i for i in range(len(qs))])
+    return refs, qs
+
+
+def FLANK_END(gapped):
+    return len(gapped) - 20000                                    # where the right flank starts
+
+
+@pytest.mark.parametrize("fill", ["N", "A", "T", None], ids=["N", "A", "T", "control"])
+def test_gapped_reference_and_query(fill, tmp_path):
+    """-f of a reference sequence and -q of a query that list more moshes than the estimate: text, .mosh and .ref equal the model's with and without
+    --slab 3000 (every sequence alone); through RefMap the set's scan_retries rises by two for the reference batch (-f scans a batch twice: find-or-add, which
+    counts found hashes in acc[], then the ordered list) and by one for the query batch"""
+    import hash10x_amd
+    dm = os.path.join(str(tmp_path), "model"); os.makedirs(dm)
+    refs, qs = gap_case(dm, fill)
+    st, out, err = mp.run_commands(GAPPED, dm)
+    assert st == 0, err
+    k, w = 19, 31
+    model = mm.MoshModel(20, k, w, 17)
+    listed = [len(model.moshes(to_codes(s))[0]) for s in (refs[0], qs[0])]
+    if fill:
+        assert listed[0] > scan_cap([len(s) for s in refs], k, w) and listed[1] > scan_cap([len(s) for s in qs], k, w) and min(listed) > GAP - k
+    else:
+        assert max(listed) < 6000
+    for slab in (0, 3000):
+        d = os.path.join(str(tmp_path), "slab%d" % slab); os.makedirs(d)
+        for n in ("ref.fa", "q.fa"):
+            os.link(os.path.join(dm, n), os.path.join(d, n))
+        r = run((["--slab", slab] if slab else []) + GAPPED, d)
+        assert r.returncode == 0, r.stderr.decode()
+        gout, gerr = mm.mask_lines(r.stdout), mm.mask_lines(r.stderr)
+        if slab:
+            gout.remove("user")
+            gerr = [ln for ln in gerr if not ln.startswith("COMMAND --slab")]
+        assert gerr == mm.mask_lines(err.encode())
+        assert gout == mm.mask_lines(out.encode())
+        for n in ("r.mosh", "r.ref"):
+            with open(os.path.join(d, n), "rb") as f, open(os.path.join(dm, n), "rb") as g:
+                assert mp.mask_file(n, f.read()) == mp.mask_file(n, g.read()), "%s (slab %d)" % (n, slab)
+        ms = hash10x_amd.MoshSet(B=20)
+        if slab:
+            ms.set_option("mosh_slab", slab)
+        rm = hash10x_amd.RefMap(ms)
+        rm.add(*mm.flatten([to_codes(s) for s in refs]))
+        assert ms.counters()["scan_retries"] == (2 if fill else 0)
+        rm.pack()
+        ref_model = mp.RefModel.from_bytes(mm.MoshModel.from_bytes(open(os.path.join(dm, "r.mosh"), "rb").read()), open(os.path.join(dm, "r.ref"), "rb").read())
+        got = rm.export()
+        for key, exp in (("index", ref_model.index), ("offset", ref_model.offset), ("id", ref_model.id), ("rev", ref_model.rev), ("loc", ref_model.loc)):
+            assert np.array_equal(got[key], np.array(exp, np.uint32)), key
+        res = rm.query(*mm.flatten([to_codes(s) for s in qs]))
+        assert ms.counters()["scan_retries"] == (3 if fill else 0)
+        qlines = [ln for ln in out.splitlines() if ln.startswith("Q\t")]
+        for q, s in enumerate(qs):
+            c = res["counts"][q]
+            assert qlines[q] == "Q\tq%d\t%d\t%d miss, %d copy1, %d copy2, %d multi, %s hit" % (q, len(s), c[0], c[1], c[2], c[3], mp.c_ratio(int(c[1] + c[2] + c[3]), int(c.sum())))
+        rm.close(); ms.close()
 
 
 # ---- (c) limits and misuse ---------------------------------------------------------------------------------------------------------------

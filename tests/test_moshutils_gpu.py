@@ -10,6 +10,7 @@ import numpy as np
 import pytest
 
 import mosh_model as mm
+from gap_cases import GAP, gap_seqs, scan_cap, to_codes, write_fa
 import orc
 
 pytestmark = pytest.mark.gpu
@@ -168,6 +169,96 @@ def test_chain_matches_model(seed, B, k, w, tmp_path):
     assert other.merge(os.path.join(d, "s2.mosh")) is False and other.max == 0
     for s in (ms, un, other):
         s.close()
+
+
+# ---- the scan's second attempt: a batch that lists more moshes than the estimate its list is sized by ----------------------
+# An assembly gap of N (code 0 = A) or a homopolymer run hashes to 0 at every position, and 0 is a mosh for every w: the batch lists
+# every k-mer of the run, more than 2 * (k-mers / w) + 65536, and the scan runs again at the exact size (moshScanWith, stage_g.hip).
+# slab 0: the three sequences of g.fa in one batch; 162000: the gapped one and the right flank together, as the issue's batch of two; 50000: the gapped one alone
+@pytest.mark.parametrize("fill", ["N", "A", "T", None], ids=["N", "A", "T", "control"])
+def test_add_second_attempt(fill, tmp_path):
+    """-a of a batch that overflows its list while it also holds hashes that are found (they count in acc[] during the first attempt):
+    .mosh and -H histogram equal the model's, value 0 is saturated, the flank moshes have depth 2 or 3 and not twice that; scan_retries
+    rises by one per overflowing batch and stays 0 on random sequence of the same lengths"""
+    import hash10x_amd
+    k, w = 19, 31
+    left, gapped, right = gap_seqs(fill)
+    three = [gapped, right, left[:5000]]
+    assert scan_cap([len(gapped)], k, w) == 74566 and len(gapped) - k + 1 == 139982           # the figures of the issue
+    dm = os.path.join(str(tmp_path), "model"); os.makedirs(dm)
+    write_fa(os.path.join(dm, "l.fa"), [left]); write_fa(os.path.join(dm, "g.fa"), three)
+    cmd = [str(x) for x in ["-c", 20, k, w, 17, "-a", "l.fa", "-a", "g.fa", "-w", "s.mosh", "-H", "s.his"]]
+    st, out, err = mm.run_commands(cmd, dm)
+    assert st == 0, err
+    model = mm.MoshModel.from_bytes(open(os.path.join(dm, "s.mosh"), "rb").read())
+    listed = len(model.moshes(to_codes(gapped))[0])
+    if fill:
+        assert listed > scan_cap([len(s) for s in three], k, w) > scan_cap([len(gapped)], k, w) and listed >= GAP - k + 1
+        assert model.depth[model.ix[0]] == 65535
+        flank = {int(h) for s in (left, right) for h in model.moshes(to_codes(s))[0]} - {0}   # (a k-mer across a junction occurs once)
+        assert len(flank) > 1000 and {model.depth[model.ix[h]] for h in flank} == {2, 3}
+    else:
+        assert listed < 6000 and 0 not in model.ix
+    exp_his = "\n".join(mm.mask_lines(open(os.path.join(dm, "s.his"), "rb").read())).encode()
+    for slab in (0, 162000, 50000):
+        d = os.path.join(str(tmp_path), "slab%d" % slab); os.makedirs(d)
+        for n in ("l.fa", "g.fa"):
+            os.link(os.path.join(dm, n), os.path.join(d, n))
+        r = run((["--slab", slab] if slab else []) + cmd, d)
+        assert r.returncode == 0, r.stderr.decode()
+        got = mm.mask_lines(r.stdout)
+        if slab:
+            got.remove("user")
+        assert got == mm.mask_lines(out.encode())
+        assert open(os.path.join(d, "s.mosh"), "rb").read() == open(os.path.join(dm, "s.mosh"), "rb").read(), "slab %d" % slab
+        assert "\n".join(mm.mask_lines(open(os.path.join(d, "s.his"), "rb").read())).encode() == exp_his
+        # the same batches through the class, where the counter can be read
+        ms = hash10x_amd.MoshSet(B=20, k=k, w=w, seed=17)
+        if slab:
+            ms.set_option("mosh_slab", slab)
+        ms.add(*mm.flatten([to_codes(left)]))
+        assert ms.counters()["scan_retries"] == 0
+        n = ms.add(*mm.flatten([to_codes(s) for s in three]))
+        assert ms.counters()["scan_retries"] == (1 if fill else 0), "slab %d" % slab
+        assert n == sum(len(model.moshes(to_codes(s))[0]) for s in three)
+        ms.write(os.path.join(d, "py.mosh"))
+        assert open(os.path.join(d, "py.mosh"), "rb").read() == open(os.path.join(dm, "s.mosh"), "rb").read(), "slab %d (class)" % slab
+        h, c = ms.hist()
+        assert h[:len(model.hist())].tolist() == model.hist().tolist() and int(h.sum()) == model.max
+        ms.close()
+
+
+@pytest.mark.parametrize("fill", ["N", "A", "T", None], ids=["N", "A", "T", "control"])
+def test_scan_second_attempt_matches_reference_iterator(fill, tmp_path):
+    """list mode: hashes, sequence numbers and positions in order, against the reference's own iterator (k 16, w 32, seed 1). Its test program reads N
+    through another table than moshutils' reader does (N is code 0 = A there: the golden cases), so it is given the run as A where the scan is given N"""
+    import hash10x_amd
+    ref = os.path.join(orc.REF_DIR, "seqhash_test")
+    if not os.path.exists(ref):
+        pytest.fail("oracle/_ref/seqhash_test is missing: build() makes it where the reference is present")
+    _, gapped, right = gap_seqs(fill)
+    path = os.path.join(str(tmp_path), "g.fa")
+    write_fa(path, [gapped.replace("N", "A"), right])
+    r = subprocess.run([ref], input=open(path, "rb").read(), stdout=subprocess.PIPE, check=True)
+    exp, s = [], -1
+    for line in r.stdout.decode().splitlines():
+        if line.startswith("read sequence"):
+            s += 1
+        elif line.startswith("\t"):
+            h, p, _ = line.split()
+            exp.append((int(h, 16), s, int(p)))
+    overflow = bool(fill)
+    assert (len(exp) > scan_cap([len(gapped), len(right)], 16, 32)) == overflow
+    codes, start = mm.flatten([to_codes(gapped), to_codes(right)])
+    for slab, retries in ((0, 1), (50000, 1)):                 # one batch of both; the gapped sequence alone
+        ms = hash10x_amd.MoshSet(B=20, k=16, w=32, seed=1)
+        if slab:
+            ms.set_option("mosh_slab", slab)
+        h, q, p = ms.scan(codes, start)
+        # (MoshSet.scan calls h10x_mosh_scan a second time with room for all when the first call reports more moshes than its arrays hold: two scans of the batch)
+        assert ms.counters()["scan_retries"] == (2 * retries if overflow else 0)
+        assert list(zip(h.tolist(), q.tolist(), p.tolist())) == exp
+        ms.close()
 
 
 # ---- -x with a first read shorter than 23 bases (the reference aborts on an assert) ----------------------------------------

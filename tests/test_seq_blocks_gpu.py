@@ -266,6 +266,46 @@ def test_sequences_on_generated_molecules(tmp_path):
     h.close()
 
 
+
+def test_gapped_contig(tmp_path):
+    """a contig with an assembly gap lists more moshes than the estimate its batch's list is sized by (moshScanWith with no accumulators): every batch that
+    holds it is scanned twice, and its hash list and row are those of the same contig with the gap cut down to 30 bases (the list is a set)"""
+    d = str(tmp_path)
+    h, m, seqs, left, right = cases.gapped_state(d)
+    assert h.counters()["scan_retries"] == 0
+    plain = [seqs["control"], seqs["N30"], right]
+    _check_sequences(h, m, plain, (1, 5), (0, 50000))
+    assert h.counters()["scan_retries"] == 0                                         # random sequence of the same length does not overflow
+    gapped = [seqs["N"], seqs["N30"], right, seqs["T"], seqs["T30"], left[:K - 1]]
+    exp = _check_sequences(h, m, gapped, (1, 5), (0, 50000, 300000))
+    # slab 0: one batch; 50000: the two gapped contigs alone; 300000: [N, N30, right], [T, T30, left]; 2 + 2 * 2 scans of sequences and of their reverse complements each
+    assert h.counters()["scan_retries"] == 6 * (1 + 2 + 2)
+    off, hsh, fig = h.seq_hashes(gapped)
+    rows = h.seq_blocks(gapped, 1)
+    for a, b in ((0, 1), (3, 4)):
+        assert hsh[int(off[a]):int(off[a + 1])].tolist() == hsh[int(off[b]):int(off[b + 1])].tolist() and int(off[a + 1] - off[a]) > 100
+        ra, rb = [(x[int(rows[0][i]):int(rows[0][i + 1])].tolist() for x in rows[1:3]) for i in (a, b)]
+        assert [list(x) for x in ra] == [list(x) for x in rb]
+        assert int(fig["moshes"][a]) - int(fig["moshes"][b]) == 100000 - 30 and int(fig["query"][a]) == int(fig["query"][b])
+    ix = orc.value0_depth(orc.HashFile(cases.state_bytes(h, d)))[0]
+    assert ix in hsh[int(off[0]):int(off[1])].tolist()                               # the gap's own hash is in the state and in range: it is in the list, once
+    # the command: SEQ_BLOCKS prints moshes larger by the gap
+    names = ["gapN", "shortN", "right", "gapT", "shortT", "tiny"]
+    with open(os.path.join(d, "c.fa"), "w") as f:
+        f.write("".join(">%s\n%s\n" % (n, "".join("ACGT"[c] for c in s) if "N" not in n else "".join("ACGT"[c] for c in s[:20000]) + "N" * (len(s) - 40000) +
+                                       "".join("ACGT"[c] for c in s[-20000:])) for n, s in zip(names, gapped)))
+    before = h.counters()["scan_retries"]
+    h.write_seq_blocks(1, os.path.join(d, "c.fa"), os.path.join(d, "c.sb"), out=os.path.join(d, "c.out"), verbose=True)
+    assert h.counters()["scan_retries"] == before + 1
+    lines = {ln[0]: [int(v) for v in ln[1:]] for ln in VERBOSE.findall(open(os.path.join(d, "c.out")).read())}
+    assert lines["gapN"][1] - lines["shortN"][1] == 100000 - 30 == lines["gapT"][1] - lines["shortT"][1]
+    assert lines["gapN"][2] - lines["shortN"][2] == 100000 - 30                      # value 0 is in the state: every mosh of the gap is found
+    assert lines["gapN"][3:] == lines["shortN"][3:] and lines["gapT"][3:] == lines["shortT"][3:] and lines["gapN"][3] > 100   # query, rows, best, count
+    info, roff, rblk, rcnt, table, rnames = _hx().read_seq_blocks(os.path.join(d, "c.sb"))
+    _same((roff, rblk, rcnt), exp[1][:3], "the .sb file")
+    h.close()
+
+
 # ------------------------------------------------------------------------------------ kept results
 def test_kept_results():
     recs = cases.small_records()

@@ -18,6 +18,7 @@ import seqlinks_model as slm
 pytestmark = pytest.mark.gpu
 
 TOP = 2 ** 31 - 1
+K, W = cases.K, cases.W
 _hx, _budget = orc.hx, orc.set_budget
 FIGURES = ("lists", "rowEntries", "blocksUsed", "skippedBlocks", "pairs", "links", "maxShared")
 
@@ -269,6 +270,24 @@ def test_sequences_on_small():
         h.seq_links(seqs[:2], 1, 0, 100)
     with pytest.raises(_hx().Hash10xError, match="!! seqLinks endLen -1 must be >= 0"):
         h.seq_links(seqs[:2], 1, 1, -1)
+    h.close()
+
+
+def test_gapped_contigs(tmp_path):
+    """the ends of contigs with an assembly gap (end_len 0: whole contigs; 70 000: each end holds half the gap) list more moshes than the estimate: the
+    batch is scanned twice and the links are the model's, which are those of the contigs with the gap cut down to 30 bases"""
+    d = str(tmp_path)
+    h, m, seqs, left, right = cases.gapped_state(d)
+    cases_ = [(1, 1, 0, 0), (1, 2, 70000, 0), (2, 1, 70000, 8)]
+    _check_sequences(h, m, [seqs["control"], seqs["N30"], right, left], cases_, (0,))
+    assert h.counters()["scan_retries"] == 0
+    gapped = [seqs["N"], seqs["T"], right, left]
+    got = _check_sequences(h, m, gapped, cases_, (0, 150000))
+    # end_len 0: one batch (slab 0), then each gapped contig alone (slab 150000). end_len 70000: one batch, then the two ends of a gapped contig together
+    # in a batch of their own, and the same for the reverse complements. (An end alone cannot overflow: its estimate is all of its k-mers.)
+    assert h.counters()["scan_retries"] == (1 + 2) + 2 * (1 + 2 + 2)
+    short = _check_sequences(h, m, [seqs["N30"], seqs["T30"], right, left], cases_[:1], (0,))
+    assert slm.as_dict(*got[cases_[0]]) == slm.as_dict(*short[cases_[0]]) and len(got[cases_[0]][1]) >= 5
     h.close()
 
 

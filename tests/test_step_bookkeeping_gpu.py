@@ -128,6 +128,29 @@ def test_block_without_any_mosh(sets, slots):
     h.close()
 
 
+@pytest.mark.parametrize("slots", [0, 256], ids=["lds", "fallback"])
+def test_block_of_poly_a_pairs_only(sets, slots):
+    """a barcode of three A-only read pairs right behind tiny.fqb's barcode without a mosh: its block has one distinct hash, VALUE 0, which is also what the
+    stand-in entry of the block without a mosh holds — the two blocks share one hash index >= 1 (the oracle says so; the bytes must agree)"""
+    recs = _tiny().reshape(-1, 30)
+    codes = np.unique(recs[:, 0])
+    assert int(codes[1]) + 1 < int(codes[2])                    # room for a new barcode right behind barcode 2
+    new = np.stack([orc.make_record(int(codes[1]) + 1, np.zeros(135, np.uint32), np.zeros(151, np.uint32))] * 3)
+    at = int(np.searchsorted(recs[:, 0], codes[1], side="right"))
+    recs = np.concatenate([recs[:at], new, recs[at:]]).reshape(-1)
+    h = _hip(stage_a_max_slots=slots)
+    h.read_fqb(recs)
+    b = h.export_blocks()
+    assert b["nHash"][2] == 1 and b["nHash"][3] == 1
+    o = orc.Oracle(21, 31, 17, 20)
+    o.read_fqb(recs)
+    ix = [int(o.clushash(c).copy()["hash"][0]) for c in (2, 3)]
+    assert ix[0] == ix[1] >= 1 and int(o.hash_value()[ix[0]]) == 0 and int(o.hash_depth()[0][ix[0]]) >= 2
+    o.close()
+    _same(_finish(h, sets["tmp"], "hip.hash", ranges=((1, 14),), ct=1), _oracle(recs, sets["tmp"], ranges=((1, 14),), ct=1))
+    h.close()
+
+
 def test_some_blocks_on_the_fallback_path(sets):
     """a 256-slot table holds 25 read pairs: the larger blocks take the global path (a fallback table, repaired counts), the others stay"""
     h = _hip(stage_a_max_slots=256)
