@@ -239,6 +239,9 @@ def load_native():
     hip.h10x_hash_copies_get_device.argtypes = [vp, vp, cu64, cu64]
     hip.h10x_hash_copies_tally.argtypes = [vp, vp]
     hip.h10x_crib_export.argtypes = [vp, vp, vp, vp, vp]
+    hip.h10x_crib_sizes.argtypes = [vp, ctypes.POINTER(ctypes.c_uint32), vp]
+    hip.h10x_crib_summary.argtypes = [vp, vp, vp, vp]
+    hip.h10x_crib_words.argtypes = [vp, cu64, cu64, vp]
     host.h10x_session_hashCopies.argtypes = [vp, ci, cs, vp]
     host.h10x_session_hashCopiesRun.argtypes = [vp, ci, vp]
     # the state as a mosh set (csrc/stage_o.hip)
@@ -678,6 +681,54 @@ class Hash10x:
             out.append((known.value, unknown.value))
         self._chk_ctx(self._hip.h10x_crib_finish(self._ctx()))
         return out
+
+    def crib_sequences(self, seqs_a, seqs_b):
+        """crib_genomes with the sequence starts of the caller: each haplotype as a list of sequences (text or codes 0..3, as seq_hashes takes them; a sequence
+        may be shorter than k, or empty). Returns [(known, unknown) moshes of genome 1, of genome 2]."""
+        out = []
+        for which, seqs in enumerate((seqs_a, seqs_b)):
+            codes, starts = self._flatten_seqs(seqs)
+            known, unknown = ctypes.c_uint64(0), ctypes.c_uint64(0)
+            self._chk_ctx(self._hip.h10x_crib_genome(self._seq_ctx("crib_sequences"), codes.ctypes.data, starts.ctypes.data, int(starts.size - 1), which, ctypes.byref(known), ctypes.byref(unknown)))
+            out.append((known.value, unknown.value))
+        self._chk_ctx(self._hip.h10x_crib_finish(self._ctx()))
+        return out
+
+    def crib_export(self):
+        """the crib as h10x_crib_export gives it: chr (int16), pos (uint16) and type (uint8) per hash index, the four depth histograms hist[0..3] = err, het, hom,
+        mul (uint32, one row each, as long as the deepest hash needs) and arrayMax[4] = one past the deepest hash of each class (0: none). Fails before a crib."""
+        dim, amax = ctypes.c_uint32(0), np.zeros(4, dtype=np.uint32)
+        self._chk_ctx(self._hip.h10x_crib_sizes(self._seq_ctx("crib_export"), ctypes.byref(dim), amax.ctypes.data))
+        n = self.sizes()["hashNumber"]
+        chrom, pos, typ = np.zeros(n, dtype=np.int16), np.zeros(n, dtype=np.uint16), np.zeros(n, dtype=np.uint8)
+        hist = np.zeros((4, dim.value), dtype=np.uint32)
+        self._chk_ctx(self._hip.h10x_crib_export(self._ctx(), chrom.ctypes.data, pos.ctypes.data, typ.ctypes.data, hist.ctypes.data))
+        return {"chr": chrom, "pos": pos, "type": typ, "hist": hist, "arrayMax": amax}
+
+    def cluster_report_raw(self, first, n):
+        """h10x_cluster_report over blocks [first, first + n) of THIS rank: (one record per block: nGood, nClusHash, nClusRead; one per sub-cluster, the blocks'
+        min(nSubCluster, 255) records one after the other: n, nRead, nt[5], nBad, chr, pMin, pMax, nOtherListed, other[10])."""
+        brep = np.zeros(max(int(n), 1), dtype=_BLOCK_REP)
+        crep = np.zeros(255 * int(n) + 1, dtype=_CLUSTER_REP)
+        ncl = ctypes.c_uint64(0)
+        self._chk_ctx(self._hip.h10x_cluster_report(self._seq_ctx("cluster_report_raw"), int(first), int(n), brep.ctypes.data, crep.ctypes.data, ctypes.c_uint64(crep.size), ctypes.byref(ncl)))
+        return brep[: int(n)], crep[: ncl.value]
+
+    def crib_summary_raw(self):
+        """h10x_crib_summary: (counts[12] = records per crib type in base blocks, in blocks --clusterSplit made, base blocks without block 0, split blocks;
+        seen_base, seen_cluster = per hash index whether a block of that kind holds it, as bool arrays)."""
+        n = self.sizes()["hashNumber"]
+        words = (n + 31) // 32
+        counts, seen = np.zeros(12, dtype=np.uint64), np.zeros((2, words), dtype=np.uint32)
+        self._chk_ctx(self._hip.h10x_crib_summary(self._seq_ctx("crib_summary_raw"), counts.ctypes.data, seen[0].ctypes.data, seen[1].ctypes.data))
+        bits = [((seen[i][np.arange(n) >> 5] >> (np.arange(n, dtype=np.uint32) & 31)) & 1).astype(bool) for i in range(2)]
+        return counts, bits[0], bits[1]
+
+    def crib_words(self, first, count):
+        """h10x_crib_words: records [first, first + count) of this rank's ClusterHash table as cribSummary's words (bit 31 split block, 28-30 crib type, 0-27 hash index)."""
+        out = np.zeros(max(int(count), 1), dtype=np.uint32)
+        self._chk_ctx(self._hip.h10x_crib_words(self._seq_ctx("crib_words"), int(first), int(count), out.ctypes.data))
+        return out[: int(count)]
 
     def cluster_report_figures(self, first_block=1, n_blocks=None, run=1 << 16):
         """codeClusterReport's figures (hash10x.c:870-952) reduced over blocks [first, first + n) of THIS rank without forming the text: the sums tests/orc.report_digest reads

@@ -25,25 +25,31 @@ REPLAY_SMALL, REPLAY_MID = 2040, 16376                       # cluster.hpp
 MERGE_SMALL_READS, MERGE_KEPT = 4096, 2048                   # stage_c.hip: read_merge_kernel's BIG form; records it keeps in registers
 
 
-def image(blocks, B=20):
+def image(blocks, B=20, values=None, table=None):
     """bytes of a version 2 .hash file (hash10x.c:244-267). blocks[i] = (records: CLUSHASH array, nRead, nSubCluster, pointToMin) of block
-    i + 1. Asserts what the reference relies on without checking: every read below nRead, at most 255 clusters in a file's block."""
+    i + 1. Asserts what the reference relies on without checking: every read below nRead, at most 255 clusters in a file's block.
+    values: hashValue[] (slot 0 unused) in place of 31 * index, and with it the number of hash indices; table: hashIndex[2^B] in place of
+    the empty one (tests/crib_cases.py: real hash values and the probe table that finds them)."""
     n_blocks = len(blocks) + 1
-    table = np.zeros(n_blocks, dtype=BLOCK)
+    block_table = np.zeros(n_blocks, dtype=BLOCK)
     for i, (rec, n_read, n_sub, ptm) in enumerate(blocks, start=1):
         assert rec.dtype == CLUSHASH and n_sub <= 255
         assert len(rec) == 0 or int(rec["read"].max()) < n_read, "block %d: a read beyond nRead (readMap[] is nRead long, hash10x.c:842)" % i
-        table[i] = (n_read, len(rec), n_sub, 0, 0, ptm)
+        block_table[i] = (n_read, len(rec), n_sub, 0, 0, ptm)
     hashes = np.concatenate([rec["hash"] for rec, _, _, _ in blocks]).astype(np.int64)
-    n_index = int(hashes.max()) + 1
+    n_index = int(hashes.max()) + 1 if values is None else len(values)
+    assert hashes.size == 0 or int(hashes.max()) < n_index
     depth = np.bincount(hashes, minlength=n_index).astype("<u4")
+    values = np.arange(n_index, dtype="<u8") * 31 if values is None else np.asarray(values, dtype="<u8")
+    table = bytes(4 << B) if table is None else np.asarray(table, dtype="<u4").tobytes()
+    assert len(table) == 4 << B
 
     def array_header(n, size):
         return np.array([(8918274, 0, 0, n, size, n, 0)], dtype="<i4,<i4,<u8,<i4,<i4,<i4,<i4").tobytes()
 
     u16, u32 = (lambda v: int(v).to_bytes(2, "little")), (lambda v: int(v).to_bytes(4, "little"))
-    head = b"10XH" + u32(2) + u16(8) + u16(32) + u32(B) + bytes(4 << B) + u32(n_index) + (np.arange(n_index, dtype="<u8") * 31).tobytes()
-    return b"".join([head, array_header(n_index, 4), depth.tobytes(), array_header(n_blocks, 32), table.tobytes()] + [rec.tobytes() for rec, _, _, _ in blocks])
+    head = b"10XH" + u32(2) + u16(8) + u16(32) + u32(B) + table + u32(n_index) + values.tobytes()
+    return b"".join([head, array_header(n_index, 4), depth.tobytes(), array_header(n_blocks, 32), block_table.tobytes()] + [rec.tobytes() for rec, _, _, _ in blocks])
 
 
 def plain_image(blocks, B=20):
