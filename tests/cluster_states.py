@@ -12,6 +12,12 @@ holds it (its owner), and rank i counts, per earlier owner, the companions it ho
 msMax and msTot, replays the serial labelling, the cut at the 256th cluster and the read merge in plain Python (`Subject.expect`), and a
 case's check compares that with the oracle's output before anything runs on the GPU: a changed builder cannot empty a case unnoticed.
 
+A list is ascending in barcode number and block numbers are barcode numbers, so where a companion lies in the file decides which entry of a
+rank's list it is. A companion lies behind every subject of the file unless it is made with front=True: then it lies directly in front of
+its subject, in the order made. `Subject.lay` writes a whole list entry by entry — own entry, counted entries and fillers at stated
+indices — and `Subject.lists` states, per rank, what the list loop is given and must find (`Rank`): the cases of tests/list_cases.py, a
+registry of its own (REGISTRIES), are built on the two. A case carries its own --hashDepthRange (Case.lo, Case.hi).
+
 TEST INFRASTRUCTURE — plain Python and numpy, never imported by hash10x_amd/."""
 import collections
 import functools
@@ -20,7 +26,7 @@ import numpy as np
 
 from orc import BLOCK, CLUSHASH
 
-LO, HI = 2, 100                                              # --hashDepthRange of every case: a hash is good when 2 .. 99 records hold it
+LO, HI = 2, 100                                              # --hashDepthRange of a case that states none: a hash is good when 2 .. 99 records hold it
 REPLAY_SMALL, REPLAY_MID = 2040, 16376                       # cluster.hpp
 MERGE_SMALL_READS, MERGE_KEPT = 4096, 2048                   # stage_c.hip: read_merge_kernel's BIG form; records it keeps in registers
 
@@ -62,6 +68,11 @@ def plain_image(blocks, B=20):
     return image(out, B)
 
 
+Rank = collections.namedtuple("Rank", "d own best mx tot q at codes")
+# one rank's list as the list loop sees it (Subject.lists): d entries, ascending in barcode number, the block's own among them at index `own`;
+# msBest (None: no counted entry), msMax and msTot of hash10x.c:801-806; q = minShareCount[clusterMin[label]] of an active rank (hash10x.c:821), else 0;
+# at = {owner: indices of its entries in the list} (an entry's chunk is index // 64); codes = the barcode number of every entry (after State.build)
+
 Expect = collections.namedtuple("Expect", "n raw abandoned stop labelled terms all_terms ptm nsub labels")
 # n good hashes; raw clusters of codeClusterFind (0 if abandoned); stop = the abandoning turn; labelled = good hashes with a label before the merge;
 # terms = [(rank, a, b)] of the pointToMin quotients a / b added up to the stop, all_terms = the same without the cut at 255 clusters;
@@ -75,6 +86,8 @@ class Subject:
     def __init__(self, n_read=None, n_sub=0, ptm=0.0, raw=None):
         self.read, self.label = [], []                       # per rank: read, label in the file (wiped by codeClusterFind)
         self.comps = []                                      # companion blocks: the ranks whose hashes each holds
+        self.comp_front = []                                 # per companion: it lies in front of the subject in the file (a lower barcode number), else behind every subject
+        self.comp_code = []                                  # per companion: its barcode number (State.build)
         self.owned = {}                                      # rank -> the companions made for it by own()
         self.front, self.back = [], []                       # extras: (read, label)
         self.n_read, self.n_sub, self.ptm = n_read, n_sub, ptm
@@ -93,8 +106,8 @@ class Subject:
         self.read.extend(range(first, first + k)); self.label.extend([label] * k)
         return range(first, first + k)
 
-    def comp(self, members):
-        self.comps.append(members if isinstance(members, range) else list(members))
+    def comp(self, members, front=False):
+        self.comps.append(members if isinstance(members, range) else list(members)); self.comp_front.append(front)
 
     def extra(self, read=0, label=0, front=False, k=1):
         (self.front if front else self.back).extend([(read, label)] * k)
@@ -129,11 +142,11 @@ class Subject:
             self.comp([i, i + 1])
         return r
 
-    def own(self, f, k):
+    def own(self, f, k, front=False):
         """k companions that rank f owns (held by f alone until a child() joins them)"""
         for _ in range(k):
             c = [f]
-            self.comps.append(c)
+            self.comps.append(c); self.comp_front.append(front)   # (the list itself: child() appends to it)
             self.owned.setdefault(f, []).append(c)
 
     def child(self, shares):
@@ -141,24 +154,62 @@ class Subject:
         i = self.rank()
         for f, a in shares.items():
             assert len(self.owned.get(f, [])) >= a, "rank %d owns fewer than %d companions" % (f, a)
-            for c in self.owned[f][:a]:
+            for c in (self.owned[f][:a] if a >= 0 else self.owned[f][a:]):   # (a < 0: the LAST -a of them)
                 c.append(i)
         return i
 
+    def fill(self, i, k, front=False):
+        """k fillers of rank i — companions that hold it alone and count for nobody — at this place of the file order"""
+        for _ in range(k):
+            self.comp([i], front)
+
+    def lay(self, i, d, own_at, counted):
+        """the whole list of rank i, entry by entry: d entries, the block's own at index own_at, counted[index] = the earlier rank that owns the entry
+        there (a companion of its own, held by the two), a filler everywhere else. Call once per rank, ranks in ascending order."""
+        assert 0 <= own_at < d and own_at not in counted and all(0 <= j < d and 1 <= f < i for j, f in counted.items())
+        for j in range(d):
+            if j != own_at:
+                self.comp([counted[j], i] if j in counted else [i], front=j < own_at)
+
     # ---- what the reference makes of it
-    def _level(self):
+    def _level(self, lo=LO, hi=HI):
         """fillers — companions that hold one rank alone: they count for nobody — until the depths are >= 2 and never fall along the ranks, so that the
         order of the ranks is the order written here (goodHashes are sorted by depth, ties keep their position: hash10x.c:758)"""
         n = len(self.read)
         d = np.ones(n, dtype=np.int64)
         for c in self.comps:
             d[np.asarray(c, dtype=np.int64)] += 1
-        need = np.maximum(np.maximum.accumulate(np.maximum(d, LO)) - d, 0)
+        need = np.maximum(np.maximum.accumulate(np.maximum(d, lo)) - d, 0)
         for i in np.flatnonzero(need):
-            for _ in range(int(need[i])):
-                self.comps.append([int(i)])
+            self.fill(int(i), int(need[i]))
         d += need
-        assert n == 0 or (d.min() >= LO and d.max() < HI and np.all(np.diff(d) >= 0))
+        assert n == 0 or (d.min() >= lo and d.max() < hi and np.all(np.diff(d) >= 0))
+
+    def lists(self, ct):
+        """per rank, what the list loop is given and what it must find (Rank above); after State.build, which adds the levelling fillers and numbers the companions"""
+        n = len(self.read)
+        assert len(self.comp_code) == len(self.comps) == len(self.comp_front), "State.build first"
+        order = sorted(range(len(self.comps)), key=lambda k: self.comp_code[k])
+        ent = [[] for _ in range(n)]                         # per rank: (barcode number, owner or None) ascending
+        for k in order:
+            a = [int(x) for x in self.comps[k]]
+            live = [x for x in a if x >= 1]
+            f = min(live) if live else None
+            for i in a:
+                ent[i].append((self.comp_code[k], f if f is not None and i > f else None))
+        q = {i: a for i, a, _ in self.replay(ct, cap=False)[4]}
+        out = []
+        for i in range(n):
+            e = sorted(ent[i] + [(self.code, None)])
+            assert [c for c, _ in e] == sorted({c for c, _ in e}), "rank %d: a companion twice" % i
+            at = collections.OrderedDict()
+            for j, (_, f) in enumerate(e):
+                if f is not None and i >= 1:
+                    at.setdefault(f, []).append(j)
+            mx = max((len(v) for v in at.values()), default=0)
+            best = min((f for f, v in at.items() if len(v) == mx), default=None)
+            out.append(Rank(len(e), [c for c, _ in e].index(self.code), best, mx, sum(len(v) for v in at.values()), q.get(i, 0), at, [c for c, _ in e]))
+        return out
 
     def replay(self, ct, cap=True):
         """codeClusterFind (hash10x.c:789-823) from the companions: labels per rank, raw clusters, abandoning turn, terms"""
@@ -258,16 +309,17 @@ class State:
     def subjects(self):
         return self.items
 
-    def build(self, crange=(1, 0)):
+    def build(self, crange=(1, 0), lo=LO, hi=HI):
         nxt = [1]                                            # hash indices from 1 on
 
         def fresh(k):
             a = np.arange(nxt[0], nxt[0] + k, dtype=np.int64); nxt[0] += k
             return a
-        blocks, companions = [], []
-        for code, s in enumerate(self.items, start=1):
-            s.code = code
-            s._level()
+        blocks, companions, behind = [], [], []
+        for s in self.items:
+            s._level(lo, hi)
+            s.code = len(blocks) + 1 + sum(s.comp_front)      # its companions in front of it come first
+            s.comp_code = [0] * len(s.comps)
             hf, hr, hb = fresh(len(s.front)), fresh(len(s.read)), fresh(len(s.back))
             rec = np.zeros(len(hf) + len(hr) + len(hb), dtype=CLUSHASH)
             rec["hash"] = np.concatenate([hf, hr, hb])
@@ -276,51 +328,65 @@ class State:
             rec["subCluster"] = [l for _, l in s.front] + list(s.label) + [l for _, l in s.back]
             n_read = s.n_read if s.n_read is not None else max(reads, default=0) + 1
             assert all(r < n_read for r in reads) and (n_read <= 65536 or max(reads, default=0) < 65536)
-            blocks.append((rec, n_read, s.n_sub, s.ptm))
-            for c in s.comps:
+            for k, c in enumerate(s.comps):
                 r2 = np.zeros(len(c), dtype=CLUSHASH)
                 r2["hash"] = hr[np.asarray(c, dtype=np.int64)]
-                companions.append((r2, 1, 0, 0.0))
-        n_codes = len(blocks) + len(companions) + 1
-        lo, hi = (crange[0] or 1), (crange[1] or n_codes)
+                if s.comp_front[k]:
+                    blocks.append((r2, 1, 0, 0.0)); s.comp_code[k] = len(blocks)
+                else:
+                    companions.append((r2, 1, 0, 0.0)); behind.append((s, k))
+            blocks.append((rec, n_read, s.n_sub, s.ptm))
+            assert len(blocks) == s.code
+        for j, (s, k) in enumerate(behind):
+            s.comp_code[k] = len(blocks) + 1 + j
+        n_codes = self.n_codes = len(blocks) + len(companions) + 1   # barcode numbers 1 .. n_codes - 1
+        c_lo, c_hi = (crange[0] or 1), (crange[1] or n_codes)
         for s in self.items:
-            s.in_range = lo <= s.code < hi
-        assert not companions or len(self.items) == 1 or hi == n_codes, "companions lie behind the subjects: cluster to the end of the file"
+            s.in_range = c_lo <= s.code < c_hi
+        assert not companions or len(self.items) == 1 or c_hi == n_codes, "companions lie behind the subjects: cluster to the end of the file"
         return image(blocks + companions)
 
 
-Case = collections.namedtuple("Case", "name make ct crange heavy")
+Case = collections.namedtuple("Case", "name make ct crange heavy lo hi")   # lo, hi: the case's --hashDepthRange
 CASES = collections.OrderedDict()
+REGISTRIES = [CASES]                                         # every registry of cases (tests/list_cases.py adds its own): names are unique over all of them
 
 
-def case(name, ct=1, crange=(1, 0), heavy=False):
+def case(name, ct=1, crange=(1, 0), heavy=False, lo=LO, hi=HI, registry=CASES):
     def deco(f):
-        assert name not in CASES
-        CASES[name] = Case(name, f, ct, crange, heavy)
+        assert not any(name in r for r in REGISTRIES)
+        registry[name] = Case(name, f, ct, crange, heavy, lo, hi)
         return f
     return deco
+
+
+def find(name):
+    for r in REGISTRIES:
+        if name in r:
+            return r[name]
+    raise KeyError("no case named %r in any registry" % (name,))
 
 
 @functools.lru_cache(maxsize=None)
 def built(name):
     """(the file's bytes, State, the case's own check) — made once per process"""
-    c = CASES[name]
+    c = find(name)
     st, where = c.make()
-    data = st.build(c.crange)
+    data = st.build(c.crange, c.lo, c.hi)
     return data, st, where
 
 
 def args(name, inp, out):
     """the command line of a case, for the reference binary and for tests/driver.run_commands"""
-    c = CASES[name]
-    return ["-B", 20, "-ct", c.ct, "--readHash", inp, "--hashDepthRange", LO, HI, "--cluster", c.crange[0], c.crange[1], "--writeHash", out]
+    c = find(name)
+    return ["-B", 20, "-ct", c.ct, "--readHash", inp, "--hashDepthRange", c.lo, c.hi, "--cluster", c.crange[0], c.crange[1], "--writeHash", out]
 
 
 def check(name, hf, n_good):
     """hf: orc.HashFile of the oracle's output, n_good: {code: good hashes} from the oracle. Every subject equals the builder's own replay — labels,
     cluster count, pointToMin bit for bit — and the case still sits where it is meant to (its own `where`)."""
     _, st, where = built(name)
-    ct = CASES[name].ct
+    ct = find(name).ct
     ex = []
     for s in st.subjects:
         e = s.expect(ct)

@@ -47,12 +47,12 @@ def oracle(tmp_path_factory):
 
 def _cluster(root, name, opts, mode, times=1):
     import hash10x_amd
-    c = cs.CASES[name]
+    c = cs.find(name)
     h = hash10x_amd.Hash10x(B=20)
     for k, v in opts.items():
         h.set_option(k, v)
     h.read_hash(os.path.join(root, name + ".in.hash"))
-    h.depth_range(cs.LO, cs.HI)
+    h.depth_range(c.lo, c.hi)
     outs = []
     for t in range(times):
         h.cluster(c.crange[0], c.crange[1], c.ct)
