@@ -152,6 +152,16 @@ struct SegMap {
 };
 struct ShardSegInfo { u32 rank, localStart, count, globalBase; u64 entries; };   // one segment of one rank (allgathered: shard.hip)
 
+// ---- a kept result of the row censuses (census_rows.hip): the rows (a, b) of unit q at [offsets[q], offsets[q + 1]), back to back on the device
+struct Ctx;
+struct KeptRows {
+  DevBuf<u32> a, b; DevBuf<u64> offsets;                    // offsets[lists + 1]
+  u64 rows = 0; u32 lists = 0; bool have = false;
+  void release() { have = false; rows = 0; lists = 0; a.release(); b.release(); offsets.release(); }
+  // offsets[lists + 1] and the first min(cap, rows) rows, to host (toDevice = 0) or device memory; any may be null. what = the refusal where nothing is kept
+  int get(Ctx *c, u64 *offsetsOut, u32 *aOut, u32 *bOut, u64 cap, int toDevice, const char *what);
+};
+
 // ---- the context ------------------------------------------------------------------------------------
 struct Ctx {
   h10x_params prm{};
@@ -261,8 +271,8 @@ struct Ctx {
   int64_t optFqbSlab = 0;     // records per device batch of the host forms of the census and the fix (0 = default 2^22); results do not depend on it
   int64_t optMolGlobal = 0;   // testing knob: 1 = the molecule map keeps first[] of every clustered block in its HBM scratch slice, also where it would fit LDS (stage_k.hip)
   // the share graph of the last h10x_share_graph_run (stage_l.hip), kept until the next run, a new depth range, --clusterSplit or a new state:
-  // rows (block, count) of blocks [sgCodeMin, sgCodeMax) back to back, sgOffsets[sgCodeMax - sgCodeMin + 1]
-  DevBuf<u32> sgBlock, sgCount; DevBuf<u64> sgOffsets; u64 sgRows = 0; u32 sgCodeMin = 0, sgCodeMax = 0; bool haveShareGraph = false;
+  // rows (block, count) of blocks [sgCodeMin, sgCodeMax), one list each
+  KeptRows sg; u32 sgCodeMin = 0, sgCodeMax = 0;
   // the components of the share graph (stage_m.hip). Between h10x_share_components_begin and _finish: scParent[scBlocks], the union-find forest the ranges' rows
   // are hooked into. After _finish, kept until the next begin, a new depth range, --clusterSplit or a new state: scComp / scRoot [scBlocks] and, per component
   // 0 .. scComps, its root, member count and record sum
@@ -273,14 +283,14 @@ struct Ctx {
   DevBuf<u32> hcOut; u32 hcHashes = 0; bool haveHashCopies = false; u64 hcTally[16] = {}; h10x_hash_copies_info hcInfo{};
   // from sequences to blocks (stage_p.hip). The query lists of the last h10x_seq_hashes / h10x_seq_blocks_run: sqHash = the distinct in-range hash indices of
   // sequence s at [sqOffsets[s], sqOffsets[s + 1]) (sqHostOff: the same offsets on the host). The rows of the last h10x_list_share_run / h10x_seq_blocks_run:
-  // (block, count) of list q at [sbOffsets[q], sbOffsets[q + 1]). Both kept until the next run, a new depth range, --clusterSplit or a new state
+  // sb = (block, count) of list q. Both kept until the next run, a new depth range, --clusterSplit or a new state
   DevBuf<u32> sqHash; DevBuf<u64> sqOffsets; std::vector<u64> sqHostOff; u64 sqEntries = 0; u32 sqSeqs = 0; bool haveSeqHashes = false;
-  DevBuf<u32> sbBlock, sbCount; DevBuf<u64> sbOffsets; u64 sbRows = 0; u32 sbLists = 0; bool haveSeqBlocks = false;
+  KeptRows sb;
   // row links (stage_q.hip). Between h10x_row_links_begin and the next begin: rqKeys = the rqEntries row entries of the rqLists lists added so far as keys
-  // block << 32 | list, in (list, block) order, every block below rqBlocks. After h10x_row_links_finish: the links (other list, shared blocks) of list e at
-  // [rlOffsets[e], rlOffsets[e + 1]). Both kept until the next begin, a new depth range, --clusterSplit or a new state
+  // block << 32 | list, in (list, block) order, every block below rqBlocks. After h10x_row_links_finish: rl = the links (other list, shared blocks)
+  // of list e. Both kept until the next begin, a new depth range, --clusterSplit or a new state
   DevBuf<u64> rqKeys; u64 rqEntries = 0, rqLists = 0; u32 rqBlocks = 0; bool rqOpen = false;
-  DevBuf<u32> rlOther, rlShared; DevBuf<u64> rlOffsets; u64 rlLinks = 0; u32 rlLists = 0; bool haveRowLinks = false;
+  KeptRows rl;
   int64_t optSeqSlab = 0;     // bases per device batch of the sequence layer (0 = the mosh sets' default, 2^26); results do not depend on it
   // the -r value prm.factor1 was drawn from (option "seqhash_seed"): a mosh set made from the state carries the hasher's second multiplier too (stage_o.hip)
   int32_t seed = 0; bool haveSeed = false;
@@ -457,6 +467,17 @@ struct XGuard {
 
 #define H10X_TRY(expr) do { int rc__ = (expr); if (rc__) return rc__; } while (0)
 
+inline int KeptRows::get(Ctx *c, u64 *offsetsOut, u32 *aOut, u32 *bOut, u64 cap, int toDevice, const char *what) {
+  if (!have) return c->fail("%s", what);
+  const hipMemcpyKind kind = toDevice ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
+  const size_t m = (size_t)(cap < rows ? cap : rows);
+  if (offsetsOut) H10X_HIP(c, hipMemcpyAsync(offsetsOut, offsets.p, ((size_t)lists + 1) * 8, kind, c->stream));
+  if (m && aOut) H10X_HIP(c, hipMemcpyAsync(aOut, a.p, m * 4, kind, c->stream));
+  if (m && bOut) H10X_HIP(c, hipMemcpyAsync(bOut, b.p, m * 4, kind, c->stream));
+  H10X_HIP(c, hipStreamSynchronize(c->stream));
+  return 0;
+}
+
 static inline unsigned divUp(u64 a, u64 b) { return (unsigned)((a + b - 1) / b); }
 template <typename T> static inline T hmin(T a, T b) { return a < b ? a : b; }
 template <typename T> static inline T hmax(T a, T b) { return a > b ? a : b; }
@@ -517,7 +538,7 @@ int stageF_neighbourHist(Ctx *c, const u32 *xs, u32 nq, const u64 *offsets, u32 
 int stageF_codeShare(Ctx *c, const u32 *codes, u32 nq, u64 *offsets, u32 *barcode, u32 *count, u32 *firstRank, u32 *firstHash, u64 cap);
 int stageF_codeExplore(Ctx *c, int code, int threshold, u32 *out /* 8: h10x_code_explore_rep */);
 int stageF_codeCrib(Ctx *c, const u32 *codes, u32 n, u32 *out);
-// the census family (stage_f / stage_l / stage_m / stage_n): what its drivers share
+// the census family (stage_f / stage_l / stage_m / stage_n / stage_p / stage_q): what its drivers share (the tail of the row censuses: census_rows.hpp)
 int ce_check(Ctx *c, const char *cmd, int64_t minShare = 1);   // the refusals: no state, a sharded context, no good lists, minShare < 1 (stage_f.hip)
 inline int keyBits(u64 v) { int b = 1; while (b < 64 && (v >> b)) ++b; return b; }   // bits that hold 0 .. v (at least one)
 // The batch cutter. Queries [0, nq) with size[q] records each over the index range [0, top), in order: as many whole queries to a batch as fit

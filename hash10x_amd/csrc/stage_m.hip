@@ -153,11 +153,11 @@ int stageM_add(Ctx *c, u32 codeMin, u32 codeMax) {
       stageM_release(c);
       return c->fail("shareComponents: blocks [%u, %u) still have rows across two components after %u hook rounds", g.codeMin, g.codeMax, SM_MAX_ROUNDS);
     }
-    sm_hook_kernel<<<(unsigned)hmin<u64>(divUp(g.rows, 256), 65536), 256, 0, st>>>(c->sgOffsets.p, c->sgBlock.p, g.rows, g.codeMin, nq, c->scParent.p, nB);
+    sm_hook_kernel<<<(unsigned)hmin<u64>(divUp(g.rows, 256), 65536), 256, 0, st>>>(c->sg.offsets.p, c->sg.a.p, g.rows, g.codeMin, nq, c->scParent.p, nB);
     H10X_HIP(c, hipGetLastError());
     ++z.hookRounds;
     H10X_HIP(c, hipMemsetAsync(open.p, 0, 4, st));
-    sm_check_kernel<<<grid, 256, 0, st>>>(c->sgOffsets.p, c->sgBlock.p, g.rows, g.codeMin, nq, c->scParent.p, nB, open.p);
+    sm_check_kernel<<<grid, 256, 0, st>>>(c->sg.offsets.p, c->sg.a.p, g.rows, g.codeMin, nq, c->scParent.p, nB, open.p);
     H10X_HIP(c, hipGetLastError());
     u32 left = 0;
     H10X_TRY(c->readback(&left, open.p, 4)); H10X_TRY(c->syncReadbacks());

@@ -203,7 +203,7 @@ int stageN_run(Ctx *c, int64_t minShare, h10x_hash_copies_info *info) {
     const u32 cap = hmax<u32>((deepest + WAVE - 1) / WAVE * WAVE, WAVE);          // LDS words per array and wave: from the state's deepest list, not from the limit
     const u32 wpw = (u32)hmin<size_t>(4, HC_LDS_BYTES / ((size_t)cap * 8));       // cap <= 4096: at least two waves
     const unsigned grid = (unsigned)hmin<u64>(divUp(nx, wpw), 65536);
-    hc_groups_kernel<<<grid, wpw * WAVE, (size_t)wpw * cap * 8, st>>>(xs.p, nx, c->hashDepth.p, c->rowStart.p, c->rows.p, c->sgOffsets.p, c->sgBlock.p, c->nBlocks, cap,
+    hc_groups_kernel<<<grid, wpw * WAVE, (size_t)wpw * cap * 8, st>>>(xs.p, nx, c->hashDepth.p, c->rowStart.p, c->rows.p, c->sg.offsets.p, c->sg.a.p, c->nBlocks, cap,
                                                                        (uint2 *)c->hcOut.p, small.p + 1);
     H10X_HIP(c, hipGetLastError());
     hc_tally_kernel<<<(unsigned)hmin<u64>(divUp(nx, 256), HC_GRID), 256, 0, st>>>(xs.p, nx, (const uint2 *)c->hcOut.p, c->haveCrib ? c->cribType.p : nullptr, c->hashDepth.p,

@@ -16,27 +16,14 @@
 //   units    one lane per (list, hash) unit: the entries of that barcode list in the window; their exclusive sum is every unit's place;
 //   gather   one wave per unit: key = (list - first of batch) << keyBits(nBlocks) | d. Nothing is left out (no own block here), so a lane's place is
 //            the unit's place + its position in the list and there is no ballot. 32-bit keys where slot and block fit, else 64-bit;
-//   sort     prim_sort_keys_u32 / _u64 on the bits in use;
-//   runs     a run of equal keys is one (list, d) with count = its length; only runs of length >= T are flagged;
-//   rows     a scan of the flags places (d, count) behind the rows of the batches before; rows per list by two searches in the slot column.
+//   tail     census_rows.hip: the keys sorted, a run of equal keys is one (list, d) with count = its length, the runs of length >= T placed by a scan
+//            as rows (d, count) behind those of the batches before, the rows per list summed to offsets[].
 // Batches are cut by list entries against "neighbour_budget"; a list above it runs alone in windows of block index (whole runs each: the lists ascend).
-// The run, emit and row-count kernels are this file's own copies of stage_l.hip's: sharing them through a header would have changed how that file is laid
-// out, and its code object is required to stay as it is.
-#include "common.hpp"
-#include "prim.hpp"
+#include "census_rows.hpp"
 #include "mosh.hpp"
 #include "wave.hpp"
 
 namespace h10x {
-
-static constexpr u64 SP_DEFAULT_BUDGET = 1ull << 26;       // list entries per batch (stage_l.hip's SG_DEFAULT_BUDGET)
-static constexpr unsigned SP_EMIT_GRID = 2048;
-
-// the first index in [l, r) with keys[index] >= v
-__device__ __forceinline__ u64 sp_lower64(const u64 *__restrict__ keys, u64 l, u64 r, u64 v) {
-  while (l < r) { const u64 m = (l + r) >> 1; if (keys[m] < v) l = m + 1; else r = m; }
-  return l;
-}
 
 // ------------------------------------------------------------------------------------------------ layer 1
 // occurrence i of the slab -> key[i]. seqRel[0 .. ns] = the slab's sequence starts (seqRel[0] = 0), ord[i] = the ordinal of the k-mer in the slab
@@ -80,8 +67,8 @@ __global__ __launch_bounds__(256) void sp_figures_kernel(const u64 *__restrict__
   const u32 s = (u32)(((u64)blockIdx.x * blockDim.x + threadIdx.x) / WAVE);
   if (s >= ns) return;                                        // whole waves leave: the fold below sees all 64 lanes
   const u64 k0 = (u64)s << hb;
-  const u64 a = sp_lower64(key, 0, n, k0), z = sp_lower64(key, a, n, k0 | 1), o = sp_lower64(key, z, n, k0 | (u64)U1);
-  const u64 e = sp_lower64(key, o, n, ((u64)s + 1) << hb);
+  const u64 a = lower_bound(key, (u64)0, n, k0), z = lower_bound(key, a, n, k0 | 1), o = lower_bound(key, z, n, k0 | (u64)U1);
+  const u64 e = lower_bound(key, o, n, ((u64)s + 1) << hb);
   const u32 q0 = pos[z], q1 = pos[o];
   u64 sum = 0;
   for (u32 j = q0 + lane; j < q1; j += WAVE) sum += hashDepth[list[j]];
@@ -143,54 +130,6 @@ __global__ __launch_bounds__(256) void sp_gather_kernel(u32 nq, const u64 *__res
   }
 }
 
-// flag[i] = 1 at the head of a run of at least T equal keys, cnt[i] = its length there (stage_l.hip's sg_run_kernel: doubling steps, then bisection)
-template <typename K>
-__global__ void sp_run_kernel(const K *__restrict__ keys, u64 n, u32 T, u32 *__restrict__ flag, u32 *__restrict__ cnt) {
-  const u64 stride = (u64)gridDim.x * blockDim.x;
-  for (u64 i = (u64)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
-    const K k = keys[i];
-    u32 f = 0;
-    if (!i || keys[i - 1] != k) {
-      u64 l = i, step = 1;                                    // keys[l] == k; the first r > l with r == n or keys[r] != k
-      u64 r = i + 1;
-      while (r < n && keys[r] == k) { l = r; step <<= 1; r = l + step; }
-      if (r > n) r = n;
-      while (r - l > 1) { const u64 m = (l + r) >> 1; if (keys[m] == k) l = m; else r = m; }
-      const u64 c = r - i;
-      if (c >= T) { f = 1; cnt[i] = (u32)c; }
-    }
-    flag[i] = f;
-  }
-}
-
-// the rows of the flagged runs at oBlock / oCount [pos[i]], their slot at oSlot[pos[i]], and the largest count: one atomic per workgroup
-template <typename K>
-__global__ __launch_bounds__(256) void sp_emit_kernel(const K *__restrict__ keys, u64 n, int cbits, const u32 *__restrict__ flag, const u32 *__restrict__ cnt,
-                                                      const u32 *__restrict__ pos, u64 runs, u32 *__restrict__ oBlock, u32 *__restrict__ oCount,
-                                                      u32 *__restrict__ oSlot, u32 *__restrict__ maxCount) {
-  __shared__ u32 sMax[256 / WAVE];
-  const u64 stride = (u64)gridDim.x * blockDim.x;
-  u32 mx = 0;
-  for (u64 i0 = (u64)blockIdx.x * blockDim.x; i0 < n; i0 += stride) {   // wave-uniform: whole workgroups
-    const u64 i = i0 + threadIdx.x;
-    if (i < n && flag[i]) {
-      const K k = keys[i]; const u32 p = pos[i], c = cnt[i];
-      if (p < runs) { oBlock[p] = (u32)(k & (((K)1 << cbits) - 1)); oCount[p] = c; oSlot[p] = (u32)(k >> cbits); }
-      mx = mx > c ? mx : c;
-    }
-  }
-  mx = wg_max(mx, sMax);
-  if (threadIdx.x == 0 && mx) atomicMax(maxCount, mx);
-}
-
-// rowCnt[q] += rows of the batch with slot q (oSlot ascends). A windowed list comes here once per window, one launch after the other
-__global__ void sp_rowcount_kernel(const u32 *__restrict__ oSlot, u64 runs, u32 nq, u32 *__restrict__ rowCnt) {
-  const u32 q = blockIdx.x * blockDim.x + threadIdx.x;
-  if (q >= nq) return;
-  const u64 s = lower_bound(oSlot, (u64)0, runs, q);
-  rowCnt[q] += (u32)(upper_bound(oSlot, s, runs, q) - s);
-}
-
 // ------------------------------------------------------------------------------------------------ drivers
 namespace {
 
@@ -206,18 +145,6 @@ int sp_check(Ctx *c, const char *cmd, int64_t minShare, bool hasher) {
 }
 
 void release_lists(Ctx *c) { c->haveSeqHashes = false; c->sqSeqs = 0; c->sqEntries = 0; c->sqHash.release(); c->sqOffsets.release(); c->sqHostOff.clear(); }
-void release_rows(Ctx *c) { c->haveSeqBlocks = false; c->sbRows = 0; c->sbLists = 0; c->sbBlock.release(); c->sbCount.release(); c->sbOffsets.release(); }
-
-// dst holds at least `need` words; the first `used` are kept (grown by doubling)
-int sp_reserve(Ctx *c, DevBuf<u32> &dst, u64 used, u64 need) {
-  if (need <= dst.n && dst.p) return 0;
-  DevBuf<u32> b;
-  H10X_HIP(c, b.alloc(hmax<u64>(need, 2 * (u64)dst.n)));
-  if (used) H10X_HIP(c, hipMemcpyAsync(b.p, dst.p, (size_t)used * 4, hipMemcpyDeviceToDevice, c->stream));
-  dst.swap(b);
-  H10X_HIP(c, hipStreamSynchronize(c->stream));               // the old block goes back to the cache behind the copy
-  return 0;
-}
 
 // ---- layer 1: the lists of sequences [0, nSeq) into c->sqHash / sqOffsets, the figures to fig[nSeq] (host)
 int seq_lists(Ctx *c, const u8 *codes, const u64 *seqStart, u32 nSeq, h10x_seq_figures *fig) {
@@ -261,7 +188,7 @@ int seq_lists(Ctx *c, const u8 *codes, const u64 *seqStart, u32 nSeq, h10x_seq_f
       H10X_HIP(c, hipGetLastError());
       H10X_HIP(c, hipMemcpyAsync(hFig.data(), dFig.p, (size_t)24 * ns, hipMemcpyDeviceToHost, st));
       if (kept) {
-        H10X_TRY(sp_reserve(c, c->sqHash, used, used + kept));
+        H10X_TRY(reserve_keep(c, c->sqHash, used, used + kept));
         H10X_HIP(c, hipMemcpyAsync(c->sqHash.p + used, part.p, (size_t)kept * 4, hipMemcpyDeviceToDevice, st));
       }
       H10X_HIP(c, hipStreamSynchronize(st));
@@ -287,13 +214,11 @@ int seq_lists(Ctx *c, const u8 *codes, const u64 *seqStart, u32 nSeq, h10x_seq_f
 
 // ---- layer 2
 struct ListShare {
-  Ctx *c; u32 T, nq; u64 budget;
+  Ctx *c; u32 nq; u64 budget;
   const u64 *hOff; const u64 *dOff; const u32 *dHash;       // the lists: offsets on the host and the device, indices on the device
   std::vector<u64> size;
-  DevBuf<u32> rowCnt, maxCount;
-  DevBuf<u64> keys64, keys64s, listPos, dSize; DevBuf<u32> keys32, keys32s, listCnt, flag, cnt, pos, oSlot;
-  PrimTemp pt;
-  u64 rows = 0, entries = 0; u32 batches = 0, windows = 0, wide = 0;
+  DevBuf<u64> listPos, dSize; DevBuf<u32> listCnt;
+  RowTail tail;
 
   int sizes(u32 q0, u32 n, u32 lo, u32 hi, bool full, u64 *hSize) {
     hipStream_t st = c->stream;
@@ -306,67 +231,40 @@ struct ListShare {
   }
 
   template <typename K>
-  int sortAndEmit(DevBuf<K> &keys, DevBuf<K> &keysS, u32 q0, u32 n, u32 lo, u32 hi, bool full, int cbits, int endBit, u64 units, u64 nKeys) {
-    hipStream_t st = c->stream;
-    if (keys.n < nKeys) { H10X_HIP(c, keys.alloc(nKeys)); H10X_HIP(c, keysS.alloc(nKeys)); }
-    sp_gather_kernel<K><<<(unsigned)hmin<u64>(divUp(units, 4), 65536), 256, 0, st>>>(n, dOff + q0, dHash, c->rowStart.p, c->hashDepth.p, c->rows.p, lo, hi, full ? 1 : 0,
-                                                                                  cbits, listPos.p, nKeys, keys.p);
+  int gather(K *keys, u32 q0, u32 n, u32 lo, u32 hi, bool full, int cbits, u64 units, u64 nKeys) {
+    sp_gather_kernel<K><<<(unsigned)hmin<u64>(divUp(units, 4), 65536), 256, 0, c->stream>>>(n, dOff + q0, dHash, c->rowStart.p, c->hashDepth.p, c->rows.p, lo, hi,
+                                                                                         full ? 1 : 0, cbits, listPos.p, nKeys, keys);
     H10X_HIP(c, hipGetLastError());
-    if (sizeof(K) == 4) H10X_TRY(prim_sort_keys_u32(c, pt, (const u32 *)keys.p, (u32 *)keysS.p, nKeys, 0, endBit));
-    else H10X_TRY(prim_sort_keys_u64(c, pt, (const u64 *)keys.p, (u64 *)keysS.p, nKeys, 0, endBit));
-    if (flag.n < nKeys) { H10X_HIP(c, flag.alloc(nKeys)); H10X_HIP(c, cnt.alloc(nKeys)); H10X_HIP(c, pos.alloc(nKeys)); }
-    const unsigned gr = (unsigned)hmin<u64>(divUp(nKeys, 256), 16384);
-    sp_run_kernel<K><<<gr, 256, 0, st>>>(keysS.p, nKeys, T, flag.p, cnt.p);
-    H10X_HIP(c, hipGetLastError());
-    H10X_TRY(prim_exclusive_scan_u32(c, pt, flag.p, pos.p, nKeys));
-    u32 lastPos = 0, lastFlag = 0;
-    H10X_TRY(c->readback(&lastPos, pos.p + (nKeys - 1), 4)); H10X_TRY(c->readback(&lastFlag, flag.p + (nKeys - 1), 4)); H10X_TRY(c->syncReadbacks());
-    const u64 runs = (u64)lastPos + lastFlag;
-    if (!runs) return 0;
-    H10X_TRY(sp_reserve(c, c->sbBlock, rows, rows + runs)); H10X_TRY(sp_reserve(c, c->sbCount, rows, rows + runs));
-    if (oSlot.n < runs) H10X_HIP(c, oSlot.alloc(runs));
-    sp_emit_kernel<K><<<hmin<unsigned>(gr, SP_EMIT_GRID), 256, 0, st>>>(keysS.p, nKeys, cbits, flag.p, cnt.p, pos.p, runs, c->sbBlock.p + rows, c->sbCount.p + rows, oSlot.p,
-                                                                       maxCount.p);
-    H10X_HIP(c, hipGetLastError());
-    sp_rowcount_kernel<<<divUp(n, 256), 256, 0, st>>>(oSlot.p, runs, n, rowCnt.p + q0);
-    H10X_HIP(c, hipGetLastError());
-    rows += runs;
     return 0;
   }
 
   // lists [q0, q0 + n) in the window [lo, hi); total = list entries gathered
   int batch(u32 q0, u32 n, u32 lo, u32 hi, bool full, u64 total) {
-    hipStream_t st = c->stream;
-    if (!full) { c->nbStats[3] += 1; ++windows; }             // one window of a list above the budget
-    c->nbStats[2] += 1; ++batches;
+    tail.batch(full);                                         // (a window: of a list above the budget)
     if (!total) return 0;
     if (total >= 0xFFFFFFFFull) return c->fail("listShare: %llu list entries in one batch, beyond 2^32 (list %u alone)", total, q0);
     const u64 u0 = hOff[q0], units = hOff[q0 + n] - u0;
     if (listCnt.n < units + 1) { H10X_HIP(c, listCnt.alloc(units + 1)); H10X_HIP(c, listPos.alloc(units + 1)); }
-    sp_unit_kernel<<<divUp(units + 1, 256), 256, 0, st>>>(u0, units, dHash, c->rowStart.p, c->hashDepth.p, c->rows.p, lo, hi, full ? 1 : 0, listCnt.p);
+    sp_unit_kernel<<<divUp(units + 1, 256), 256, 0, c->stream>>>(u0, units, dHash, c->rowStart.p, c->hashDepth.p, c->rows.p, lo, hi, full ? 1 : 0, listCnt.p);
     H10X_HIP(c, hipGetLastError());
-    H10X_TRY(prim_exclusive_scan_u32_u64(c, pt, listCnt.p, listPos.p, units + 1));
-    unsigned long long nKeys = 0;
-    H10X_TRY(c->readback(&nKeys, listPos.p + units, 8)); H10X_TRY(c->syncReadbacks());
+    u64 nKeys = 0;
+    H10X_TRY(tail.places(listCnt.p, listPos.p, units, &nKeys));
     if (nKeys != total) return c->fail("listShare: %llu keys of %llu list entries", nKeys, total);
-    c->nbStats[0] += total; c->nbStats[1] += nKeys; entries += total;
+    tail.gathered(total, nKeys);
     const int cbits = keyBits(c->nBlocks), endBit = cbits + keyBits(n - 1);
-    if (endBit <= 32) return sortAndEmit<u32>(keys32, keys32s, q0, n, lo, hi, full, cbits, endBit, units, nKeys);
-    ++wide;
-    return sortAndEmit<u64>(keys64, keys64s, q0, n, lo, hi, full, cbits, endBit, units, nKeys);
+    H10X_TRY(tail.keys(nKeys, endBit > 32));
+    H10X_TRY(endBit > 32 ? gather(tail.keys64.p, q0, n, lo, hi, full, cbits, units, nKeys) : gather(tail.keys32.p, q0, n, lo, hi, full, cbits, units, nKeys));
+    return tail.emit(nKeys, cbits, endBit, q0, n);
   }
 
-  int run() {
-    hipStream_t st = c->stream;
+  int run(u32 T, u32 *maxCount) {
     size.resize(nq);
     H10X_TRY(sizes(0, nq, 0, c->nBlocks, true, size.data()));
-    H10X_HIP(c, rowCnt.alloc((size_t)nq + 1)); H10X_HIP(c, hipMemsetAsync(rowCnt.p, 0, ((size_t)nq + 1) * 4, st));
-    H10X_HIP(c, maxCount.alloc(1)); H10X_HIP(c, hipMemsetAsync(maxCount.p, 0, 4, st));
+    H10X_TRY(tail.begin(c, &c->sb, T, nq));
     H10X_TRY(cut_batches(size.data(), nq, c->nBlocks, budget,
                          [&](u32 q, u32 lo, u32 hi, u64 *records) { return sizes(q, 1, lo, hi, false, records); },
                          [&](u32 q0, u32 n, u32 lo, u32 hi, bool full, u64 total) { return batch(q0, n, lo, hi, full, total); }));
-    H10X_HIP(c, c->sbOffsets.alloc((size_t)nq + 1));
-    return prim_exclusive_scan_u32_u64(c, pt, rowCnt.p, c->sbOffsets.p, (size_t)nq + 1);
+    return tail.finish(maxCount);
   }
 };
 
@@ -374,25 +272,24 @@ struct ListShare {
 int list_share(Ctx *c, int64_t minShare, const u64 *hOff, const u64 *dOff, const u32 *dHash, u32 nq, h10x_list_share_info *info) {
   memset(info, 0, sizeof *info);
   info->nBlocks = c->nBlocks; info->lists = nq; info->listHashes = nq ? hOff[nq] : 0;
-  ListShare g; g.c = c; g.T = (u32)hmin<int64_t>(minShare, 0xFFFFFFFFll); g.nq = nq; g.hOff = hOff; g.dOff = dOff; g.dHash = dHash;
-  g.budget = c->optNbBudget > 0 ? (u64)c->optNbBudget : SP_DEFAULT_BUDGET;
+  ListShare g; g.c = c; g.nq = nq; g.hOff = hOff; g.dOff = dOff; g.dHash = dHash;
+  g.budget = c->optNbBudget > 0 ? (u64)c->optNbBudget : ROWS_DEFAULT_BUDGET;
   if (!nq) {
-    H10X_HIP(c, c->sbOffsets.alloc(1)); H10X_HIP(c, hipMemsetAsync(c->sbOffsets.p, 0, 8, c->stream));
+    H10X_HIP(c, c->sb.offsets.alloc(1)); H10X_HIP(c, hipMemsetAsync(c->sb.offsets.p, 0, 8, c->stream));
   } else {
-    const int rc = g.run();
-    if (rc) { (void)hipStreamSynchronize(c->stream); release_rows(c); return rc; }
     u32 mx = 0;
-    H10X_TRY(c->readback(&mx, g.maxCount.p, 4)); H10X_TRY(c->syncReadbacks());
+    const int rc = g.run((u32)hmin<int64_t>(minShare, 0xFFFFFFFFll), &mx);
+    if (rc) { (void)hipStreamSynchronize(c->stream); c->sb.release(); return rc; }
     info->maxCount = mx;
   }
   H10X_HIP(c, hipStreamSynchronize(c->stream));
-  c->haveSeqBlocks = true; c->sbRows = g.rows; c->sbLists = nq;
-  info->rows = g.rows; info->listEntries = g.entries; info->batches = g.batches; info->windows = g.windows; info->wideBatches = g.wide;
+  c->sb.have = true; c->sb.rows = g.tail.rows; c->sb.lists = nq;
+  info->rows = g.tail.rows; info->listEntries = g.tail.entries; info->batches = g.tail.batches; info->windows = g.tail.windows; info->wideBatches = g.tail.wide;
   return 0;
 }
 }  // namespace
 
-void stageP_release(Ctx *c) { release_lists(c); release_rows(c); }
+void stageP_release(Ctx *c) { release_lists(c); c->sb.release(); }
 
 int stageP_seqHashes(Ctx *c, const u8 *codes, const u64 *seqStart, u32 nSeq, h10x_seq_figures *fig) {
   release_lists(c);
@@ -415,7 +312,7 @@ int stageP_seqHashesGet(Ctx *c, u64 *offsets, u32 *hashes, u64 cap) {
 }
 
 int stageP_listShare(Ctx *c, int64_t minShare, const u64 *offsets, const u32 *hashes, u32 nq, h10x_list_share_info *info) {
-  release_rows(c);
+  c->sb.release();
   H10X_TRY(sp_check(c, "listShare", minShare, false));
   if (nq && (!offsets || (offsets[nq] && !hashes))) return c->fail("listShare: null argument");
   const u64 zero = 0;
@@ -449,16 +346,8 @@ int stageP_seqBlocks(Ctx *c, int64_t minShare, const u8 *codes, const u64 *seqSt
   return rc;
 }
 
-// offsets[lists + 1] and the first min(cap, rows) rows of the kept result, to host (toDevice = 0) or device memory; any may be null
 int stageP_get(Ctx *c, u64 *offsets, u32 *block, u32 *count, u64 cap, int toDevice) {
-  if (!c->haveSeqBlocks) return c->fail("seqBlocks: no rows are kept (run it first; a new range, --clusterSplit and a new state release them)");
-  const hipMemcpyKind kind = toDevice ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
-  const size_t m = (size_t)hmin<u64>(cap, c->sbRows);
-  if (offsets) H10X_HIP(c, hipMemcpyAsync(offsets, c->sbOffsets.p, ((size_t)c->sbLists + 1) * 8, kind, c->stream));
-  if (m && block) H10X_HIP(c, hipMemcpyAsync(block, c->sbBlock.p, m * 4, kind, c->stream));
-  if (m && count) H10X_HIP(c, hipMemcpyAsync(count, c->sbCount.p, m * 4, kind, c->stream));
-  H10X_HIP(c, hipStreamSynchronize(c->stream));
-  return 0;
+  return c->sb.get(c, offsets, block, count, cap, toDevice, "seqBlocks: no rows are kept (run it first; a new range, --clusterSplit and a new state release them)");
 }
 
 }  // namespace h10x

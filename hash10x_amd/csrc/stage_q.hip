@@ -11,40 +11,23 @@
 //   gather   one LANE per output pair: its unit by a search in the places, then key = (e - first list of batch) << listBits | f. The units are short
 //            (a block stands in few ends), a wave per unit would idle most lanes; a lane per pair keeps whole waves and coalesced stores.
 //            32-bit keys where slot and list fit, else 64-bit;
-//   sort     prim_sort_keys_u32 / _u64 on the bits in use;
-//   runs     a run of equal keys is one (e, f) with shared = its length; runs of length >= M are flagged, siblings (2s, 2s + 1) are not;
-//   rows     a scan of the flags places (f, shared) behind the rows of the batches before; rows per list by two searches in the slot column.
+//   tail     census_rows.hip: the keys sorted, a run of equal keys is one (e, f) with shared = its length, the runs of length >= M (siblings
+//            (2s, 2s + 1) are none) placed by a scan as rows (f, shared) behind those of the batches before, the rows per list summed to offsets[].
 // Batches are cut by list against "neighbour_budget" (pairs gathered); a list above it runs alone in windows of the other list's number (its units'
-// partners ascend, so a window is a stretch of each). The run, emit and row-count kernels are this file's own copies of stage_l.hip's.
-#include "common.hpp"
-#include "prim.hpp"
+// partners ascend, so a window is a stretch of each).
+#include "census_rows.hpp"
+#include "runs.hpp"
 #include "wave.hpp"
 
 namespace h10x {
 
-static constexpr u64 SQ_DEFAULT_BUDGET = 1ull << 26;       // pairs per batch (stage_l.hip's SG_DEFAULT_BUDGET)
-static constexpr unsigned SQ_EMIT_GRID = 2048;
 static constexpr u64 SQ_LIST_MASK = 0xFFFFFFFFull;         // accumulator key = block << 32 | list
 
-// the first index in [l, r) with keys[index] >= v
-__device__ __forceinline__ u64 sq_lower64(const u64 *__restrict__ keys, u64 l, u64 r, u64 v) {
-  while (l < r) { const u64 m = (l + r) >> 1; if (keys[m] < v) l = m + 1; else r = m; }
-  return l;
-}
 // the first entry of list e in the accumulator (its list field ascends)
 __device__ __forceinline__ u64 sq_list_start(const u64 *__restrict__ acc, u64 n, u64 e) {
   u64 l = 0, r = n;
   while (l < r) { const u64 m = (l + r) >> 1; if ((acc[m] & SQ_LIST_MASK) < e) l = m + 1; else r = m; }
   return l;
-}
-
-// the end of the run of block d that holds sorted[p]: the first r > p with r == n or another block there (doubling steps, then bisection: the runs are short)
-__device__ __forceinline__ u64 sq_run_end(const u64 *__restrict__ sorted, u64 n, u64 p, int lb, u64 d) {
-  u64 l = p, step = 1, r = p + 1;
-  while (r < n && (sorted[r] >> lb) == d) { l = r; step <<= 1; r = l + step; }
-  if (r > n) r = n;
-  while (r - l > 1) { const u64 m = (l + r) >> 1; if ((sorted[m] >> lb) == d) l = m; else r = m; }
-  return r;
 }
 
 // entry j of rows in CSR form (off[0] = 0, m = off[nLists]) -> acc[j]
@@ -70,7 +53,7 @@ __global__ __launch_bounds__(256) void sq_blocks_kernel(const u64 *__restrict__ 
     if (i < n) {
       const u64 d = sorted[i] >> lb;
       if (!i || (sorted[i - 1] >> lb) != d) {
-        const u64 len = sq_run_end(sorted, n, i, lb, d) - i;
+        const u64 len = run_end(sorted, n, i, [lb](u64 k) { return k >> lb; }) - i;   // the block's run
         if (!maxLists || len <= maxLists) ++used; else ++skipped;
       }
     }
@@ -87,12 +70,12 @@ __global__ __launch_bounds__(256) void sq_unit_kernel(const u64 *__restrict__ ac
   if (i > n) return;
   if (i == n) { cnt[i] = 0; return; }
   const u64 k = acc[i], d = k >> 32;
-  const u64 at = sq_lower64(sorted, 0, n, d << lb | (k & SQ_LIST_MASK)), p = at + 1;   // the key itself: it is there
-  const u64 re = sq_run_end(sorted, n, at, lb, d);
+  const u64 at = lower_bound(sorted, (u64)0, n, d << lb | (k & SQ_LIST_MASK)), p = at + 1;   // the key itself: it is there
+  const u64 re = run_end(sorted, n, at, [lb](u64 v) { return v >> lb; });   // the end of block d's run
   u64 e = re;
   if (maxLists) {                                             // the run's start matters only within maxLists of the key: a run that reaches further back is too long
     const u64 lo = at > maxLists ? at - maxLists : 0;
-    if (re - sq_lower64(sorted, lo, at, d << lb) > maxLists) e = p;
+    if (re - lower_bound(sorted, lo, at, d << lb) > maxLists) e = p;
   }
   src[i] = (u32)p; end[i] = (u32)e; cnt[i] = (u32)(e - p);
 }
@@ -113,7 +96,7 @@ __device__ __forceinline__ void sq_window(const u64 *__restrict__ acc, const u64
   a = src[i]; b = end[i];
   if (full) return;
   const u64 base = (acc[i] >> 32) << lb;
-  a = sq_lower64(sorted, a, b, base + lo); b = sq_lower64(sorted, a, b, base + hi);
+  a = lower_bound(sorted, a, b, base + lo); b = lower_bound(sorted, a, b, base + hi);
 }
 
 // one lane per unit u of the batch (row entry i0 + u): cntW[u] = its partners in the window, from srcW[u]; cntW[units] = 0
@@ -152,59 +135,9 @@ __global__ __launch_bounds__(256) void sq_gather_kernel(const u64 *__restrict__ 
   }
 }
 
-// flag[i] = 1 at the head of a run of at least T equal keys that is no sibling pair, cnt[i] = its length there (stage_l.hip's sg_run_kernel)
-template <typename K>
-__global__ void sq_run_kernel(const K *__restrict__ keys, u64 n, u32 T, int siblings, u32 q0, int lb, u32 *__restrict__ flag, u32 *__restrict__ cnt) {
-  const u64 stride = (u64)gridDim.x * blockDim.x;
-  for (u64 i = (u64)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
-    const K k = keys[i];
-    u32 f = 0;
-    if (!i || keys[i - 1] != k) {
-      u64 l = i, step = 1;                                    // keys[l] == k; the first r > l with r == n or keys[r] != k
-      u64 r = i + 1;
-      while (r < n && keys[r] == k) { l = r; step <<= 1; r = l + step; }
-      if (r > n) r = n;
-      while (r - l > 1) { const u64 m = (l + r) >> 1; if (keys[m] == k) l = m; else r = m; }
-      const u64 c = r - i;
-      const u32 a = q0 + (u32)((u64)k >> lb), b = (u32)((u64)k & (((u64)1 << lb) - 1));
-      if (c >= T && !(siblings && (a >> 1) == (b >> 1))) { f = 1; cnt[i] = (u32)c; }
-    }
-    flag[i] = f;
-  }
-}
-
-// the rows of the flagged runs at oOther / oShared [pos[i]], their slot at oSlot[pos[i]], and the largest length: one atomic per workgroup
-template <typename K>
-__global__ __launch_bounds__(256) void sq_emit_kernel(const K *__restrict__ keys, u64 n, int lb, const u32 *__restrict__ flag, const u32 *__restrict__ cnt,
-                                                      const u32 *__restrict__ pos, u64 runs, u32 *__restrict__ oOther, u32 *__restrict__ oShared,
-                                                      u32 *__restrict__ oSlot, u32 *__restrict__ maxShared) {
-  __shared__ u32 sMax[256 / WAVE];
-  const u64 stride = (u64)gridDim.x * blockDim.x;
-  u32 mx = 0;
-  for (u64 i0 = (u64)blockIdx.x * blockDim.x; i0 < n; i0 += stride) {   // wave-uniform: whole workgroups
-    const u64 i = i0 + threadIdx.x;
-    if (i < n && flag[i]) {
-      const u64 k = (u64)keys[i]; const u32 p = pos[i], c = cnt[i];
-      if (p < runs) { oOther[p] = (u32)(k & (((u64)1 << lb) - 1)); oShared[p] = c; oSlot[p] = (u32)(k >> lb); }
-      mx = mx > c ? mx : c;
-    }
-  }
-  mx = wg_max(mx, sMax);
-  if (threadIdx.x == 0 && mx) atomicMax(maxShared, mx);
-}
-
-// rowCnt[q] += rows of the batch with slot q (oSlot ascends). A windowed list comes here once per window, one launch after the other
-__global__ void sq_rowcount_kernel(const u32 *__restrict__ oSlot, u64 runs, u32 nq, u32 *__restrict__ rowCnt) {
-  const u32 q = blockIdx.x * blockDim.x + threadIdx.x;
-  if (q >= nq) return;
-  const u64 s = lower_bound(oSlot, (u64)0, runs, q);
-  rowCnt[q] += (u32)(upper_bound(oSlot, s, runs, q) - s);
-}
-
 // ------------------------------------------------------------------------------------------------ drivers
 namespace {
 
-void release_links(Ctx *c) { c->haveRowLinks = false; c->rlLinks = 0; c->rlLists = 0; c->rlOther.release(); c->rlShared.release(); c->rlOffsets.release(); }
 void release_acc(Ctx *c) { c->rqOpen = false; c->rqEntries = 0; c->rqLists = 0; c->rqBlocks = 0; c->rqKeys.release(); }
 
 int sq_ctx_check(Ctx *c, const char *cmd) {
@@ -217,24 +150,12 @@ int sq_open_check(Ctx *c, const char *cmd) {
   return 0;
 }
 
-// dst holds at least `need` words; the first `used` are kept (grown by doubling)
-template <typename T>
-int sq_reserve(Ctx *c, DevBuf<T> &dst, u64 used, u64 need) {
-  if (need <= dst.n && dst.p) return 0;
-  DevBuf<T> b;
-  H10X_HIP(c, b.alloc(hmax<u64>(need, 2 * (u64)dst.n)));
-  if (used) H10X_HIP(c, hipMemcpyAsync(b.p, dst.p, (size_t)used * sizeof(T), hipMemcpyDeviceToDevice, c->stream));
-  dst.swap(b);
-  H10X_HIP(c, hipStreamSynchronize(c->stream));               // the old block goes back to the cache behind the copy
-  return 0;
-}
-
 // nLists rows with m entries in CSR form on the device (dOff[0] = 0) go behind the accumulator
 int append(Ctx *c, const u64 *dOff, const u32 *dBlock, u64 nLists, u64 m) {
   if (c->rqLists + nLists > 0xFFFFFFFFull) return c->fail("rowLinks: %llu lists, beyond 2^32 - 1", c->rqLists + nLists);
   if (c->rqEntries + m >= 0xFFFFFFFFull) return c->fail("rowLinks: %llu row entries, beyond 2^32 - 2", c->rqEntries + m);
   if (m) {
-    H10X_TRY(sq_reserve(c, c->rqKeys, c->rqEntries, c->rqEntries + m));
+    H10X_TRY(reserve_keep(c, c->rqKeys, c->rqEntries, c->rqEntries + m));
     sq_append_kernel<<<(unsigned)hmin<u64>(divUp(m, 256), 16384), 256, 0, c->stream>>>(dOff, dBlock, (u32)nLists, m, (u32)c->rqLists, c->rqKeys.p + c->rqEntries);
     H10X_HIP(c, hipGetLastError());
   }
@@ -243,62 +164,36 @@ int append(Ctx *c, const u64 *dOff, const u32 *dBlock, u64 nLists, u64 m) {
 }
 
 struct RowLinks {
-  Ctx *c; u32 T, maxLists, nq; int siblings, lb; u64 n, budget;
+  Ctx *c; u32 maxLists, nq; int lb; u64 n, budget;
   std::vector<u64> size, hOff;
-  DevBuf<u64> packed, sorted, place, dOff, dSize, placeW, keys64, keys64s, winSize;
-  DevBuf<u32> src, end, cnt, cntW, srcW, keys32, keys32s, flag, rcnt, pos, oSlot, rowCnt;
-  u32 *tally = nullptr;                                     // used, skipped, maxShared
-  PrimTemp pt;
-  u64 rows = 0, pairs = 0; u32 batches = 0, windows = 0, wide = 0;
+  DevBuf<u64> packed, sorted, place, dOff, dSize, placeW, winSize;
+  DevBuf<u32> src, end, cnt, cntW, srcW;
+  RowTail tail;
 
   template <typename K>
-  int sortAndEmit(DevBuf<K> &keys, DevBuf<K> &keysS, u32 q0, u32 nl, int endBit, u64 i0, u64 units, u64 nKeys) {
-    hipStream_t st = c->stream;
-    if (keys.n < nKeys) { H10X_HIP(c, keys.alloc(nKeys)); H10X_HIP(c, keysS.alloc(nKeys)); }
-    const unsigned gr = (unsigned)hmin<u64>(divUp(nKeys, 256), 16384);
-    sq_gather_kernel<K><<<gr, 256, 0, st>>>(c->rqKeys.p, sorted.p, i0, (u32)units, placeW.p, srcW.p, q0, lb, nKeys, keys.p);
+  int gather(K *keys, u32 q0, u64 i0, u64 units, u64 nKeys) {
+    sq_gather_kernel<K><<<(unsigned)hmin<u64>(divUp(nKeys, 256), 16384), 256, 0, c->stream>>>(c->rqKeys.p, sorted.p, i0, (u32)units, placeW.p, srcW.p, q0, lb, nKeys, keys);
     H10X_HIP(c, hipGetLastError());
-    if (sizeof(K) == 4) H10X_TRY(prim_sort_keys_u32(c, pt, (const u32 *)keys.p, (u32 *)keysS.p, nKeys, 0, endBit));
-    else H10X_TRY(prim_sort_keys_u64(c, pt, (const u64 *)keys.p, (u64 *)keysS.p, nKeys, 0, endBit));
-    if (flag.n < nKeys) { H10X_HIP(c, flag.alloc(nKeys)); H10X_HIP(c, rcnt.alloc(nKeys)); H10X_HIP(c, pos.alloc(nKeys)); }
-    sq_run_kernel<K><<<gr, 256, 0, st>>>(keysS.p, nKeys, T, siblings, q0, lb, flag.p, rcnt.p);
-    H10X_HIP(c, hipGetLastError());
-    H10X_TRY(prim_exclusive_scan_u32(c, pt, flag.p, pos.p, nKeys));
-    u32 lastPos = 0, lastFlag = 0;
-    H10X_TRY(c->readback(&lastPos, pos.p + (nKeys - 1), 4)); H10X_TRY(c->readback(&lastFlag, flag.p + (nKeys - 1), 4)); H10X_TRY(c->syncReadbacks());
-    const u64 runs = (u64)lastPos + lastFlag;
-    if (!runs) return 0;
-    H10X_TRY(sq_reserve(c, c->rlOther, rows, rows + runs)); H10X_TRY(sq_reserve(c, c->rlShared, rows, rows + runs));
-    if (oSlot.n < runs) H10X_HIP(c, oSlot.alloc(runs));
-    sq_emit_kernel<K><<<hmin<unsigned>(gr, SQ_EMIT_GRID), 256, 0, st>>>(keysS.p, nKeys, lb, flag.p, rcnt.p, pos.p, runs, c->rlOther.p + rows, c->rlShared.p + rows, oSlot.p,
-                                                                       tally + 2);
-    H10X_HIP(c, hipGetLastError());
-    sq_rowcount_kernel<<<divUp(nl, 256), 256, 0, st>>>(oSlot.p, runs, nl, rowCnt.p + q0);
-    H10X_HIP(c, hipGetLastError());
-    rows += runs;
     return 0;
   }
 
   // lists [q0, q0 + nl) against the partners numbered [lo, hi); total = pairs gathered
   int batch(u32 q0, u32 nl, u32 lo, u32 hi, bool full, u64 total) {
-    hipStream_t st = c->stream;
-    if (!full) { c->nbStats[3] += 1; ++windows; }             // one window of a list above the budget
-    c->nbStats[2] += 1; ++batches;
+    tail.batch(full);                                         // (a window: of a list above the budget)
     if (!total) return 0;
     if (total >= 0xFFFFFFFFull) return c->fail("rowLinks: %llu pairs in one batch, beyond 2^32 (list %u alone)", total, q0);
     const u64 i0 = hOff[q0], units = hOff[q0 + nl] - i0;
     if (cntW.n < units + 1) { H10X_HIP(c, cntW.alloc(units + 1)); H10X_HIP(c, srcW.alloc(units + 1)); H10X_HIP(c, placeW.alloc(units + 1)); }
-    sq_window_kernel<<<divUp(units + 1, 256), 256, 0, st>>>(c->rqKeys.p, sorted.p, src.p, end.p, i0, units, lb, lo, hi, full ? 1 : 0, cntW.p, srcW.p);
+    sq_window_kernel<<<divUp(units + 1, 256), 256, 0, c->stream>>>(c->rqKeys.p, sorted.p, src.p, end.p, i0, units, lb, lo, hi, full ? 1 : 0, cntW.p, srcW.p);
     H10X_HIP(c, hipGetLastError());
-    H10X_TRY(prim_exclusive_scan_u32_u64(c, pt, cntW.p, placeW.p, units + 1));
-    unsigned long long nKeys = 0;
-    H10X_TRY(c->readback(&nKeys, placeW.p + units, 8)); H10X_TRY(c->syncReadbacks());
+    u64 nKeys = 0;
+    H10X_TRY(tail.places(cntW.p, placeW.p, units, &nKeys));
     if (nKeys != total) return c->fail("rowLinks: %llu keys of %llu pairs", nKeys, total);
-    c->nbStats[0] += total; c->nbStats[1] += nKeys; pairs += total;
+    tail.gathered(total, nKeys);
     const int endBit = lb + keyBits(nl - 1);
-    if (endBit <= 32) return sortAndEmit<u32>(keys32, keys32s, q0, nl, endBit, i0, units, nKeys);
-    ++wide;
-    return sortAndEmit<u64>(keys64, keys64s, q0, nl, endBit, i0, units, nKeys);
+    H10X_TRY(tail.keys(nKeys, endBit > 32));
+    H10X_TRY(endBit > 32 ? gather(tail.keys64.p, q0, i0, units, nKeys) : gather(tail.keys32.p, q0, i0, units, nKeys));
+    return tail.emit(nKeys, lb, endBit, q0, nl);
   }
 
   int windowSize(u32 q, u32 lo, u32 hi, u64 *records) {
@@ -311,13 +206,12 @@ struct RowLinks {
     return 0;
   }
 
-  int run(h10x_row_links_info *info) {
-    hipStream_t st = c->stream;
+  int run(u32 T, bool siblings, h10x_row_links_info *info) {
+    hipStream_t st = c->stream; PrimTemp &pt = tail.pt;
     const u64 *acc = c->rqKeys.p;
-    tally = c->zeros(3);
+    u32 *tally = c->zeros(2);                                 // used, skipped
     if (!tally) return -1;
-    H10X_HIP(c, rowCnt.alloc((size_t)nq + 1)); H10X_HIP(c, hipMemsetAsync(rowCnt.p, 0, ((size_t)nq + 1) * 4, st));
-    H10X_HIP(c, c->rlOffsets.alloc((size_t)nq + 1));
+    H10X_TRY(tail.begin(c, &c->rl, T, nq, siblings));
     if (n) {
       const int endBit = lb + keyBits(c->rqBlocks ? c->rqBlocks - 1 : 0);
       const unsigned gr = (unsigned)hmin<u64>(divUp(n, 256), 16384);
@@ -326,7 +220,7 @@ struct RowLinks {
       H10X_HIP(c, hipGetLastError());
       H10X_TRY(prim_sort_keys_u64(c, pt, packed.p, sorted.p, n, 0, endBit));
       packed.release();
-      sq_blocks_kernel<<<hmin<unsigned>(gr, SQ_EMIT_GRID), 256, 0, st>>>(sorted.p, n, lb, maxLists, tally);
+      sq_blocks_kernel<<<hmin<unsigned>(gr, ROWS_EMIT_GRID), 256, 0, st>>>(sorted.p, n, lb, maxLists, tally);
       H10X_HIP(c, hipGetLastError());
       H10X_HIP(c, src.alloc(n)); H10X_HIP(c, end.alloc(n)); H10X_HIP(c, cnt.alloc(n + 1)); H10X_HIP(c, place.alloc(n + 1));
       sq_unit_kernel<<<divUp(n + 1, 256), 256, 0, st>>>(acc, sorted.p, n, lb, maxLists, src.p, end.p, cnt.p);
@@ -346,16 +240,15 @@ struct RowLinks {
                            [&](u32 q, u32 lo, u32 hi, u64 *records) { return windowSize(q, lo, hi, records); },
                            [&](u32 q0, u32 nl, u32 lo, u32 hi, bool full, u64 total) { return batch(q0, nl, lo, hi, full, total); }));
     }
-    H10X_TRY(prim_exclusive_scan_u32_u64(c, pt, rowCnt.p, c->rlOffsets.p, (size_t)nq + 1));
-    u32 t[3] = {0, 0, 0};
-    H10X_TRY(c->readback(t, tally, 12)); H10X_TRY(c->syncReadbacks());
-    info->blocksUsed = t[0]; info->skippedBlocks = t[1]; info->maxShared = t[2];
+    u32 t[2] = {0, 0}, mx = 0;
+    H10X_TRY(c->readback(t, tally, 8)); H10X_TRY(tail.finish(&mx));   // (one round trip for both)
+    info->blocksUsed = t[0]; info->skippedBlocks = t[1]; info->maxShared = mx;
     return 0;
   }
 };
 }  // namespace
 
-void stageQ_release(Ctx *c) { release_acc(c); release_links(c); }
+void stageQ_release(Ctx *c) { release_acc(c); c->rl.release(); }
 
 int stageQ_begin(Ctx *c, u32 nBlocks) {
   stageQ_release(c);
@@ -394,51 +287,43 @@ int stageQ_addKept(Ctx *c) {
   H10X_TRY(sq_open_check(c, "rowLinks"));
   if (!c->haveState) return c->fail("no hash state loaded: use readFQB or readHash first");
   if (!c->haveRange || !c->haveGood) return c->fail("!! you must set hashDepthRange before rowLinks");
-  if (!c->haveSeqBlocks) return c->fail("rowLinks: no rows are kept (run h10x_list_share_run or h10x_seq_blocks_run first)");
+  if (!c->sb.have) return c->fail("rowLinks: no rows are kept (run h10x_list_share_run or h10x_seq_blocks_run first)");
   if (c->nBlocks > c->rqBlocks) return c->fail("rowLinks: the kept rows are of %u blocks, the accumulator of %u", c->nBlocks, c->rqBlocks);
-  return append(c, c->sbOffsets.p, c->sbBlock.p, c->sbLists, c->sbRows);
+  return append(c, c->sb.offsets.p, c->sb.a.p, c->sb.lists, c->sb.rows);
 }
 
 int stageQ_finish(Ctx *c, int64_t minBlocks, int64_t maxLists, int siblings, h10x_row_links_info *info) {
-  release_links(c);
+  c->rl.release();
   memset(info, 0, sizeof *info);
   H10X_TRY(sq_open_check(c, "rowLinks"));
   if (minBlocks < 1) return c->fail("!! seqLinks minBlocks %lld must be >= 1", (long long)minBlocks);
   if (maxLists < 0) return c->fail("!! seqLinks maxEnds %lld must be >= 0", (long long)maxLists);
   if (c->rqLists > 0xFFFFFFFFull) return c->fail("rowLinks: %llu lists, beyond 2^32 - 1", c->rqLists);
-  RowLinks g; g.c = c; g.T = (u32)hmin<int64_t>(minBlocks, 0xFFFFFFFFll); g.maxLists = (u32)hmin<int64_t>(maxLists, 0xFFFFFFFFll);
-  g.nq = (u32)c->rqLists; g.siblings = siblings ? 1 : 0; g.n = c->rqEntries; g.lb = keyBits(g.nq ? g.nq - 1 : 0);
-  g.budget = c->optNbBudget > 0 ? (u64)c->optNbBudget : SQ_DEFAULT_BUDGET;
+  RowLinks g; g.c = c; g.maxLists = (u32)hmin<int64_t>(maxLists, 0xFFFFFFFFll);
+  g.nq = (u32)c->rqLists; g.n = c->rqEntries; g.lb = keyBits(g.nq ? g.nq - 1 : 0);
+  g.budget = c->optNbBudget > 0 ? (u64)c->optNbBudget : ROWS_DEFAULT_BUDGET;
   if (g.lb + keyBits(c->rqBlocks) > 63) return c->fail("rowLinks: %u lists of %u blocks do not fit a 64-bit key", g.nq, c->rqBlocks);
   info->lists = c->rqLists; info->rowEntries = c->rqEntries;
   ZeroScope zs(c);
   if (zs.rc) return zs.rc;
-  const int rc = g.run(info);
-  if (rc) { (void)hipStreamSynchronize(c->stream); release_links(c); return rc; }
+  const int rc = g.run((u32)hmin<int64_t>(minBlocks, 0xFFFFFFFFll), siblings != 0, info);
+  if (rc) { (void)hipStreamSynchronize(c->stream); c->rl.release(); return rc; }
   H10X_HIP(c, hipStreamSynchronize(c->stream));
-  if (!c->rlOther.p) { H10X_HIP(c, c->rlOther.alloc(1)); H10X_HIP(c, c->rlShared.alloc(1)); }
-  c->haveRowLinks = true; c->rlLinks = g.rows; c->rlLists = g.nq;
-  info->pairs = g.pairs; info->links = g.rows; info->batches = g.batches; info->windows = g.windows; info->wideBatches = g.wide;
+  if (!c->rl.a.p) { H10X_HIP(c, c->rl.a.alloc(1)); H10X_HIP(c, c->rl.b.alloc(1)); }
+  c->rl.have = true; c->rl.rows = g.tail.rows; c->rl.lists = g.nq;
+  info->pairs = g.tail.entries; info->links = g.tail.rows; info->batches = g.tail.batches; info->windows = g.tail.windows; info->wideBatches = g.tail.wide;
   return 0;
 }
 
-// offsets[lists + 1] and the first min(cap, links) links of the kept result, to host (toDevice = 0) or device memory; any may be null
 int stageQ_get(Ctx *c, u64 *offsets, u32 *other, u32 *shared, u64 cap, int toDevice) {
-  if (!c->haveRowLinks) return c->fail("rowLinks: no links are kept (finish first; a new begin, a new range, --clusterSplit and a new state release them)");
-  const hipMemcpyKind kind = toDevice ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
-  const size_t m = (size_t)hmin<u64>(cap, c->rlLinks);
-  if (offsets) H10X_HIP(c, hipMemcpyAsync(offsets, c->rlOffsets.p, ((size_t)c->rlLists + 1) * 8, kind, c->stream));
-  if (m && other) H10X_HIP(c, hipMemcpyAsync(other, c->rlOther.p, m * 4, kind, c->stream));
-  if (m && shared) H10X_HIP(c, hipMemcpyAsync(shared, c->rlShared.p, m * 4, kind, c->stream));
-  H10X_HIP(c, hipStreamSynchronize(c->stream));
-  return 0;
+  return c->rl.get(c, offsets, other, shared, cap, toDevice, "rowLinks: no links are kept (finish first; a new begin, a new range, --clusterSplit and a new state release them)");
 }
 
 int stageQ_getRange(Ctx *c, u64 first, u64 count, u32 *other, u32 *shared) {
-  if (!c->haveRowLinks) return c->fail("rowLinks: no links are kept (finish first; a new begin, a new range, --clusterSplit and a new state release them)");
-  if (first > c->rlLinks || count > c->rlLinks - first) return c->fail("rowLinks: links %llu .. %llu of %llu", first, first + count, c->rlLinks);
-  if (count && other) H10X_HIP(c, hipMemcpyAsync(other, c->rlOther.p + first, (size_t)count * 4, hipMemcpyDeviceToHost, c->stream));
-  if (count && shared) H10X_HIP(c, hipMemcpyAsync(shared, c->rlShared.p + first, (size_t)count * 4, hipMemcpyDeviceToHost, c->stream));
+  if (!c->rl.have) return c->fail("rowLinks: no links are kept (finish first; a new begin, a new range, --clusterSplit and a new state release them)");
+  if (first > c->rl.rows || count > c->rl.rows - first) return c->fail("rowLinks: links %llu .. %llu of %llu", first, first + count, c->rl.rows);
+  if (count && other) H10X_HIP(c, hipMemcpyAsync(other, c->rl.a.p + first, (size_t)count * 4, hipMemcpyDeviceToHost, c->stream));
+  if (count && shared) H10X_HIP(c, hipMemcpyAsync(shared, c->rl.b.p + first, (size_t)count * 4, hipMemcpyDeviceToHost, c->stream));
   H10X_HIP(c, hipStreamSynchronize(c->stream));
   return 0;
 }

@@ -1,4 +1,4 @@
-// wave.hpp — device helpers of the census family (stage_f / stage_l / stage_m / stage_n): wave and workgroup folds, searches in ascending
+// wave.hpp — device helpers of the census family (stage_f / stage_l / stage_m / stage_n / stage_p / stage_q, census_rows): wave and workgroup folds, searches in ascending
 // arrays, the window of a barcode list and the compaction step. No kernels here. Everything is wave-uniform where it says so: call it from
 // code that every lane of the wave reaches.
 #pragma once
@@ -27,8 +27,8 @@ __device__ __forceinline__ u32 wg_max(u32 v, u32 *s) { return wg_fold<true>(v, s
 
 // ---- searches. rows[l .. r) ascends (global memory or LDS: inlined, the reads keep their address space)
 // the first index in [l, r) with rows[index] >= lo (r if there is none)
-template <typename I>
-__device__ __forceinline__ I lower_bound(const u32 *rows, I l, I r, u32 lo) {
+template <typename E, typename I>
+__device__ __forceinline__ I lower_bound(const E *rows, I l, I r, E lo) {
   while (l < r) { const I m = (l + r) >> 1; if (rows[m] < lo) l = m + 1; else r = m; }
   return l;
 }

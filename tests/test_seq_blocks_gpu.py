@@ -177,6 +177,49 @@ def test_both_key_widths(tmp_path):
     h.close()
 
 
+# ------------------------------------------------------------------------------------ run lengths at the steps of the run search
+RUN_LENGTHS = (1, 2, 3, 4, 7, 8, 9, 15, 16, 17)                # the search probes at head + 2^j - 1
+
+
+def test_run_lengths(tmp_path):
+    """Hash i + 1 stands RUN_LENGTHS[i] times in block i + 1 and RUN_LENGTHS[(i + 3) % 10] times in block i + 11, and nowhere else: the row of the
+    one-hash list [i + 1] is those two blocks with those counts, where they reach the threshold. Ten lists, rotated so that each in turn is the last:
+    its second run then ends the batch's key array. Thresholds c - 1, c, c + 1 around that run's length c; every list is checked at each. Budget 2 is
+    below every list: each runs alone in windows of block index, its two runs in different windows, so its row count is added to twice."""
+    n = len(RUN_LENGTHS)
+    table = {i + 1: ((i + 1, RUN_LENGTHS[i]), (i + 1 + n, RUN_LENGTHS[(i + 3) % n])) for i in range(n)}
+    blocks = [[] for _ in range(2 * n)]
+    for x, runs in table.items():
+        for b, c in runs:
+            blocks[b - 1] += [x] * c
+    h = orc.load_image(tmp_path, blocks, 1, 100)
+    seen = set()
+    for last in range(n):
+        lists = [(last + 1 + j) % n + 1 for j in range(n)]     # one-hash lists, hash last + 1 the last
+        off, hsh = _csr([[x] for x in lists])
+        c_last = table[lists[-1]][1][1]
+        for t in (c_last - 1, c_last, c_last + 1):
+            if t < 1:
+                continue
+            seen.add(t)
+            rows = [[(b, c) for b, c in table[x] if c >= t] for x in lists]
+            exp = (np.concatenate([[0], np.cumsum([len(r) for r in rows])]).astype(np.uint64),
+                   np.array([b for r in rows for b, _ in r], dtype=np.uint32), np.array([c for r in rows for _, c in r], dtype=np.uint32))
+            for budget in (0, 2):
+                _budget(h, budget)
+                _same(h.list_share(off, hsh, t), exp, (last, t, budget))
+                info = h.seq_blocks_info
+                assert info["rows"] == len(exp[1]) and info["maxCount"] == (int(exp[2].max()) if len(exp[2]) else 0), (last, t, budget)
+                assert info["listEntries"] == 2 * sum(RUN_LENGTHS) and info["wideBatches"] == 0
+                if budget:
+                    assert info["windows"] >= 2 * n and info["batches"] >= 2 * n, info
+                else:
+                    assert (info["batches"], info["windows"]) == (1, 0), info
+    assert seen == {t for c in RUN_LENGTHS for t in (c - 1, c, c + 1) if t >= 1}
+    _budget(h, 0)
+    h.close()
+
+
 # ------------------------------------------------------------------------------------ the sequence layer
 def _check_sequences(h, m, seqs, thresholds, slabs):
     exp_h = m.seq_hashes(seqs)

@@ -163,6 +163,43 @@ def test_hand_made_state(tmp_path):
     h.close()
 
 
+def test_wide_keys(tmp_path):
+    """65540 blocks in one batch: keyBits(nBlocks) = 17 and keyBits(nq - 1) = 17, 34 bits, so the tail runs on 64-bit keys. Block b holds hashes b and
+    b + 1, so blocks b and b + 1 share hash b + 1 once; a block of DOUBLED holds hash b + 1 twice, which makes that count 2 in both rows. Hash X stands 60
+    times in block HEAVY and 30 times in block PARTNER: 1800 in both rows, and HEAVY's lists hold 5404 entries, above the budget of the second pass, so it
+    runs alone in windows while the other blocks run some 250 to a batch. The expected rows are stated here, not taken from the dense model."""
+    n, doubled, heavy, partner = 65540, (3, 1000, 32768, 65000), 20000, 50000
+    x = n + 2
+    blocks = [[b, b + 1] + [b + 1] * (b in doubled) for b in range(1, n + 1)]
+    blocks[heavy - 1] += [x] * 60
+    blocks[partner - 1] += [x] * 30
+    h = orc.load_image(tmp_path, blocks, 2, 100)
+    assert h.sizes()["nBlocks"] == n + 1 and (n + 1).bit_length() + (n - 1).bit_length() == 34
+    # every (row, block, count): neighbours b and b + 1 both ways, HEAVY and PARTNER both ways
+    b = np.arange(1, n, dtype=np.int64)
+    m = np.where(np.isin(b, doubled), 2, 1)
+    row = np.concatenate([b, b + 1, [heavy, partner]])
+    other = np.concatenate([b + 1, b, [partner, heavy]])
+    count = np.concatenate([m, m, [1800, 1800]])
+    order = np.lexsort((other, row))
+    row, other, count = row[order], other[order], count[order]
+    for budget in (0, 4000):
+        _budget(h, budget)
+        for t in (1, 2, 3):
+            keep = count >= t
+            off = np.concatenate([[0], np.cumsum(np.bincount(row[keep] - 1, minlength=n))]).astype(np.uint64)
+            _same(h.share_graph(t), (off, other[keep].astype(np.uint32), count[keep].astype(np.uint32)), (budget, t))
+            info = h.share_graph_info
+            assert info["rows"] == int(keep.sum()) == (2 * (n - 1) + 2, 2 * len(doubled) + 2, 2)[t - 1]
+            assert info["listEntries"] == int(count.sum()) and info["maxCount"] == 1800 and (info["codeMin"], info["codeMax"]) == (1, n + 1)
+            if budget:
+                assert info["windows"] >= 2 and info["batches"] > 60, info
+            else:
+                assert (info["batches"], info["windows"]) == (1, 0), info
+    _budget(h, 0)
+    h.close()
+
+
 # ------------------------------------------------------------------------------------ refusals
 def test_refusals(small):
     err = _hx().Hash10xError
