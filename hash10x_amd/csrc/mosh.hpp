@@ -1,11 +1,10 @@
 // mosh.hpp — the mosh set object shared by stage_g.hip (moshutils) and stage_h.hip (moshasm's readsets over a set)
 #pragma once
 #include "common.hpp"
+#include "seq_scan.hpp"
 
 namespace h10x {
 
-constexpr int MOSH_RUN = 64;                                 // k-mer start positions per lane
-constexpr int MOSH_X_SKIP = 23;                              // moshutils.c:43: barcode + spacer of the first read of a 10x pair
 constexpr u64 MOSH_SLAB_DEFAULT = (u64)1 << 26;              // bases per batch
 constexpr u64 RS_CHUNK_ENTRIES_DEFAULT = (u64)1 << 26;       // expanded (x, y) entries per chunk of queries of a readset's overlap table (stage_h.hip)
 constexpr u32 RS_CHUNK_READS_MAX = 65536;                    // queries per chunk: a read's place in its chunk travels in 16 bits
@@ -45,9 +44,10 @@ template <typename F> static int moshBatches(Mosh *m, const u64 *seqStart, u32 n
 int moshOpen(Mosh **out, int B, int k, int w, u64 factor1, u64 factor2, int device, char *err, int errlen);
 int moshAllocSet(Mosh *m, u32 size);
 int moshPlace(Mosh *m, u32 D);
+int moshFold(Mosh *m);                                       // depth = min(65535, depth + acc), acc = 0: the end of a batch of -a / -x and of a readset's -f
 
 // one uploaded batch and the list its scan left (stage_g.hip)
-struct MoshBatch { DevBuf<u8> codes; DevBuf<u64> seq, run, tallies, outHash; DevBuf<u32> outOrd; u64 nRuns = 0, total = 0, listed = 0, found = 0; };
+struct MoshBatch : SeqBatch { DevBuf<u64> tallies, outHash; DevBuf<u32> outOrd; u64 nRuns = 0, total = 0, listed = 0, found = 0; };
 // the scan of one batch with a hasher given as arguments, on the stream of any context: acc = null lists every mosh in b.outHash / b.outOrd (in no
 // order; b.listed of them), else the moshes found in c's table count in acc[accSize] and only the others are listed (stage_g.hip; stage_p.hip)
 int moshScanWith(Ctx *c, int k, int w, u64 factor1, int B, u32 *acc, u32 accSize, MoshBatch &b, const u8 *codes, const u64 *seqStart, u32 nSeq, int skipOdd,

@@ -4,46 +4,34 @@
 // sequence with the mosh iterator and updates crib[index] in order of appearance: the first occurrence sets
 // (chr, pos >> 10), the second turns chr into -1, every further one decrements it. Order-independent form:
 //   count[index] = occurrences,   first[index] = min (sequence number, position)   =>   chr = count == 1 ? seq : -(count - 1)
-// so one lane can own any run of k-mer positions: it rolls the forward and reverse-complement words over its run
-// (the same arithmetic as mosh_lds_kernel: seqhash.c:58-80,154-195), looks the moshes up in the probe table
-// (find only: hashIndexFind(hash, FALSE)) and posts count / first with atomics.
+// so one lane can own any run of k-mer positions: it walks its run (KmerRun and KmerRoll of seq_scan.hpp / seq_plan.hpp, the walk of all three
+// sequence scans), looks the moshes up in the probe table (find only: hashIndexFind(hash, FALSE)) and posts count / first with atomics.
 #include "common.hpp"
 #include "prim.hpp"
+#include "seq_scan.hpp"
 
 namespace h10x {
 
-constexpr int CRIB_RUN = 64;                               // k-mer start positions per lane
 enum { CRIB_ERR = 0, CRIB_HTA = 1, CRIB_HTB = 2, CRIB_HOM = 3, CRIB_MUL = 4 };   // hash10x.c:411-415
 
-// runStart[s] = number of runs in sequences before s; a sequence shorter than k has none (seqhash.c:162)
+// the one walk of seq_scan.hpp over the plan's runs (no ballot in here: a plain grid-stride loop); per mosh: count and the lowest (sequence, position)
 __global__ __launch_bounds__(256)
 void crib_scan_kernel(const u8 *__restrict__ codes, const u64 *__restrict__ seqStart, const u64 *__restrict__ runStart, u32 nSeq,
                       int k, int w, u64 factor1, const u32 *__restrict__ table, const u64 *__restrict__ hashValue, int B,
                       u32 *__restrict__ count, u64 *__restrict__ first, u64 *__restrict__ tallies /* present, absent */) {
   const u64 nRuns = runStart[nSeq];
-  const int shift1 = 64 - 2 * k, k2 = 2 * k;
-  const u64 mask = k2 == 64 ? ~0ULL : ((1ULL << k2) - 1);
   u64 present = 0, absent = 0;
   for (u64 run = (u64)blockIdx.x * blockDim.x + threadIdx.x; run < nRuns; run += (u64)gridDim.x * blockDim.x) {
-    u32 lo = 0, hi = nSeq;                                   // largest s with runStart[s] <= run
-    while (hi - lo > 1) { const u32 mid = (lo + hi) / 2; if (runStart[mid] <= run) lo = mid; else hi = mid; }
-    const u32 s = lo;
-    const u64 len = seqStart[s + 1] - seqStart[s];
-    const u64 p0 = (run - runStart[s]) * CRIB_RUN, nK = len - (u64)k + 1;
-    const int cnt = (int)(nK - p0 < (u64)CRIB_RUN ? nK - p0 : (u64)CRIB_RUN);
-    const u8 *b = codes + seqStart[s] + p0;
-    u64 f = 0, rc = 0;
-    for (int j = 0; j < k - 1; ++j) { const u64 x = b[j] & 3; f = (f << 2) | x; rc = (rc >> 2) | ((3 - x) << (k2 - 2)); }
-    for (int j = 0; j < cnt; ++j) {
-      const u64 x = b[k - 1 + j] & 3;
-      f = ((f << 2) | x) & mask; rc = (rc >> 2) | ((3 - x) << (k2 - 2));          // seqhash.c:72-76
-      const u64 hf = (f * factor1) >> shift1, hr = (rc * factor1) >> shift1;      // seqhash.c:58-59
-      const u64 h = hf < hr ? hf : hr;
+    const KmerRun r = KmerRun::open(codes, seqStart, runStart, nSeq, run, k, SeqSkip{0, 0});
+    KmerRoll roll(k, factor1);
+    roll.prime(r.b);
+    for (int j = 0; j < r.cnt; ++j) {
+      const u64 h = roll.next(r.b[k - 1 + j]);
       if (h % (u64)w) continue;
       const u32 ix = probe_find(table, hashValue, B, h);
       if (ix) {
         atomicAdd(&count[ix], 1u);
-        atomicMin(&first[ix], ((u64)(s + 1) << 32) | (u64)(u32)(p0 + j));
+        atomicMin(&first[ix], ((u64)(r.s + 1) << 32) | (u64)(u32)(r.p0 + j));
         ++present;
       } else ++absent;
     }
@@ -94,21 +82,12 @@ int stageD_cribGenome(Ctx *c, const u8 *hostCodes, const u64 *seqStart, u32 nSeq
   H10X_HIP(c, hipMemsetAsync(c->cribCount[which].p, 0, (size_t)U1 * 4, st));
   H10X_HIP(c, hipMemsetAsync(c->cribFirst[which].p, 0xFF, (size_t)U1 * 8, st));
   c->haveCrib = false;
-  std::vector<u64> runStart((size_t)nSeq + 1, 0);
-  for (u32 s = 0; s < nSeq; ++s) {
-    const u64 len = seqStart[s + 1] - seqStart[s];
-    runStart[s + 1] = runStart[s] + (len >= (u64)k ? (len - (u64)k + 1 + CRIB_RUN - 1) / CRIB_RUN : 0);
-  }
-  const u64 total = seqStart[nSeq], nRuns = runStart[nSeq];
-  DevBuf<u8> dCodes; DevBuf<u64> dSeq, dRun, tallies;
-  H10X_HIP(c, dCodes.alloc(total + 1)); H10X_HIP(c, dSeq.alloc((size_t)nSeq + 1)); H10X_HIP(c, dRun.alloc((size_t)nSeq + 1)); H10X_HIP(c, tallies.alloc(2));
-  if (total) H10X_HIP(c, hipMemcpyAsync(dCodes.p, hostCodes, total, hipMemcpyHostToDevice, st));
-  H10X_HIP(c, hipMemcpyAsync(dSeq.p, seqStart, ((size_t)nSeq + 1) * 8, hipMemcpyHostToDevice, st));
-  H10X_HIP(c, hipMemcpyAsync(dRun.p, runStart.data(), ((size_t)nSeq + 1) * 8, hipMemcpyHostToDevice, st));
-  H10X_HIP(c, hipMemsetAsync(tallies.p, 0, 16, st));
-  if (nRuns) {
-    const unsigned grid = (unsigned)hmin<u64>(divUp(nRuns, 256), (u64)c->numCU * 64);
-    crib_scan_kernel<<<grid, 256, 0, st>>>(dCodes.p, dSeq.p, dRun.p, nSeq, k, c->prm.w, c->prm.factor1, c->hashIndex.p, c->hashValue.p, c->prm.B,
+  const SeqPlan plan(seqStart, nSeq, k); StreamWait wait{st};   // (a genome is one batch of any size: positions are kept per sequence)
+  SeqBatch b; DevBuf<u64> tallies; H10X_HIP(c, tallies.alloc(2)); H10X_HIP(c, hipMemsetAsync(tallies.p, 0, 16, st));
+  if (plan.nRuns) {
+    H10X_TRY(b.upload(c, plan, hostCodes + seqStart[0]));
+    const unsigned grid = (unsigned)hmin<u64>(divUp(plan.nRuns, 256), (u64)c->numCU * 64);
+    crib_scan_kernel<<<grid, 256, 0, st>>>(b.codes.p, b.seq.p, b.run.p, nSeq, k, c->prm.w, c->prm.factor1, c->hashIndex.p, c->hashValue.p, c->prm.B,
                                           c->cribCount[which].p, c->cribFirst[which].p, tallies.p);
     H10X_HIP(c, hipGetLastError());
   }

@@ -8,9 +8,9 @@
 //      and nothing already placed moves ("Index build");
 //   3. depth = min(65535, depth + occurrences) (moshutils.c:26: ++depth, a wrap to 0 becomes 65535), so occurrences may
 //      be counted in any order.
-// -a / -x, per batch of whole sequences: scan (one lane per run of k-mer start positions, the rolling words of
-// crib_scan_kernel; a hit adds 1 to a 32-bit accumulator of its index, a miss appends (hash, ordinal) to a list whose
-// space is reserved once per wave step) -> sort the misses by hash -> per distinct hash its count and lowest ordinal
+// -a / -x, per batch of whole sequences: scan (one lane per run of k-mer start positions, the one walk of seq_scan.hpp;
+// a hit adds 1 to a 32-bit accumulator of its index, a miss appends (hash, ordinal) to a list whose space is reserved
+// once per wave step: wave_append) -> sort the misses by hash -> per distinct hash its count and lowest ordinal
 // -> sort those by ordinal -> index = max + 1 + rank -> insert -> fold the accumulators into depth[].
 #include "common.hpp"
 #include "prim.hpp"
@@ -20,10 +20,9 @@
 namespace h10x {
 
 // ------------------------------------------------------------------------------------------------ kernels
-// Sequence s of the batch: bases [seqStart[s], seqStart[s + 1]); with skipOdd the 1st, 3rd, ... sequence of the FILE
-// (seqBase = sequences before this batch) starts 23 bases in. runStart[s] = lane runs in the sequences before s.
+// The batch as its SeqPlan lays it out (seqStart = rel[], runStart; skipOdd and seqBase = its SeqSkip).
 // ADD = 0: every mosh goes to the list; ADD = 1: a mosh found in the table counts in acc[], the others go to the list.
-// Both loops have the same trip count in every lane of a wave: the ballots inside see all 64 lanes.
+// Both loops have the same trip count in every lane of a wave: the ballots of wave_append see all 64 lanes.
 template <int ADD>
 __global__ __launch_bounds__(256)
 void mosh_scan_kernel(const u8 *__restrict__ codes, const u64 *__restrict__ seqStart, const u64 *__restrict__ runStart, u32 nSeq,
@@ -31,33 +30,17 @@ void mosh_scan_kernel(const u8 *__restrict__ codes, const u64 *__restrict__ seqS
                       const u32 *__restrict__ table, const u64 *__restrict__ value, int B, u32 *__restrict__ acc,
                       u64 *__restrict__ outHash, u32 *__restrict__ outOrd, u64 cap, u64 *__restrict__ tallies /* listed, found */) {
   const u64 nRuns = runStart[nSeq];
-  const int shift1 = 64 - 2 * k, k2 = 2 * k;
-  const u64 mask = k2 == 64 ? ~0ULL : ((1ULL << k2) - 1);
   const u64 T = (u64)gridDim.x * blockDim.x, iters = (nRuns + T - 1) / T;
   const int lane = threadIdx.x & (WAVE - 1);
   u64 found = 0;
   for (u64 it = 0; it < iters; ++it) {
     const u64 run = it * T + (u64)blockIdx.x * blockDim.x + threadIdx.x;
-    const bool active = run < nRuns;
-    int cnt = 0; const u8 *b = codes; u64 ord0 = 0; u64 f = 0, rc = 0;
-    if (active) {
-      u32 lo = 0, hi = nSeq;                                 // largest s with runStart[s] <= run
-      while (hi - lo > 1) { const u32 mid = (lo + hi) / 2; if (runStart[mid] <= run) lo = mid; else hi = mid; }
-      const u32 s = lo;
-      const u64 off = (skipOdd && ((seqBase + s + 1) & 1)) ? MOSH_X_SKIP : 0;
-      const u64 len = seqStart[s + 1] - seqStart[s] - off;
-      const u64 p0 = (run - runStart[s]) * MOSH_RUN, nK = len - (u64)k + 1;
-      cnt = (int)(nK - p0 < (u64)MOSH_RUN ? nK - p0 : (u64)MOSH_RUN);
-      ord0 = seqStart[s] + off + p0; b = codes + ord0;
-      for (int j = 0; j < k - 1; ++j) { const u64 x = b[j] & 3; f = (f << 2) | x; rc = (rc >> 2) | ((3 - x) << (k2 - 2)); }
-    }
-    for (int j = 0; j < MOSH_RUN; ++j) {
+    KmerRun r = {0, 0, 0, 0, codes}; KmerRoll roll(k, factor1);   // (a lane beyond the last run walks nothing and takes part in the ballots)
+    if (run < nRuns) { r = KmerRun::open(codes, seqStart, runStart, nSeq, run, k, SeqSkip{skipOdd, seqBase}); roll.prime(r.b); }
+    for (int j = 0; j < SEQ_RUN; ++j) {
       bool emit = false; u64 h = 0;
-      if (j < cnt) {
-        const u64 x = b[k - 1 + j] & 3;
-        f = ((f << 2) | x) & mask; rc = (rc >> 2) | ((3 - x) << (k2 - 2));          // seqhash.c:72-76
-        const u64 hf = (f * factor1) >> shift1, hr = (rc * factor1) >> shift1;      // seqhash.c:58-59
-        h = hf < hr ? hf : hr;
+      if (j < r.cnt) {
+        h = roll.next(r.b[k - 1 + j]);
         if (h % (u64)w == 0) {
           if (ADD) {
             const u32 ix = probe_find(table, value, B, h);
@@ -65,17 +48,8 @@ void mosh_scan_kernel(const u8 *__restrict__ codes, const u64 *__restrict__ seqS
           } else emit = true;
         }
       }
-      const u64 m = __ballot(emit);
-      if (m) {                                               // one reservation per wave step
-        const int leader = __ffsll((long long)m) - 1;
-        u64 base = 0;
-        if (lane == leader) base = atomicAdd((unsigned long long *)&tallies[0], (unsigned long long)__popcll(m));
-        base = __shfl(base, leader);
-        if (emit) {
-          const u64 at = base + (u64)__popcll(m & (((u64)1 << lane) - 1));
-          if (at < cap) { outHash[at] = h; outOrd[at] = (u32)(ord0 + (u64)j); }
-        }
-      }
+      const u64 at = wave_append(emit, &tallies[0]);
+      if (emit && at < cap) { outHash[at] = h; outOrd[at] = (u32)(r.ord0 + (u64)j); }
     }
   }
   for (int o = 32; o; o >>= 1) found += __shfl_down(found, o);
@@ -124,7 +98,7 @@ __global__ void mosh_insert_kernel(const u64 *__restrict__ value, u32 first, u32
     }
   }
 }
-__global__ void mosh_fold_kernel(u16 *__restrict__ depth, u32 *__restrict__ acc, u32 n1) {
+__global__ void mosh_fold_kernel(u16 *__restrict__ depth, u32 *__restrict__ acc, u32 n1) {   // moshutils.c:26, moshasm.c:148: ++depth, a wrap to 0 becomes 65535
   const u64 i = (u64)blockIdx.x * blockDim.x + threadIdx.x;   // 64-bit: a set may hold up to 2^32 - 2 entries (B = 34)
   if (i == 0 || i >= n1) return;
   const u32 a = acc[i];
@@ -343,52 +317,34 @@ int moshPlace(Mosh *m, u32 D) {
 int moshScanWith(Ctx *c, int k, int w, u64 factor1, int B, u32 *acc, u32 accSize, MoshBatch &b, const u8 *codes, const u64 *seqStart, u32 nSeq, int skipOdd,
                  u64 seqBase) {
   hipStream_t st = c->stream; const bool add = acc != nullptr;
-  const u64 base = seqStart[0];
-  std::vector<u64> rel((size_t)nSeq + 1), runStart((size_t)nSeq + 1, 0);
-  struct SyncOnExit { hipStream_t s; ~SyncOnExit() { (void)hipStreamSynchronize(s); } } guard{st};   // every way out waits for the copies from the two vectors above
-  u64 nK = 0;
-  for (u32 s = 0; s <= nSeq; ++s) rel[s] = seqStart[s] - base;
-  for (u32 s = 0; s < nSeq; ++s) {
-    u64 len = rel[s + 1] - rel[s];
-    if (skipOdd && ((seqBase + s + 1) & 1)) {
-      if (len < (u64)MOSH_X_SKIP) return c->fail("10x sequence %llu has %llu bases: the first read of a pair needs at least %d", seqBase + s + 1, len, MOSH_X_SKIP);
-      len -= MOSH_X_SKIP;
-    }
-    const u64 n = len >= (u64)k ? len - (u64)k + 1 : 0;
-    nK += n; runStart[s + 1] = runStart[s] + (n + MOSH_RUN - 1) / MOSH_RUN;
-  }
-  b.total = rel[nSeq]; b.nRuns = runStart[nSeq]; b.listed = b.found = 0;
+  const SeqPlan plan(seqStart, nSeq, k, SeqSkip{skipOdd, seqBase}); StreamWait wait{st};
+  if (plan.tooShort < nSeq) return c->fail("10x sequence %llu has %llu bases: the first read of a pair needs at least %d", seqBase + plan.tooShort + 1, plan.len(plan.tooShort), MOSH_X_SKIP);
+  b.total = plan.total; b.nRuns = plan.nRuns; b.listed = b.found = 0;
   if (b.total > 0xFFFFFFFFull) return c->fail("a batch of %llu bases: at most 2^32 - 1 are supported per call", b.total);
   if (!b.nRuns) return 0;
-  H10X_HIP(c, b.codes.alloc(b.total + 1)); H10X_HIP(c, b.seq.alloc((size_t)nSeq + 1)); H10X_HIP(c, b.run.alloc((size_t)nSeq + 1)); H10X_HIP(c, b.tallies.alloc(2));
-  H10X_HIP(c, hipMemcpyAsync(b.codes.p, codes + base, b.total, hipMemcpyHostToDevice, st));
-  H10X_HIP(c, hipMemcpyAsync(b.seq.p, rel.data(), ((size_t)nSeq + 1) * 8, hipMemcpyHostToDevice, st));
-  H10X_HIP(c, hipMemcpyAsync(b.run.p, runStart.data(), ((size_t)nSeq + 1) * 8, hipMemcpyHostToDevice, st));
-  u64 cap = hmin<u64>(nK, 2 * (nK / (u64)w) + ((u64)1 << 16));
+  H10X_TRY(b.upload(c, plan, codes + seqStart[0])); H10X_HIP(c, b.tallies.alloc(2));
   const unsigned grid = (unsigned)hmin<u64>(divUp(b.nRuns, 256), (u64)c->numCU * 16);
-  for (int attempt = 0; attempt < 2; ++attempt) {
+  u64 ht[2] = {0, 0};
+  const int rc = seqScanTwice(c, plan.cap(w), b.tallies.p, ht, 2, "mosh scan: the list overflowed twice", [&](u64 cap) -> int {
     H10X_HIP(c, b.outHash.alloc(cap)); H10X_HIP(c, b.outOrd.alloc(cap));
     H10X_HIP(c, hipMemsetAsync(b.tallies.p, 0, 16, st));
     if (add) mosh_scan_kernel<1><<<grid, 256, 0, st>>>(b.codes.p, b.seq.p, b.run.p, nSeq, skipOdd, seqBase, k, w, factor1, c->hashIndex.p, c->hashValue.p, B,
                                                        acc, b.outHash.p, b.outOrd.p, cap, b.tallies.p);
     else mosh_scan_kernel<0><<<grid, 256, 0, st>>>(b.codes.p, b.seq.p, b.run.p, nSeq, skipOdd, seqBase, k, w, factor1, nullptr, nullptr, B,
                                                    nullptr, b.outHash.p, b.outOrd.p, cap, b.tallies.p);
-    H10X_HIP(c, hipGetLastError());
-    u64 ht[2];
-    H10X_HIP(c, hipMemcpyAsync(ht, b.tallies.p, 16, hipMemcpyDeviceToHost, st));
-    H10X_HIP(c, hipStreamSynchronize(st));                   // (the host vectors above are free to go from here)
-    b.listed = ht[0]; b.found = ht[1];
-    if (b.listed <= cap) return 0;
-    if (attempt) break;
-    cap = b.listed;                                          // the estimate was too small: once more with the exact size
-    ++c->scanRetries;
-    if (add) H10X_HIP(c, hipMemsetAsync(acc, 0, (size_t)accSize * 4, st));   // (acc[] is all zero between batches)
-  }
-  return c->fail("mosh scan: the list overflowed twice");
+    return 0;
+  }, [&]() -> int { if (add) H10X_HIP(c, hipMemsetAsync(acc, 0, (size_t)accSize * 4, st)); return 0; });   // (acc[] is all zero between batches)
+  b.listed = ht[0]; b.found = ht[1];
+  return rc;
 }
 
 static int moshScanBatch(Mosh *m, MoshBatch &b, const u8 *codes, const u64 *seqStart, u32 nSeq, int skipOdd, u64 seqBase, bool add) {
   return moshScanWith(&m->c, m->k, m->w, m->factor1, m->B, add ? m->acc.p : nullptr, m->size, b, codes, seqStart, nSeq, skipOdd, seqBase);
+}
+
+int moshFold(Mosh *m) {                                      // depth[] takes what the scans counted in acc[], which is all zero again
+  mosh_fold_kernel<<<divUp((u64)m->max + 1, 256), 256, 0, m->c.stream>>>(m->depth.p, m->acc.p, m->max + 1);
+  H10X_HIP(&m->c, hipGetLastError()); return 0;
 }
 
 // addSequence over a batch of whole sequences (moshutils.c:19-30, 41-45)
@@ -423,11 +379,8 @@ static int moshAddBatch(Mosh *m, const u8 *codes, const u64 *seqStart, u32 nSeq,
     H10X_HIP(c, hipGetLastError());
     H10X_TRY(moshPlace(m, D));
   }
-  if (b.nRuns) {
-    mosh_fold_kernel<<<divUp((u64)m->max + 1, 256), 256, 0, st>>>(m->depth.p, m->acc.p, m->max + 1);
-    H10X_HIP(c, hipGetLastError());
-  }
-  H10X_HIP(c, hipStreamSynchronize(st));                     // temporaries of this batch go back to the block cache behind finished work
+  if (b.nRuns) H10X_TRY(moshFold(m));
+  H10X_HIP(c, hipStreamSynchronize(st));                    // temporaries of this batch go back to the block cache behind finished work
   return 0;
 }
 
@@ -485,16 +438,15 @@ int stageG_scan(Mosh *m, const u8 *codes, const u64 *seqStart, u32 nSeq, int ski
     H10X_HIP(c, hipMemcpyAsync(hh.data(), sh.p, n * 8, hipMemcpyDeviceToHost, st));
     H10X_HIP(c, hipMemcpyAsync(oo.data(), so.p, n * 4, hipMemcpyDeviceToHost, st));
     H10X_HIP(c, hipStreamSynchronize(st));
-    const u64 base = seqStart[s0];
+    const u64 base = seqStart[s0]; const SeqSkip skip{skipOdd, seqBase + s0};
     u32 s = 0;
     for (u64 i = 0; i < n; ++i, ++done) {
       const u64 o = base + oo[i];
       while (seqStart[s0 + s + 1] <= o) ++s;
       if (done >= cap) continue;
-      const u64 off = (skipOdd && ((seqBase + s0 + s + 1) & 1)) ? MOSH_X_SKIP : 0;
       if (hash) hash[done] = hh[i];
       if (seq) seq[done] = s0 + s;
-      if (pos) pos[done] = (u32)(o - seqStart[s0 + s] - off);
+      if (pos) pos[done] = (u32)(o - seqStart[s0 + s] - skip.of(s));
     }
     return 0;
   });

@@ -48,57 +48,32 @@ struct ReadSet {
 };
 
 // ------------------------------------------------------------------------------------------------ kernels: build
-// mosh_scan_kernel<1> of stage_g.hip with the hit kept: a mosh found in the table goes to the list as (ordinal of its k-mer in the
-// batch, index | forward bit) and counts in acc[]; one that is not counts in nMiss of its sequence.
+// The walk of seq_scan.hpp over the plan's runs (uniform trip counts, as in mosh_scan_kernel of stage_g.hip: wave_append sees all 64 lanes). A mosh found in the
+// table goes to the list as (ordinal of its k-mer in the batch, index | forward bit) and counts in acc[]; one that is not counts in nMiss of its sequence.
 __global__ __launch_bounds__(256)
 void rs_scan_kernel(const u8 *__restrict__ codes, const u64 *__restrict__ seqStart, const u64 *__restrict__ runStart, u32 nSeq, int k, int w, u64 factor1,
                     const u32 *__restrict__ table, const u64 *__restrict__ value, int B, u32 *__restrict__ acc, u32 *__restrict__ nMiss,
                     u32 *__restrict__ outOrd, u32 *__restrict__ outHit, u64 cap, u64 *__restrict__ listed) {
   const u64 nRuns = runStart[nSeq];
-  const int shift1 = 64 - 2 * k, k2 = 2 * k;
-  const u64 mask = k2 == 64 ? ~0ULL : ((1ULL << k2) - 1);
   const u64 T = (u64)gridDim.x * blockDim.x, iters = (nRuns + T - 1) / T;
-  const int lane = threadIdx.x & (WAVE - 1);
-  for (u64 it = 0; it < iters; ++it) {                       // the same trip count in every lane: the ballots see all 64
+  for (u64 it = 0; it < iters; ++it) {
     const u64 run = it * T + (u64)blockIdx.x * blockDim.x + threadIdx.x;
-    const bool active = run < nRuns;
-    int cnt = 0; const u8 *b = codes; u64 ord0 = 0; u64 f = 0, rc = 0; u32 s = 0, miss = 0;
-    if (active) {
-      u32 lo = 0, hi = nSeq;                                 // largest s with runStart[s] <= run
-      while (hi - lo > 1) { const u32 mid = (lo + hi) / 2; if (runStart[mid] <= run) lo = mid; else hi = mid; }
-      s = lo;
-      const u64 len = seqStart[s + 1] - seqStart[s];
-      const u64 p0 = (run - runStart[s]) * MOSH_RUN, nK = len - (u64)k + 1;
-      cnt = (int)(nK - p0 < (u64)MOSH_RUN ? nK - p0 : (u64)MOSH_RUN);
-      ord0 = seqStart[s] + p0; b = codes + ord0;
-      for (int j = 0; j < k - 1; ++j) { const u64 x = b[j] & 3; f = (f << 2) | x; rc = (rc >> 2) | ((3 - x) << (k2 - 2)); }
-    }
-    for (int j = 0; j < MOSH_RUN; ++j) {
+    KmerRun r = {0, 0, 0, 0, codes}; KmerRoll roll(k, factor1); u32 miss = 0;
+    if (run < nRuns) { r = KmerRun::open(codes, seqStart, runStart, nSeq, run, k, SeqSkip{0, 0}); roll.prime(r.b); }
+    for (int j = 0; j < SEQ_RUN; ++j) {
       bool emit = false; u32 hv = 0;
-      if (j < cnt) {
-        const u64 x = b[k - 1 + j] & 3;
-        f = ((f << 2) | x) & mask; rc = (rc >> 2) | ((3 - x) << (k2 - 2));          // seqhash.c:72-76
-        const u64 hf = (f * factor1) >> shift1, hr = (rc * factor1) >> shift1;      // seqhash.c:58-59
-        const u64 h = hf < hr ? hf : hr;
+      if (j < r.cnt) {
+        const u64 h = roll.next(r.b[k - 1 + j]);
         if (h % (u64)w == 0) {
           const u32 ix = probe_find(table, value, B, h);
-          if (ix) { atomicAdd(&acc[ix], 1u); hv = hf < hr ? (ix | RS_TOP) : ix; emit = true; }   // seqhash.c:67: a tie is reverse
+          if (ix) { atomicAdd(&acc[ix], 1u); hv = roll.fwd() ? (ix | RS_TOP) : ix; emit = true; }
           else ++miss;
         }
       }
-      const u64 m = __ballot(emit);
-      if (m) {
-        const int leader = __ffsll((long long)m) - 1;
-        u64 base = 0;
-        if (lane == leader) base = atomicAdd((unsigned long long *)listed, (unsigned long long)__popcll(m));
-        base = __shfl(base, leader);
-        if (emit) {
-          const u64 at = base + (u64)__popcll(m & (((u64)1 << lane) - 1));
-          if (at < cap) { outOrd[at] = (u32)(ord0 + (u64)j); outHit[at] = hv; }
-        }
-      }
+      const u64 at = wave_append(emit, listed);
+      if (emit && at < cap) { outOrd[at] = (u32)(r.ord0 + (u64)j); outHit[at] = hv; }
     }
-    if (miss) atomicAdd(&nMiss[s], miss);
+    if (miss) atomicAdd(&nMiss[r.s], miss);
   }
 }
 // hits sorted by ordinal: dx = distance to the previous hit of the same sequence, the position itself for the first (moshasm.c:146)
@@ -106,18 +81,11 @@ __global__ void rs_dx_kernel(const u32 *__restrict__ ord, u64 n, const u64 *__re
   const u64 i = (u64)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
   const u64 o = ord[i];
-  u32 lo = 0, hi = nSeq;                                     // largest s with seqStart[s] <= o (an empty sequence never wins: the next one starts there too)
-  while (hi - lo > 1) { const u32 mid = (lo + hi) / 2; if (seqStart[mid] <= o) lo = mid; else hi = mid; }
-  const u64 s0 = seqStart[lo];
+  const u32 s = last_le(seqStart, nSeq, o);                  // (an empty sequence never wins: the next one starts there too)
+  const u64 s0 = seqStart[s];
   const u64 prev = (i > 0 && (u64)ord[i - 1] >= s0) ? (u64)ord[i - 1] - s0 : 0;
   dx[i] = (u16)(o - s0 - prev);
-  atomicAdd(&nHit[lo], 1u);
-}
-__global__ void rs_fold_kernel(u16 *__restrict__ depth, u32 *__restrict__ acc, u32 n1) {      // moshasm.c:148: ++depth, a wrap to 0 becomes 65535
-  const u64 i = (u64)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i == 0 || i >= n1) return;
-  const u32 a = acc[i];
-  if (a) { const u32 d = (u32)depth[i] + a; depth[i] = (u16)(d > 65535u || d < a ? 65535u : d); acc[i] = 0; }
+  atomicAdd(&nHit[s], 1u);
 }
 
 // ------------------------------------------------------------------------------------------------ kernels: index
@@ -309,50 +277,28 @@ static u32 rsGrowDim(u32 dim, u32 n) {                       // arrayExtend (arr
 
 static int rsAddBatch(ReadSet *rs, const u8 *codes, const u64 *seqStart, u32 nSeq) {
   Mosh *m = rs->m; Ctx *c = &m->c; hipStream_t st = c->stream; const int k = m->k; PrimTemp pt;
-  const u64 base = seqStart[0];
-  std::vector<u64> rel((size_t)nSeq + 1), runStart((size_t)nSeq + 1, 0);
-  struct SyncOnExit { hipStream_t s; ~SyncOnExit() { (void)hipStreamSynchronize(s); } } guard{st};
-  u64 nK = 0;
-  for (u32 s = 0; s <= nSeq; ++s) rel[s] = seqStart[s] - base;
-  for (u32 s = 0; s < nSeq; ++s) {
-    const u64 len = rel[s + 1] - rel[s];
-    if (len >= ((u64)1 << 31)) return c->fail("sequence of %llu bases: 2^31 or more are not supported", (unsigned long long)len);
-    const u64 n = len >= (u64)k ? len - (u64)k + 1 : 0;
-    nK += n; runStart[s + 1] = runStart[s] + (n + MOSH_RUN - 1) / MOSH_RUN;
-  }
-  const u64 total = rel[nSeq], nRuns = runStart[nSeq];
-  if (total > 0xFFFFFFFFull) return c->fail("a batch of %llu bases: at most 2^32 - 1 are supported per call", (unsigned long long)total);
+  const SeqPlan plan(seqStart, nSeq, k); StreamWait wait{st};
+  for (u32 s = 0; s < nSeq; ++s) if (plan.len(s) >= ((u64)1 << 31)) return c->fail("sequence of %llu bases: 2^31 or more are not supported", (unsigned long long)plan.len(s));
+  if (plan.total > 0xFFFFFFFFull) return c->fail("a batch of %llu bases: at most 2^32 - 1 are supported per call", plan.total);
   std::vector<u32> nHit(nSeq, 0), nMiss(nSeq, 0); std::vector<u32> hh; std::vector<u16> dd;
   u64 n = 0;
-  if (nRuns) {
-    DevBuf<u8> dCodes; DevBuf<u64> dSeq, dRun, dListed; DevBuf<u32> dMiss, dNHit, oOrd, oHit, sOrd, sHit; DevBuf<u16> dDx;
-    H10X_HIP(c, dCodes.alloc(total + 1)); H10X_HIP(c, dSeq.alloc((size_t)nSeq + 1)); H10X_HIP(c, dRun.alloc((size_t)nSeq + 1)); H10X_HIP(c, dListed.alloc(1));
-    H10X_HIP(c, dMiss.alloc(nSeq)); H10X_HIP(c, dNHit.alloc(nSeq));
-    H10X_HIP(c, hipMemcpyAsync(dCodes.p, codes + base, total, hipMemcpyHostToDevice, st));
-    H10X_HIP(c, hipMemcpyAsync(dSeq.p, rel.data(), ((size_t)nSeq + 1) * 8, hipMemcpyHostToDevice, st));
-    H10X_HIP(c, hipMemcpyAsync(dRun.p, runStart.data(), ((size_t)nSeq + 1) * 8, hipMemcpyHostToDevice, st));
-    u64 cap = hmin<u64>(nK, 2 * (nK / (u64)m->w) + ((u64)1 << 16));
-    const unsigned grid = (unsigned)hmin<u64>(divUp(nRuns, 256), (u64)c->numCU * 16);
-    for (int attempt = 0; ; ++attempt) {
+  if (plan.nRuns) {
+    SeqBatch b; DevBuf<u64> dListed; DevBuf<u32> dMiss, dNHit, oOrd, oHit, sOrd, sHit; DevBuf<u16> dDx;
+    H10X_TRY(b.upload(c, plan, codes + seqStart[0])); H10X_HIP(c, dListed.alloc(1)); H10X_HIP(c, dMiss.alloc(nSeq)); H10X_HIP(c, dNHit.alloc(nSeq));
+    const unsigned grid = (unsigned)hmin<u64>(divUp(plan.nRuns, 256), (u64)c->numCU * 16);
+    H10X_TRY(seqScanTwice(c, plan.cap(m->w), dListed.p, &n, 1, "readset scan: the list overflowed twice", [&](u64 cap) -> int {
       H10X_HIP(c, oOrd.alloc(cap)); H10X_HIP(c, oHit.alloc(cap));
       H10X_HIP(c, hipMemsetAsync(dListed.p, 0, 8, st)); H10X_HIP(c, hipMemsetAsync(dMiss.p, 0, (size_t)nSeq * 4, st));
-      rs_scan_kernel<<<grid, 256, 0, st>>>(dCodes.p, dSeq.p, dRun.p, nSeq, k, m->w, m->factor1, c->hashIndex.p, c->hashValue.p, m->B, m->acc.p, dMiss.p,
+      rs_scan_kernel<<<grid, 256, 0, st>>>(b.codes.p, b.seq.p, b.run.p, nSeq, k, m->w, m->factor1, c->hashIndex.p, c->hashValue.p, m->B, m->acc.p, dMiss.p,
                                            oOrd.p, oHit.p, cap, dListed.p);
-      H10X_HIP(c, hipGetLastError());
-      H10X_HIP(c, hipMemcpyAsync(&n, dListed.p, 8, hipMemcpyDeviceToHost, st));
-      H10X_HIP(c, hipStreamSynchronize(st));
-      if (n <= cap) break;
-      if (attempt) return c->fail("readset scan: the list overflowed twice");
-      cap = n;                                               // the estimate was too small: once more with the exact size
-      ++c->scanRetries;
-      H10X_HIP(c, hipMemsetAsync(m->acc.p, 0, (size_t)m->size * 4, st));                      // (acc[] is all zero between batches)
-    }
+      return 0;
+    }, [&]() -> int { H10X_HIP(c, hipMemsetAsync(m->acc.p, 0, (size_t)m->size * 4, st)); return 0; }));   // (acc[] is all zero between batches)
     H10X_HIP(c, hipMemcpyAsync(nMiss.data(), dMiss.p, (size_t)nSeq * 4, hipMemcpyDeviceToHost, st));
     if (n) {
       H10X_HIP(c, sOrd.alloc(n)); H10X_HIP(c, sHit.alloc(n)); H10X_HIP(c, dDx.alloc(n));
-      H10X_TRY(prim_sort_pairs_u32_u32(c, pt, oOrd.p, sOrd.p, oHit.p, sHit.p, n, 0, bitsFor(total)));
+      H10X_TRY(prim_sort_pairs_u32_u32(c, pt, oOrd.p, sOrd.p, oHit.p, sHit.p, n, 0, bitsFor(plan.total)));
       H10X_HIP(c, hipMemsetAsync(dNHit.p, 0, (size_t)nSeq * 4, st));
-      rs_dx_kernel<<<divUp(n, 256), 256, 0, st>>>(sOrd.p, n, dSeq.p, nSeq, dDx.p, dNHit.p);
+      rs_dx_kernel<<<divUp(n, 256), 256, 0, st>>>(sOrd.p, n, b.seq.p, nSeq, dDx.p, dNHit.p);
       H10X_HIP(c, hipGetLastError());
       hh.resize(n); dd.resize(n);
       H10X_HIP(c, hipMemcpyAsync(hh.data(), sHit.p, n * 4, hipMemcpyDeviceToHost, st));
@@ -366,13 +312,12 @@ static int rsAddBatch(ReadSet *rs, const u8 *codes, const u64 *seqStart, u32 nSe
   if (rs->totHit + n >= RS_TOP) return c->fail("readset of %llu hits: 2^31 or more are not supported", (unsigned long long)(rs->totHit + n));
   if ((u64)rs->reads.size() + nSeq >= RS_TOP) return c->fail("readset of 2^31 reads or more is not supported");
   if (n) {                                                   // only a batch that is taken counts in the set's depths (a refused one leaves acc[] to the caller's reset)
-    rs_fold_kernel<<<divUp((u64)m->max + 1, 256), 256, 0, st>>>(m->depth.p, m->acc.p, m->max + 1);
-    H10X_HIP(c, hipGetLastError());
+    H10X_TRY(moshFold(m));
     H10X_HIP(c, hipStreamSynchronize(st));
   }
   for (u32 s = 0; s < nSeq; ++s) {
     h10x_read_t r; memset(&r, 0, sizeof r);
-    r.len = (int32_t)(rel[s + 1] - rel[s]); r.nHit = (int32_t)nHit[s]; r.nMiss = (int32_t)nMiss[s];
+    r.len = (int32_t)plan.len(s); r.nHit = (int32_t)nHit[s]; r.nMiss = (int32_t)nMiss[s];
     const u32 ix = (u32)rs->reads.size();
     if (ix >= rs->dim) rs->dim = rsGrowDim(rs->dim, ix);
     rs->reads.push_back(r);

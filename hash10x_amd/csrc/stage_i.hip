@@ -43,8 +43,7 @@ __global__ void rm_hit_kernel(const u64 *__restrict__ hash, const u32 *__restric
   const u64 i = (u64)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
   const u64 o = ord[i];
-  u32 lo = 0, hi = nSeq;                                     // largest s with seqStart[s] <= o (an empty sequence never wins: the next one starts there too)
-  while (hi - lo > 1) { const u32 mid = (lo + hi) / 2; if (seqStart[mid] <= o) lo = mid; else hi = mid; }
+  const u32 lo = last_le(seqStart, nSeq, o);                 // (an empty sequence never wins: the next one starts there too)
   const u32 ix = probe_find(table, value, B, hash[i]);
   index[i] = ix; offset[i] = (u32)(o - seqStart[lo]); id[i] = idBase + lo;
   if (ix) atomicAdd(&depth[ix], 1u); else *absent = 1;
@@ -88,8 +87,7 @@ __global__ void rm_seed_kernel(const u64 *__restrict__ hash, const u32 *__restri
   const u64 i = (u64)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
   const u64 o = ord[i];
-  u32 lo = 0, hi = nSeq;
-  while (hi - lo > 1) { const u32 mid = (lo + hi) / 2; if (seqStart[mid] <= o) lo = mid; else hi = mid; }
+  const u32 lo = last_le(seqStart, nSeq, o);
   pos[i] = (u32)(o - seqStart[lo]);
   h10x_mapseed_t r = {0, 0, 0, 0};
   const u32 ix = probe_find(table, value, B, hash[i]);

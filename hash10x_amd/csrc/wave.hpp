@@ -1,5 +1,5 @@
-// wave.hpp — device helpers of the census family (stage_f / stage_l / stage_m / stage_n / stage_p / stage_q, census_rows): wave and workgroup folds, searches in ascending
-// arrays, the window of a barcode list and the compaction step. No kernels here. Everything is wave-uniform where it says so: call it from
+// wave.hpp — device helpers of the census family (stage_f / stage_l / stage_m / stage_n / stage_p / stage_q, census_rows) and the sequence scans (seq_scan.hpp): wave and
+// workgroup folds, searches in ascending arrays, the window of a barcode list, the compaction step and the list append. No kernels here. Everything is wave-uniform where it says so: call it from
 // code that every lane of the wave reaches.
 #pragma once
 #include "common.hpp"
@@ -69,6 +69,15 @@ __device__ __forceinline__ P wave_place(bool keep, P &p0) {
   const P p = p0 + (P)__popcll(m & ((1ull << (threadIdx.x & (WAVE - 1))) - 1));
   p0 += (P)__popcll(m);
   return p;
+}
+// The slot of this lane's item in a list that grows behind *counter: one reservation per wave step, made by the lowest lane that emits. EVERY lane of
+// the wave must reach it (the ballot and the shuffle are over all 64); what a lane without an item gets means nothing
+__device__ __forceinline__ u64 wave_append(bool emit, u64 *counter) {
+  const u64 m = __ballot(emit);
+  if (!m) return 0;
+  const int lane = threadIdx.x & (WAVE - 1), leader = __ffsll((long long)m) - 1;
+  const u64 base = lane == leader ? atomicAdd((unsigned long long *)counter, (unsigned long long)__popcll(m)) : 0;
+  return __shfl(base, leader) + (u64)__popcll(m & (((u64)1 << lane) - 1));
 }
 
 }  // namespace h10x

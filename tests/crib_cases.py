@@ -22,7 +22,7 @@ import crib_model as cm
 import orc
 
 K, B = 21, 20
-RUN = 64                                                     # CRIB_RUN of stage_d.hip: k-mer starts per lane
+RUN = 64                                                     # SEQ_RUN of csrc/seq_plan.hpp: k-mer starts per lane
 REP_THREADS = 256                                            # stage_e.hip: threads of cluster_report_kernel
 LO, HI = 1, 100000                                           # --hashDepthRange of every case: every hash a record holds is good
 
