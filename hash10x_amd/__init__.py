@@ -265,6 +265,12 @@ def load_native():
     hip.h10x_row_links_get_device.argtypes = [vp, vp, vp, vp, cu64]
     hip.h10x_row_links_get_range.argtypes = [vp, cu64, cu64, vp, vp]
     host.h10x_session_seqLinks.argtypes = [vp, ci, ci, ci, ci, cs, cs, vp, ci]
+    # sequence spans (csrc/stage_r.hip)
+    hip.h10x_seq_spans_run.argtypes = [vp, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, vp, vp, ctypes.c_uint32, vp, vp]
+    hip.h10x_seq_spans_get.argtypes = [vp, vp, vp, vp, vp, vp, cu64]
+    hip.h10x_seq_spans_get_range.argtypes = [vp, cu64, cu64, vp, vp, vp, vp]
+    hip.h10x_seq_spans_cover_get.argtypes = [vp, vp, vp, cu64]
+    host.h10x_session_seqSpans.argtypes = [vp, ci, ci, ci, ci, cs, cs, vp, ci]
     # mosh sets (csrc/stage_g.hip, host/mosh_host.c)
     pvp, ci32, cu32 = ctypes.POINTER(vp), ctypes.c_int32, ctypes.c_uint32
     hip.h10x_factors_from_seed.restype = None; hip.h10x_factors_from_seed.argtypes = [ci32, ctypes.POINTER(cu64), ctypes.POINTER(cu64)]
@@ -1225,6 +1231,35 @@ class Hash10x:
         the file `out`."""
         self._with_file(out, lambda f: self._host.h10x_session_seqBlocks(self._s, int(min_share), os.fsencode(seqfile), os.fsencode(path), f, 1 if verbose else 0))
 
+    # ---- sequence spans (h10x_seq_spans_*, csrc/stage_r.hip) ----
+    def seq_spans(self, seqs, min_share, max_gap=0, window=0):
+        """Per sequence the extents of the blocks on it: the hits of a block (one per entry of the barcode list of every in-range mosh occurrence,
+        at the occurrence's position) cut where they lie more than max_gap apart (0: never), kept at min_share hits, ascending by (block, first);
+        and for window >= 1 the number of kept extents that span each multiple of window inside the sequence. Returns (offsets uint64[n + 1],
+        block, first, last, hits uint32[], cover_offsets uint64[n + 1], cover uint32[]). The figures of the run are kept in self.seq_spans_info,
+        the per-sequence ones (len, moshes, found, inRange, extents) as its entry "figures"."""
+        ctx = self._seq_ctx("seqSpans")
+        codes, start = self._flatten_seqs(seqs)
+        n = len(start) - 1
+        fig = np.zeros(max(n, 1), dtype=_SEQ_SPAN_FIGURES); z = np.zeros(1, dtype=_SEQ_SPANS_INFO)
+        self._chk_ctx(self._hip.h10x_seq_spans_run(ctx, int(min_share), int(max_gap), int(window), codes.ctypes.data, start.ctypes.data, n, fig.ctypes.data, z.ctypes.data))
+        self.seq_spans_info = {k: int(z[k][0]) for k in _SEQ_SPANS_INFO.names if k != "reserved"}
+        self.seq_spans_info["figures"] = fig[:n].copy()
+        m, nb = self.seq_spans_info["extents"], self.seq_spans_info["boundaries"]
+        off, coff = np.zeros(n + 1, dtype=np.uint64), np.zeros(n + 1, dtype=np.uint64)
+        cols = [np.zeros(max(m, 1), dtype=np.uint32) for _ in range(4)]
+        cover = np.zeros(max(nb, 1), dtype=np.uint32)
+        self._chk_ctx(self._hip.h10x_seq_spans_get(ctx, off.ctypes.data, *[c.ctypes.data for c in cols], m))
+        self._chk_ctx(self._hip.h10x_seq_spans_cover_get(ctx, coff.ctypes.data, cover.ctypes.data, nb))
+        return (off,) + tuple(c[:m] for c in cols) + (coff, cover[:nb])
+
+    def write_seq_spans(self, min_share, max_gap, window, min_cover, seqfile, path, out=None, verbose=False):
+        """--seqSpans <min_share> <max_gap> <window> <min_cover> <seqfile> <path>: the extents and the spanning coverage of every sequence of a
+        FASTA / FASTQ file (gzip or plain) written slab by slab as a .ss file (read_seq_spans reads it); one line of counts, and with verbose
+        one SEQ_SPANS line per sequence and one SEQ_WEAK line per run of boundaries below min_cover, are appended to the file `out`."""
+        self._with_file(out, lambda f: self._host.h10x_session_seqSpans(self._s, int(min_share), int(max_gap), int(window), int(min_cover), os.fsencode(seqfile),
+                                                                        os.fsencode(path), f, 1 if verbose else 0))
+
     # ---- row links (h10x_row_links_*, csrc/stage_q.hip) ----
     def _row_links_ctx(self, cmd):
         """the session's context (it comes with the first state; the row layer itself reads none)"""
@@ -1306,6 +1341,9 @@ _LIST_SHARE_INFO = np.dtype([("rows", "<u8"), ("listEntries", "<u8"), ("listHash
                              ("wideBatches", "<u4"), ("nBlocks", "<u4"), ("lists", "<u4")])
 _ROW_LINKS_INFO = np.dtype([("lists", "<u8"), ("rowEntries", "<u8"), ("blocksUsed", "<u8"), ("skippedBlocks", "<u8"), ("pairs", "<u8"), ("links", "<u8"),
                             ("maxShared", "<u4"), ("batches", "<u4"), ("windows", "<u4"), ("wideBatches", "<u4")])
+_SEQ_SPAN_FIGURES = np.dtype([("len", "<u8"), ("moshes", "<u4"), ("found", "<u4"), ("inRange", "<u4"), ("extents", "<u4")])
+_SEQ_SPANS_INFO = np.dtype([(k, "<u8") for k in ("sequences", "bases", "moshes", "found", "inRange", "hits", "extentsAll", "extents", "sumSpan", "boundaries")] +
+                           [(k, "<u4") for k in ("maxHits", "maxSpan", "batches", "windows", "nBlocks", "reserved")])
 _SEQ_CODE = np.zeros(256, dtype=np.uint8)
 for _i, _c in enumerate("ACGT"):
     _SEQ_CODE[ord(_c)] = _SEQ_CODE[ord(_c.lower())] = _i
@@ -1382,6 +1420,73 @@ def read_seq_blocks(path):
     names = [blob[int(a):int(b) - 1].decode(errors="replace") for a, b in zip(name_off[:-1], name_off[1:])]
     info = {"version": version, "nBlocks": n_blocks, "minShare": min_share, "nSeq": n_seq, "rows": rows, "nameBytes": name_bytes}
     return info, off, blk, cnt, table, names
+
+
+_SS_RECORD = np.dtype([("len", "<u8"), ("moshes", "<u4"), ("found", "<u4"), ("inRange", "<u4"), ("weak", "<u4")])
+
+
+def read_seq_spans(path):
+    """A --seqSpans file (magic "10XE", u32 version 1, u32 nBlocks, u32 minShare, u32 maxGap, u32 window, u32 minCover, u32 0, u64 nSeq, u64 extents,
+    u64 boundaries, u64 nameBytes; extents records {u32 block, u32 first, u32 last, u32 hits}; nSeq records {u64 len, u32 moshes, u32 found, u32
+    inRange, u32 weak}; nSeq + 1 u64 offsets; nSeq + 1 u64 cover offsets; boundaries u32 cover; nSeq + 1 u64 name offsets; the names, NUL-terminated;
+    little-endian; needs no device): (info, offsets, block, first, last, hits, cover_offsets, cover, table, names). Raises Hash10xError for a file
+    that is not one or does not hold together: magic and version, the file's length, the offsets ascending to `extents`, the cover offsets against
+    (len - 1) // window, first <= last < len, blocks below nBlocks, rows ascending by (block, first), hits >= minShare, weak against cover and
+    minCover, the names."""
+    with open(path, "rb") as f:
+        data = f.read()
+    if len(data) < 64 or data[:4] != b"10XE":
+        raise Hash10xError("%s: not a seq spans file (magic 10XE)" % path)
+    version, n_blocks, min_share, max_gap, window, min_cover, zero = (int(v) for v in np.frombuffer(data, dtype="<u4", count=7, offset=4))
+    n_seq, extents, boundaries, name_bytes = (int(v) for v in np.frombuffer(data, dtype="<u8", count=4, offset=32))
+    if version != 1:
+        raise Hash10xError("%s: seq spans version %d, this reader knows 1" % (path, version))
+    need = 64 + 16 * extents + 24 * n_seq + 24 * (n_seq + 1) + 4 * boundaries + name_bytes
+    if len(data) != need:
+        raise Hash10xError("%s: %d bytes, %d sequences, %d extents, %d boundaries and %d name bytes need %d" % (path, len(data), n_seq, extents, boundaries, name_bytes, need))
+    if zero:
+        raise Hash10xError("%s: the reserved word of the header is not 0" % path)
+    at = 64
+    quad = np.frombuffer(data, dtype="<u4", count=4 * extents, offset=at).reshape(-1, 4); at += 16 * extents
+    table = np.frombuffer(data, dtype=_SS_RECORD, count=n_seq, offset=at).copy(); at += 24 * n_seq
+    off = np.frombuffer(data, dtype="<u8", count=n_seq + 1, offset=at).copy(); at += 8 * (n_seq + 1)
+    coff = np.frombuffer(data, dtype="<u8", count=n_seq + 1, offset=at).copy(); at += 8 * (n_seq + 1)
+    cover = np.frombuffer(data, dtype="<u4", count=boundaries, offset=at).copy(); at += 4 * boundaries
+    name_off = np.frombuffer(data, dtype="<u8", count=n_seq + 1, offset=at).copy(); at += 8 * (n_seq + 1)
+    blob = data[at:]
+    if off[0] != 0 or int(off[-1]) != extents or np.any(off[1:] < off[:-1]):
+        raise Hash10xError("%s: the offsets do not ascend from 0 to the %d extents" % (path, extents))
+    lens = table["len"].astype(np.int64)
+    exp = np.zeros(n_seq + 1, dtype=np.uint64)
+    if window:
+        exp[1:] = np.cumsum(np.where(lens > 0, (lens - 1) // window, 0))
+    if not np.array_equal(coff, exp) or int(coff[-1]) != boundaries:
+        raise Hash10xError("%s: the cover offsets are not those of the lengths at window %d" % (path, window))
+    if name_off[0] != 0 or int(name_off[-1]) != name_bytes or np.any(name_off[1:] <= name_off[:-1]):
+        raise Hash10xError("%s: the name offsets do not ascend from 0 to the %d name bytes" % (path, name_bytes))
+    if any(blob[int(e) - 1] != 0 for e in name_off[1:]):
+        raise Hash10xError("%s: a name does not end in NUL" % path)
+    blk, first, last, hits = (quad[:, i].copy() for i in range(4))
+    if extents:
+        row_len = np.repeat(lens, np.diff(off.astype(np.int64)))
+        if np.any(first > last) or np.any(last.astype(np.int64) >= row_len):
+            raise Hash10xError("%s: an extent does not lie in its sequence (first <= last < len)" % path)
+        if int(blk.max()) >= n_blocks:
+            raise Hash10xError("%s: an extent's block is beyond the %d blocks" % (path, n_blocks))
+        if int(hits.min()) < max(min_share, 1):
+            raise Hash10xError("%s: an extent's hits are below minShare %d" % (path, min_share))
+        inner = np.ones(extents, dtype=bool)
+        inner[off[:-1][off[:-1] < extents].astype(np.int64)] = False   # the first extent of a row has no predecessor in it
+        key = blk.astype(np.uint64) << np.uint64(32) | first.astype(np.uint64)
+        if np.any(inner[1:] & (key[1:] <= key[:-1])):
+            raise Hash10xError("%s: the extents of a row do not ascend by (block, first)" % path)
+    weak = np.add.reduceat(np.r_[(cover < min_cover).astype(np.int64), 0], coff[:-1].astype(np.int64)) * (np.diff(coff.astype(np.int64)) > 0) if n_seq else np.zeros(0, np.int64)
+    if not np.array_equal(weak, table["weak"].astype(np.int64)):
+        raise Hash10xError("%s: a sequence's weak count is not that of its cover at minCover %d" % (path, min_cover))
+    names = [blob[int(a):int(b) - 1].decode(errors="replace") for a, b in zip(name_off[:-1], name_off[1:])]
+    info = {"version": version, "nBlocks": n_blocks, "minShare": min_share, "maxGap": max_gap, "window": window, "minCover": min_cover, "nSeq": n_seq,
+            "extents": extents, "boundaries": boundaries, "nameBytes": name_bytes}
+    return info, off, blk, first, last, hits, coff, cover, table, names
 
 
 _SL_RECORD = np.dtype([("len", "<u8"), ("headRows", "<u4"), ("tailRows", "<u4")])

@@ -291,6 +291,9 @@ struct Ctx {
   // of list e. Both kept until the next begin, a new depth range, --clusterSplit or a new state
   DevBuf<u64> rqKeys; u64 rqEntries = 0, rqLists = 0; u32 rqBlocks = 0; bool rqOpen = false;
   KeptRows rl;
+  // sequence spans (stage_r.hip). The kept extents of the last h10x_seq_spans_run in row order, four columns of ssExtents entries, and the spanning coverage,
+  // ssBoundaries entries; the offsets of both per sequence on the host. Kept until the next run, a new depth range, --clusterSplit or a new state
+  DevBuf<u32> ssBlock, ssFirst, ssLast, ssHits, ssCover; std::vector<u64> ssHostOff, ssHostCoverOff; u64 ssExtents = 0, ssBoundaries = 0; u32 ssSeqs = 0; bool haveSeqSpans = false;
   int64_t optSeqSlab = 0;     // bases per device batch of the sequence layer (0 = the mosh sets' default, 2^26); results do not depend on it
   // the -r value prm.factor1 was drawn from (option "seqhash_seed"): a mosh set made from the state carries the hasher's second multiplier too (stage_o.hip)
   int32_t seed = 0; bool haveSeed = false;
@@ -584,6 +587,13 @@ int stageP_listShare(Ctx *c, int64_t minShare, const u64 *offsets, const u32 *ha
 int stageP_seqBlocks(Ctx *c, int64_t minShare, const u8 *codes, const u64 *seqStart, u32 nSeq, h10x_seq_figures *fig, h10x_list_share_info *info);
 int stageP_get(Ctx *c, u64 *offsets, u32 *block, u32 *count, u64 cap, int toDevice);
 void stageP_release(Ctx *c);
+int sp_check(Ctx *c, const char *cmd, int64_t minShare, bool hasher);   // the refusals of the sequence commands: ce_check, no range and, with hasher, the seed's
+// sequence spans (stage_r.hip): each block's extents on a sequence and the number of extents that span each window boundary
+int stageR_run(Ctx *c, int64_t minShare, int64_t maxGap, int64_t window, const u8 *codes, const u64 *seqStart, u32 nSeq, h10x_seq_span_figures *fig, h10x_seq_spans_info *info);
+int stageR_get(Ctx *c, u64 *offsets, u32 *block, u32 *first, u32 *last, u32 *hits, u64 cap);
+int stageR_getRange(Ctx *c, u64 firstRow, u64 count, u32 *block, u32 *first, u32 *last, u32 *hits);
+int stageR_coverGet(Ctx *c, u64 *coverOffsets, u32 *cover, u64 cap);
+void stageR_release(Ctx *c);
 // row links (stage_q.hip): lists of block numbers accumulated on the device, and the pairs of lists that share blocks
 int stageQ_begin(Ctx *c, u32 nBlocks);
 int stageQ_add(Ctx *c, const u64 *offsets, const u32 *block, u64 nLists);

@@ -240,7 +240,7 @@ const char *h10x_last_error(const h10x_ctx *h) { return h ? h->c.err.c_str() : "
 
 static void reset_state(Ctx &c) {
   c.haveState = false; c.haveRange = false; c.haveGood = false; c.goodFiguresPending = false; c.rangeMin = c.rangeMax = 0; c.depthBound = 0xFFFFFFFFu; c.rangeHiMax = 0;
-  release_share_results(&c); stageP_release(&c); stageQ_release(&c);
+  release_share_results(&c); stageP_release(&c); stageQ_release(&c); stageR_release(&c);
   c.within.release(); c.goodPos.release(); c.nGood.release(); c.goodEntries.release(); c.goodRow.release();
   // the tables of the state being replaced go back to the block cache NOW, not when their successors are swapped in: the second --readFQB of a
   // context then finds every block of the first one parked and allocates nothing (kept until the swap, rows[] and clusHash had no twin in the
@@ -414,6 +414,7 @@ int h10x_depth_range(h10x_ctx *h, int32_t lo, int32_t hi) {
   release_share_results(&h->c);   // a kept share graph, kept components and kept hash copies are of the lists this call replaces
   stageP_release(&h->c);          // (so are the query lists and rows of sequences)
   stageQ_release(&h->c);          // (and the row links made of them)
+  stageR_release(&h->c);          // (and the extents of sequences)
   return stageC_depthRange(&h->c, lo, hi);
 }
 
@@ -427,7 +428,7 @@ int h10x_cluster_split(h10x_ctx *h) {
   if (!h) return -1;
   H10X_TRY(enter(h->c));
   release_share_results(&h->c);   // (and of the blocks this call renumbers)
-  stageP_release(&h->c); stageQ_release(&h->c);
+  stageP_release(&h->c); stageQ_release(&h->c); stageR_release(&h->c);
   return stageC_split(&h->c);
 }
 
@@ -748,6 +749,21 @@ int h10x_row_links_get_device(h10x_ctx *h, uint64_t *devOffsets, uint32_t *devOt
 }
 int h10x_row_links_get_range(h10x_ctx *h, uint64_t first, uint64_t count, uint32_t *other, uint32_t *shared) {
   if (!h) return -1; H10X_TRY(enter(h->c)); return stageQ_getRange(&h->c, first, count, other, shared);
+}
+
+// ---- sequence spans (stage_r.hip) ----
+int h10x_seq_spans_run(h10x_ctx *h, int64_t minShare, int64_t maxGap, int64_t window, const uint8_t *codes, const uint64_t *seqStart, uint32_t nSeq,
+                       h10x_seq_span_figures *figures, h10x_seq_spans_info *info) {
+  if (!h || !info) return -1; H10X_TRY(enter(h->c)); return stageR_run(&h->c, minShare, maxGap, window, codes, (const u64 *)seqStart, nSeq, figures, info);
+}
+int h10x_seq_spans_get(h10x_ctx *h, uint64_t *offsets, uint32_t *block, uint32_t *first, uint32_t *last, uint32_t *hits, uint64_t cap) {
+  if (!h) return -1; H10X_TRY(enter(h->c)); return stageR_get(&h->c, (u64 *)offsets, block, first, last, hits, cap);
+}
+int h10x_seq_spans_get_range(h10x_ctx *h, uint64_t firstRow, uint64_t count, uint32_t *block, uint32_t *first, uint32_t *last, uint32_t *hits) {
+  if (!h) return -1; H10X_TRY(enter(h->c)); return stageR_getRange(&h->c, firstRow, count, block, first, last, hits);
+}
+int h10x_seq_spans_cover_get(h10x_ctx *h, uint64_t *coverOffsets, uint32_t *cover, uint64_t cap) {
+  if (!h) return -1; H10X_TRY(enter(h->c)); return stageR_coverGet(&h->c, (u64 *)coverOffsets, cover, cap);
 }
 
 int h10x_timing_enable(h10x_ctx *h, int on) { if (!h) return -1; h->c.timing = on != 0; return 0; }

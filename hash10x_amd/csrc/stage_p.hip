@@ -80,14 +80,7 @@ __global__ __launch_bounds__(256) void sp_figures_kernel(const u64 *__restrict__
 }
 
 // ------------------------------------------------------------------------------------------------ layer 2
-// entries [a, b) of hash x's barcode list with block in [lo, hi); full = the window covers every block
-__device__ __forceinline__ void sp_window(const u32 *__restrict__ rows, const u64 *__restrict__ rowStart, const u32 *__restrict__ hashDepth, u32 x, u32 lo, u32 hi,
-                                          bool full, u64 &a, u64 &b) {
-  a = rowStart[x]; b = a + hashDepth[x];
-  if (full) return;
-  a = lower_bound(rows, a, b, lo); b = lower_bound(rows, a, b, hi);
-}
-
+// (sp_window, the entries of a hash's barcode list in the window: wave.hpp)
 // one wave per list q0 + q: size[q] = entries of its hashes' lists in the window
 __global__ void sp_size_kernel(u32 nq, const u64 *__restrict__ qOff /* at q0 */, const u32 *__restrict__ qHash, const u64 *__restrict__ rowStart,
                                const u32 *__restrict__ hashDepth, const u32 *__restrict__ rows, u32 lo, u32 hi, int full, u64 *__restrict__ size) {
@@ -131,9 +124,7 @@ __global__ __launch_bounds__(256) void sp_gather_kernel(u32 nq, const u64 *__res
 }
 
 // ------------------------------------------------------------------------------------------------ drivers
-namespace {
-
-// the refusals both layers share; the hasher's seed as h10x_mosh_from_state takes it
+// the refusals both layers share (and stage_r.hip); the hasher's seed as h10x_mosh_from_state takes it
 int sp_check(Ctx *c, const char *cmd, int64_t minShare, bool hasher) {
   H10X_TRY(ce_check(c, cmd, minShare));
   if (!c->haveRange) return c->fail("!! you must set hashDepthRange before %s", cmd);
@@ -143,6 +134,8 @@ int sp_check(Ctx *c, const char *cmd, int64_t minShare, bool hasher) {
   if (f1 != c->prm.factor1) return c->fail("%s: option seqhash_seed %d does not give the context's hash multiplier", cmd, c->seed);
   return 0;
 }
+
+namespace {
 
 void release_lists(Ctx *c) { c->haveSeqHashes = false; c->sqSeqs = 0; c->sqEntries = 0; c->sqHash.release(); c->sqOffsets.release(); c->sqHostOff.clear(); }
 

@@ -53,6 +53,14 @@ __device__ __forceinline__ void list_window(const u32 *__restrict__ rows, u64 d,
   a = lower_bound(rows, a, b, lo); b = lower_bound(rows, a, b, hi);
 }
 
+// entries [a, b) of hash x's barcode list (rowStart / hashDepth, unsharded) with block in [lo, hi); full = the window covers every block (stage_p.hip, stage_r.hip)
+__device__ __forceinline__ void sp_window(const u32 *__restrict__ rows, const u64 *__restrict__ rowStart, const u32 *__restrict__ hashDepth, u32 x, u32 lo, u32 hi,
+                                          bool full, u64 &a, u64 &b) {
+  a = rowStart[x]; b = a + hashDepth[x];
+  if (full) return;
+  a = lower_bound(rows, a, b, lo); b = lower_bound(rows, a, b, hi);
+}
+
 // entries of block `code`'s good lists in the window, over the whole wave (wave-uniform; every lane gets the sum); n = its good ranks
 __device__ __forceinline__ u64 good_list_entries(u32 code, const u32 *__restrict__ nGood, const u64 *__restrict__ blockOff, const u64 *__restrict__ goodRow,
                                                  const u32 *__restrict__ rows, u32 rowShift, u32 lo, u32 hi, bool full, u32 &n) {

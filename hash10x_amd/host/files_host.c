@@ -257,6 +257,79 @@ done:
   return rc;
 }
 
+/* ---- .ss: --seqSpans. As .sb: the extents of each slab go to the file as they come; the per-sequence table, the offsets, the coverage (4 bytes per boundary)
+   and the names are kept on the host and written at the end, with the header. The weak boundaries are found here, from cover[]. ---- */
+int h10x_host_write_seq_spans(const char *path, const h10x_seq_spans_head *hd, h10x_seq_spans_slab_fn next, void *user, FILE *verbose,
+                              h10x_seq_spans_totals *totals, char *err, int errlen) {
+  typedef struct { uint64_t len; uint32_t moshes, found, inRange, weak; } Rec;
+  h10x_seq_spans_totals t; memset(&t, 0, sizeof t);
+  Rec *table = 0; uint64_t *offsets = 0, *coverOff = 0; uint32_t *quad = 0, *cover = 0; NameTable names; memset(&names, 0, sizeof names);
+  size_t capTable = 0, capOff = 0, capCoverOff = 0, capQuad = 0, capCover = 0;
+  OutFile o; unsigned char head[64]; memset(head, 0, sizeof head);
+  if (h10x_out_open(&o, path, err, errlen)) return -1;
+  int rc = h10x_out_write(&o, head, 1, sizeof head);
+  while (!rc) {
+    h10x_seq_spans_slab b; memset(&b, 0, sizeof b);
+    const int got = next(user, &b);
+    if (got < 0) { rc = -2; break; }                                  /* the callback's own error stands */
+    if (!got) break;
+    const uint64_t rows = b.nSeq ? b.rowOff[b.nSeq] : 0, bounds = b.nSeq ? b.coverOff[b.nSeq] : 0;
+    if (h10x_grow((void **)&table, &capTable, (size_t)(t.nSeq + b.nSeq), sizeof(Rec)) || h10x_grow((void **)&offsets, &capOff, (size_t)(t.nSeq + b.nSeq + 1), 8) ||
+        h10x_grow((void **)&coverOff, &capCoverOff, (size_t)(t.nSeq + b.nSeq + 1), 8) || h10x_grow((void **)&quad, &capQuad, (size_t)rows, 16) ||
+        h10x_grow((void **)&cover, &capCover, (size_t)(t.boundaries + bounds), 4)) goto no_memory;
+    offsets[0] = 0; coverOff[0] = 0;
+    for (uint64_t i = 0; i < rows; ++i) {
+      quad[4 * i] = b.block[i]; quad[4 * i + 1] = b.first[i]; quad[4 * i + 2] = b.last[i]; quad[4 * i + 3] = b.hits[i];
+      const uint32_t span = b.last[i] - b.first[i];
+      t.sumSpan += span;
+      if (span > t.maxSpan) t.maxSpan = span;
+      if (b.hits[i] > t.maxHits) t.maxHits = b.hits[i];
+    }
+    if ((rc = h10x_out_write(&o, quad, 16, (size_t)rows))) break;
+    if (bounds) memcpy(cover + t.boundaries, b.cover, (size_t)bounds * 4);
+    for (uint32_t q = 0; q < b.nSeq; ++q) {
+      const uint64_t at = t.nSeq + q, len = b.seqStart[q + 1] - b.seqStart[q], c0 = b.coverOff[q], c1 = b.coverOff[q + 1];
+      const h10x_seq_span_figures *g = b.fig + q;
+      const char *name = b.names + b.nameOff[q];
+      if (h10x_names_add(&names, name)) goto no_memory;
+      uint32_t weak = 0;
+      for (uint64_t j = c0; j < c1; ++j) weak += b.cover[j] < hd->minCover;
+      Rec rec = {len, g->moshes, g->found, g->inRange, weak};
+      table[at] = rec;
+      offsets[at + 1] = t.extents + b.rowOff[q + 1]; coverOff[at + 1] = t.boundaries + c1;
+      if (verbose) {
+        fprintf(verbose, "SEQ_SPANS  %s len %llu moshes %u found %u inRange %u extents %llu boundaries %llu weak %u\n", name, (unsigned long long)len, g->moshes,
+                g->found, g->inRange, (unsigned long long)(b.rowOff[q + 1] - b.rowOff[q]), (unsigned long long)(c1 - c0), weak);
+        for (uint64_t j = c0; j < c1;) {                                /* the maximal runs of boundaries below minCover; boundary j - c0 + 1 stands at (j - c0 + 1) W */
+          if (b.cover[j] >= hd->minCover) { ++j; continue; }
+          uint64_t e = j; uint32_t low = b.cover[j];
+          while (e + 1 < c1 && b.cover[e + 1] < hd->minCover) { ++e; if (b.cover[e] < low) low = b.cover[e]; }
+          fprintf(verbose, "SEQ_WEAK  %s from %llu to %llu min %u\n", name, (unsigned long long)((j - c0 + 1) * hd->window),
+                  (unsigned long long)((e - c0 + 1) * hd->window), low);
+          j = e + 1;
+        }
+      }
+      t.bases += len; t.moshes += g->moshes; t.found += g->found; t.inRange += g->inRange; t.weak += weak;
+    }
+    t.nSeq += b.nSeq; t.extents += rows; t.boundaries += bounds; t.hits += b.gathered;
+  }
+  if (!rc) {
+    Head h = head_start(head, "10XE"); put_u32(&h, hd->nBlocks); put_u32(&h, hd->minShare); put_u32(&h, hd->maxGap); put_u32(&h, hd->window); put_u32(&h, hd->minCover);
+    put_u32(&h, 0); put_u64(&h, t.nSeq); put_u64(&h, t.extents); put_u64(&h, t.boundaries); put_u64(&h, names.nBytes);
+    rc = h10x_out_write(&o, table, sizeof(Rec), (size_t)t.nSeq) || h10x_out_write(&o, offsets ? offsets : &zero64, 8, (size_t)t.nSeq + 1) ||
+         h10x_out_write(&o, coverOff ? coverOff : &zero64, 8, (size_t)t.nSeq + 1) || h10x_out_write(&o, cover, 4, (size_t)t.boundaries) ||
+         h10x_out_write(&o, names.off ? names.off : &zero64, 8, (size_t)t.nSeq + 1) || h10x_out_write(&o, names.bytes, 1, (size_t)names.nBytes) ||
+         h10x_out_rewrite(&o, head, h.n) || h10x_out_commit(&o) ? -1 : 0;
+  }
+  if (!rc && totals) *totals = t;
+  goto done;
+no_memory:
+  rc = put_err(err, errlen, "out of host memory for the table of %llu sequences", t.nSeq);
+done:
+  h10x_out_abort(&o); free(table); free(offsets); free(coverOff); free(quad); free(cover); h10x_names_free(&names);
+  return rc;
+}
+
 /* ---- .sl: --seqLinks. The tables come ready in the head; the links come back in pieces. ---- */
 int h10x_host_write_seq_links(const char *path, const h10x_seq_links_head *h, h10x_seq_links_piece_fn piece, void *user, uint64_t pieceLinks, FILE *verbose,
                               h10x_seq_links_totals *totals, char *err, int errlen) {

@@ -1844,6 +1844,55 @@ int h10x_session_seqBlocks(h10x_session *s, int minShare, const char *seqPath, c
   return 0;
 }
 
+/* ---- --seqSpans <minShare> <maxGap> <window> <minCover> <seqfile> <out.ss>: each block's extents on every sequence of a file and the spanning coverage
+   (h10x_seq_spans_run). The slabs come from the sequence file through the device; h10x_host_write_seq_spans (files_host.c) asks for one after the other,
+   writes the file and finds the weak boundaries. ---- */
+typedef struct {
+  h10x_session *s; h10x_seqreader *r; int minShare, maxGap, window; uint64_t slab;
+  h10x_seq_span_figures *fig; uint64_t *rowOff, *coverOff; uint32_t *col[4], *cover; size_t capSeq, capOff, capCoverOff, capCol[4], capCover;
+} SsFeed;
+
+static int ss_next_from_file(void *user, h10x_seq_spans_slab *b) {
+  SsFeed *z = (SsFeed *)user; h10x_session *s = z->s;
+  const uint8_t *codes; const uint64_t *seqStart, *nameOff; const char *names; uint32_t nSeq = 0;
+  const int got = h10x_seq_next_named(z->r, z->slab, &codes, &seqStart, &nSeq, &names, &nameOff);
+  if (got < 0) return fail(s, "%s", h10x_seq_error(z->r));
+  if (!got) return 0;
+  if (h10x_grow((void **)&z->fig, &z->capSeq, (size_t)nSeq + 1, sizeof *z->fig) || h10x_grow((void **)&z->rowOff, &z->capOff, (size_t)nSeq + 1, 8) ||
+      h10x_grow((void **)&z->coverOff, &z->capCoverOff, (size_t)nSeq + 1, 8)) return fail(s, "out of host memory for %u sequences", nSeq);
+  h10x_seq_spans_info info;
+  if (h10x_seq_spans_run(s->ctx, z->minShare, z->maxGap, z->window, codes, seqStart, nSeq, z->fig, &info)) return fail_ctx(s);
+  for (int k = 0; k < 4; ++k)
+    if (h10x_grow((void **)&z->col[k], &z->capCol[k], (size_t)info.extents + 1, 4)) return fail(s, "out of host memory for %llu extents", (unsigned long long)info.extents);
+  if (h10x_grow((void **)&z->cover, &z->capCover, (size_t)info.boundaries + 1, 4)) return fail(s, "out of host memory for %llu boundaries", (unsigned long long)info.boundaries);
+  if (h10x_seq_spans_get(s->ctx, z->rowOff, z->col[0], z->col[1], z->col[2], z->col[3], info.extents) ||
+      h10x_seq_spans_cover_get(s->ctx, z->coverOff, z->cover, info.boundaries)) return fail_ctx(s);
+  b->nSeq = nSeq; b->seqStart = seqStart; b->fig = z->fig; b->rowOff = z->rowOff; b->block = z->col[0]; b->first = z->col[1]; b->last = z->col[2]; b->hits = z->col[3];
+  b->coverOff = z->coverOff; b->cover = z->cover; b->gathered = info.hits; b->names = names; b->nameOff = nameOff;
+  return 1;
+}
+
+int h10x_session_seqSpans(h10x_session *s, int minShare, int maxGap, int window, int minCover, const char *seqPath, const char *outPath, FILE *out, int verbose) {
+  if (whole_state(s, "seqSpans", NO_RANGE)) return -1;
+  h10x_seq_spans_info info;
+  if (h10x_seq_spans_run(s->ctx, minShare, maxGap, window, 0, 0, 0, 0, &info)) return fail_ctx(s);   /* the refusals, before any file is touched */
+  if (minCover < 0) return fail(s, "!! seqSpans minCover %d must be >= 0", minCover);
+  char msg[512] = ""; int fatal = 0;
+  SsFeed z; memset(&z, 0, sizeof z);
+  z.s = s; z.minShare = minShare; z.maxGap = maxGap; z.window = window; { const int v = h10x_session_get(s, "seq_slab"); z.slab = v > 0 ? (uint64_t)v : 0; }
+  if (!(z.r = h10x_seq_open(seqPath, msg, (int)sizeof msg, &fatal))) return fail(s, "%s%sfailed to open sequence file %s", msg, msg[0] ? "\n" : "", seqPath);
+  const h10x_seq_spans_head head = {info.nBlocks, (uint32_t)minShare, (uint32_t)maxGap, (uint32_t)window, (uint32_t)minCover};
+  h10x_seq_spans_totals t;
+  const int w = h10x_host_write_seq_spans(outPath, &head, ss_next_from_file, &z, verbose ? out : 0, &t, s->err, (int)sizeof s->err);
+  h10x_seq_close(z.r); free(z.fig); free(z.rowOff); free(z.coverOff); free(z.cover); for (int k = 0; k < 4; ++k) free(z.col[k]);
+  if (w) return -1;                                                                       /* (-2: the callback has set the session's text) */
+  if (out) fprintf(out, "  seq spans at minShare %d, maxGap %d, window %d: %llu sequences, %llu bases, %llu moshes, %llu found, %llu in range, %llu hits, %llu extents, "
+                   "mean span %.1f, max span %u, %llu boundaries, %llu below minCover %d\n", minShare, maxGap, window, (unsigned long long)t.nSeq,
+                   (unsigned long long)t.bases, (unsigned long long)t.moshes, (unsigned long long)t.found, (unsigned long long)t.inRange, (unsigned long long)t.hits,
+                   (unsigned long long)t.extents, (double)t.sumSpan / (double)t.extents, t.maxSpan, (unsigned long long)t.boundaries, (unsigned long long)t.weak, minCover);
+  return 0;
+}
+
 /* ---- --seqLinks <minShare> <minBlocks> <endLen> <maxEnds> <seqfile> <out.sl>: which sequence ends share molecules (h10x_row_links_*). The sequence file is
    read in slabs; the host cuts each sequence's two ends, a slab of ends runs through h10x_seq_blocks_run and its rows go from device memory to the
    accumulator (h10x_row_links_add_kept): the rows never reach the host, which keeps per sequence its length, the two row counts and the name. The links

@@ -220,6 +220,38 @@ int  h10x_host_write_seq_links(const char *path, const h10x_seq_links_head *head
                                h10x_seq_links_totals *totals, char *err, int errlen);
 int  h10x_session_seqLinks(h10x_session *s, int minShare, int minBlocks, int endLen, int maxEnds, const char *seqPath, const char *outPath, FILE *out, int verbose);
 
+/* --seqSpans <minShare> <maxGap> <window> <minCover> <seqfile> <out.ss> (addition; include/h10x.h "sequence spans"): per sequence of a FASTA / FASTQ file the
+   extents {block, first, last, hits} of the blocks on it (hits of one block no more than maxGap apart, maxGap 0: one extent per block; kept at minShare hits)
+   and, for window >= 1, the number of kept extents that span each boundary j * window: after --clusterSplit and a new range, the molecules over each position.
+   A boundary with cover < minCover is weak. The file is read in slabs of "seq_slab" bases as --seqBlocks reads it; each slab runs through h10x_seq_spans_run
+   and its extents are appended to the file at once; the host keeps per sequence a record, the name and the coverage (4 bytes per boundary) until the end.
+   The file is written as <out.ss>.part and renamed when whole. Little-endian: "10XE", u32 version 1, u32 nBlocks, u32 minShare, u32 maxGap, u32 window,
+   u32 minCover, u32 0, u64 nSeq, u64 extents, u64 boundaries, u64 nameBytes (filled in at the end); extents records {u32 block, u32 first, u32 last, u32 hits};
+   nSeq records {u64 len, u32 moshes, u32 found, u32 inRange, u32 weak}; nSeq + 1 u64 offsets; nSeq + 1 u64 cover offsets; boundaries u32 cover; nSeq + 1 u64
+   name offsets; the names, NUL-terminated, cut at the first blank or tab.
+   out gets one line of counts; verbose != 0 adds per sequence "SEQ_SPANS  <name> len l moshes m found f inRange q extents e boundaries B weak w" and, per
+   maximal run of consecutive weak boundaries, "SEQ_WEAK  <name> from <first position> to <last position> min <lowest cover>". Soft errors as --seqBlocks: no
+   state or no range ("!! you must set hashDepthRange before seqSpans"), "!! seqSpans minShare 0 must be >= 1", and maxGap, window and minCover "must be >= 0";
+   a sequence file or an output path that cannot be opened fails without "!!". In every failure no file is written and no .part is left behind.
+   h10x_host_write_seq_spans is the writer alone, fed by a callback as h10x_host_write_seq_blocks is, with the same return values. */
+typedef struct { uint32_t nBlocks, minShare, maxGap, window, minCover; } h10x_seq_spans_head;
+typedef struct {
+  uint32_t nSeq;
+  const uint64_t *seqStart;                  /* nSeq + 1: sequence s has seqStart[s + 1] - seqStart[s] bases */
+  const h10x_seq_span_figures *fig;          /* nSeq */
+  const uint64_t *rowOff;                    /* nSeq + 1: the slab's extents, from 0 */
+  const uint32_t *block, *first, *last, *hits;   /* rowOff[nSeq] each */
+  const uint64_t *coverOff;                  /* nSeq + 1: the slab's boundaries, from 0 */
+  const uint32_t *cover;                     /* coverOff[nSeq] */
+  uint64_t gathered;                         /* the hits the slab's run gathered (the summary line) */
+  const char *names; const uint64_t *nameOff;   /* sequence s is called names + nameOff[s] */
+} h10x_seq_spans_slab;
+typedef struct { uint64_t nSeq, bases, moshes, found, inRange, hits, extents, sumSpan, boundaries, weak; uint32_t maxSpan, maxHits; } h10x_seq_spans_totals;
+typedef int (*h10x_seq_spans_slab_fn)(void *user, h10x_seq_spans_slab *slab);
+int  h10x_host_write_seq_spans(const char *path, const h10x_seq_spans_head *head, h10x_seq_spans_slab_fn next, void *user, FILE *verbose,
+                               h10x_seq_spans_totals *totals, char *err, int errlen);
+int  h10x_session_seqSpans(h10x_session *s, int minShare, int maxGap, int window, int minCover, const char *seqPath, const char *outPath, FILE *out, int verbose);
+
 /* --writeMosh <bits> <copy1min> <copy2min> <copyMmin> <out.mosh> (addition; include/h10x.h "the state as a mosh set"): the in-range hashes of the state as
    an MSHSTv1 file that moshutils, moshasm and moshmap read: the state's hash values, depths saturated to 16 bits, copy classes from depth by the three
    thresholds of moshutils -s and, where a --hashCopies result is kept, corrected by linkage. bits = the table bits of the set, 0 = the state's -B. The file

@@ -159,6 +159,7 @@ static void usage(void) {
   fprintf(stderr, "   --writeMosh <bits> <copy1min> <copy2min> <copyMmin> <mosh output>: the hashes in the depth range as a mosh set for moshutils / moshasm / moshmap: depths cut to 16 bits, copy classes from depth, corrected by a kept --hashCopies result (bits 0: as -B; needs hashDepthRange)\n");
   fprintf(stderr, "   --seqBlocks <minShare> <sequence file> <sb output>: for every sequence of a fasta/fastq file (gzip or plain) the blocks that stand at least minShare times in the barcode lists of its hashes in the depth range, with the counts (needs hashDepthRange; after --clusterSplit: the molecules; --verbose: a SEQ_BLOCKS line per sequence)\n");
   fprintf(stderr, "   --seqLinks <minShare> <minBlocks> <endLen> <maxEnds> <sequence file> <sl output>: which ends of the sequences (the first and last endLen bases; 0: whole sequences) share at least minBlocks blocks of their --seqBlocks rows at minShare, leaving out blocks that stand in more than maxEnds ends (0: none) (needs hashDepthRange; after --clusterSplit: the molecules; --verbose: a SEQ_LINKS line per link)\n");
+  fprintf(stderr, "   --seqSpans <minShare> <maxGap> <window> <minCover> <sequence file> <ss output>: for every sequence the extents (block, first, last, hits) of the blocks on it, the hits of a block cut where they lie more than maxGap apart (0: never) and kept at minShare hits, and per multiple of window (0: none) the number of extents that span it (needs hashDepthRange; after --clusterSplit: the molecules; --verbose: a SEQ_SPANS line per sequence and a SEQ_WEAK line per run of boundaries spanned by fewer than minCover)\n");
   fprintf(stderr, "   --cribBuild <genome1.fa> <genome2.fa>: match to genomic hashes\n");
   fprintf(stderr, "   --clusterReport <codeMin> <codeMax>\n");
   fprintf(stderr, "   --cribSummary\n");
@@ -320,6 +321,9 @@ static void cmd_seqBlocks(char **a) { one_gpu("--seqBlocks"); nb_done(h10x_sessi
 /* which sequence ends share blocks: the rows are those of --seqBlocks, so one GPU */
 static void cmd_seqLinks(char **a) { one_gpu("--seqLinks"); nb_done(h10x_session_seqLinks(team.s[0], atoi(a[0]), atoi(a[1]), atoi(a[2]), atoi(a[3]), a[4], a[5], outFile, isVerbose)); }
 
+/* where on the sequences the blocks lie: the lists of every barcode again, so one GPU */
+static void cmd_seqSpans(char **a) { one_gpu("--seqSpans"); nb_done(h10x_session_seqSpans(team.s[0], atoi(a[0]), atoi(a[1]), atoi(a[2]), atoi(a[3]), a[4], a[5], outFile, isVerbose)); }
+
 typedef struct { const char *name; int nArgs; void (*run)(char **args); const char *param; } Command;
 static const Command commands[] = {
   {"-k", 1, 0, "k"}, {"-w", 1, 0, "w"}, {"-r", 1, 0, "r"}, {"-B", 1, 0, "B"}, {"-N", 1, 0, "N"}, {"-c", 1, 0, "c"},
@@ -332,6 +336,7 @@ static const Command commands[] = {
   {"--codeCensus", 3, cmd_codeCensus, 0}, {"--fixFQB", 3, cmd_fixFQB, 0}, {"--fixFQBThresh", 3, cmd_fixFQBThresh, 0},
   {"--moleculeMap", 1, cmd_moleculeMap, 0}, {"--splitFQB", 2, cmd_splitFQB, 0}, {"--shareGraph", 2, cmd_shareGraph, 0}, {"--shareComponents", 2, cmd_shareComponents, 0},
   {"--hashCopies", 2, cmd_hashCopies, 0}, {"--writeMosh", 5, cmd_writeMosh, 0}, {"--seqBlocks", 3, cmd_seqBlocks, 0}, {"--seqLinks", 6, cmd_seqLinks, 0},
+  {"--seqSpans", 6, cmd_seqSpans, 0},
   {"--sortFQB", 2, cmd_sortFQB, 0}, {"--cribBuild", 2, cmd_cribBuild, 0}, {"--clusterReport", 2, cmd_clusterReport, 0},
   {"--cribSummary", 0, cmd_cribSummary, 0}, {"--hashStats", 0, cmd_hashStats, 0}, {"--codeStats", 0, cmd_codeStats, 0},
   {"--hashInfo", 3, cmd_hashInfo, 0}, {"--hashExplore", 1, cmd_hashExplore, 0}, {"--doubleShared", 2, cmd_doubleShared, 0},

@@ -694,6 +694,48 @@ int  h10x_row_links_get_device(h10x_ctx *ctx, uint64_t *dev_offsets, uint32_t *d
 /* links [first, first + count) of the kept result to host memory (either array may be NULL): a writer takes the links in pieces */
 int  h10x_row_links_get_range(h10x_ctx *ctx, uint64_t first, uint64_t count, uint32_t *other, uint32_t *shared);
 
+/* ---- sequence spans (csrc/stage_r.hip): where on a sequence each block lies, and how many blocks span each position (--seqSpans) ----
+   There is no reference function: hash10x.c knows no sequences beside the crib's. State and hasher as "from a sequence to its blocks" above;
+   after --clusterSplit and a new range the blocks are the molecules, and an extent is a molecule's footprint on a contig.
+   Hits. The mosh occurrences of sequence s (length L) are those of layer 1 above; occurrence i has position p_i, the 0-based start of its
+   k-mer in s. It counts when its hash is found at an index x_i with hashWithinRange[x_i]. Every counting occurrence gives one hit (d, p_i)
+   per entry d of the barcode list of x_i, repeats as the list holds them; no block is left out; a hash that occurs twice in s gives hits at
+   both positions.
+   Extents. Per (s, d) the hits sorted by position: a new extent starts at the first hit and wherever p[j + 1] - p[j] > maxGap (maxGap = 0
+   never splits; equal positions never split). An extent is {block, first, last, hits}, kept when hits >= minShare. Row s = its kept extents
+   ascending by (block, first); the result is in CSR form, offsets[nSeq + 1] and four uint32 columns.
+   Spanning coverage (window W >= 1). The boundaries of s are b_j = j W, j = 1 .. (L - 1) / W (none for L <= W); cover_s[j - 1] = the number
+   of kept extents of s with first < b_j <= last: coverOffsets[nSeq + 1] and cover[]. W = 0: no coverage, every offset 0.
+   h10x_seq_spans_run: per slab of "seq_slab" bases (whole sequences; a longer one goes alone) a scan, one look-up per occurrence, one unit
+     per counting occurrence placed by a scan, a gather of keys block << bits | ordinal in the slab, a sort, head flags where block or sequence
+     change or the gap is exceeded, a scan that numbers the extents, a second one that keeps those of minShare hits, a stable sort on the
+     sequence and a +1 / -1 difference array over the boundaries with an inclusive scan. Batches are cut by hits against "neighbour_budget", a
+     sequence above it runs alone in windows of block index; a batch of 2^32 - 1 hits or more is refused. figures[nSeq] may be NULL:
+     inRange = the counting occurrences (not distinct hashes), extents = the row's length. info: sequences, bases, moshes, found, inRange,
+     hits = the keys gathered, extentsAll / extents = before / after the threshold, maxHits, maxSpan and sumSpan over last - first of the kept
+     extents, boundaries, batches, windows, nBlocks.
+   h10x_seq_spans_get copies out offsets[nSeq + 1] and the first min(cap, extents) entries of each column, h10x_seq_spans_get_range rows
+     [firstRow, firstRow + count) of the columns, h10x_seq_spans_cover_get coverOffsets[nSeq + 1] and the first min(cap, boundaries) counts; any
+     pointer may be NULL.
+   The result depends on none of "seq_slab", "neighbour_budget", the order in which anything lands, or the run: two calls give the same bytes.
+   The kept result is released by the next run (also a refused one), h10x_depth_range, h10x_cluster_split, a new state and h10x_destroy; get
+   without it fails. Refused without a state, on a sharded context, before --hashDepthRange ("!! you must set hashDepthRange before seqSpans"),
+   for "!! seqSpans minShare 0 must be >= 1", "!! seqSpans maxGap -1 must be >= 0", "!! seqSpans window -1 must be >= 0", and without the
+   hasher's seed as h10x_seq_hashes is. */
+typedef struct {
+  uint64_t len;
+  uint32_t moshes, found, inRange, extents;
+} h10x_seq_span_figures;
+typedef struct {
+  uint64_t sequences, bases, moshes, found, inRange, hits, extentsAll, extents, sumSpan, boundaries;
+  uint32_t maxHits, maxSpan, batches, windows, nBlocks, reserved;
+} h10x_seq_spans_info;
+int  h10x_seq_spans_run(h10x_ctx *ctx, int64_t minShare, int64_t maxGap, int64_t window, const uint8_t *codes, const uint64_t *seqStart, uint32_t nSeq,
+                        h10x_seq_span_figures *figures, h10x_seq_spans_info *info);
+int  h10x_seq_spans_get(h10x_ctx *ctx, uint64_t *offsets, uint32_t *block, uint32_t *first, uint32_t *last, uint32_t *hits, uint64_t cap);
+int  h10x_seq_spans_get_range(h10x_ctx *ctx, uint64_t firstRow, uint64_t count, uint32_t *block, uint32_t *first, uint32_t *last, uint32_t *hits);
+int  h10x_seq_spans_cover_get(h10x_ctx *ctx, uint64_t *coverOffsets, uint32_t *cover, uint64_t cap);
+
 /* ---- readsets (csrc/stage_h.hip): the Readset object of the reference's moshasm (moshasm.c) over a mosh set ----
    Long reads kept as their mosh hits only: per read the set indices hit, in position order (top bit = the forward hash was strictly
    the smaller, seqhash.c:67), and the 16-bit distance of each hit to the one before it. Read 0 is the reference's burned entry. The
