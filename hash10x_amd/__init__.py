@@ -271,8 +271,16 @@ def load_native():
     hip.h10x_seq_spans_get_range.argtypes = [vp, cu64, cu64, vp, vp, vp, vp]
     hip.h10x_seq_spans_cover_get.argtypes = [vp, vp, vp, cu64]
     host.h10x_session_seqSpans.argtypes = [vp, ci, ci, ci, ci, cs, cs, vp, ci]
+    # sequence spectrum (csrc/stage_s.hip)
+    hip.h10x_seq_spectrum_begin.argtypes = [vp, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64]
+    hip.h10x_seq_spectrum_add.argtypes = [vp, vp, vp, ctypes.c_uint32, vp, vp]
+    hip.h10x_seq_spectrum_windows_get.argtypes = [vp, vp, vp, cu64]
+    hip.h10x_seq_spectrum_finish.argtypes = [vp, vp, vp, vp]
+    hip.h10x_seq_spectrum_copies_get.argtypes = [vp, cu64, cu64, vp]
+    host.h10x_session_seqSpectrum.argtypes = [vp, ci, ci, ci, ci, cs, cs, vp, ci]
+    host.h10x_host_qv.restype = ctypes.c_double; host.h10x_host_qv.argtypes = [cu64, cu64, ci]
     # mosh sets (csrc/stage_g.hip, host/mosh_host.c)
-    pvp, ci32, cu32 = ctypes.POINTER(vp), ctypes.c_int32, ctypes.c_uint32
+    pvp, ci32, cu32 =ctypes.POINTER(vp), ctypes.c_int32, ctypes.c_uint32
     hip.h10x_factors_from_seed.restype = None; hip.h10x_factors_from_seed.argtypes = [ci32, ctypes.POINTER(cu64), ctypes.POINTER(cu64)]
     hip.h10x_mosh_create.argtypes = [pvp, ci32, ci32, ci32, ci32, ci, cs, ci]
     hip.h10x_mosh_load.argtypes = [pvp, ci32, ci32, ci32, cu64, cu64, vp, vp, vp, vp, cu32, ci, cs, ci]
@@ -1260,6 +1268,45 @@ class Hash10x:
         self._with_file(out, lambda f: self._host.h10x_session_seqSpans(self._s, int(min_share), int(max_gap), int(window), int(min_cover), os.fsencode(seqfile),
                                                                         os.fsencode(path), f, 1 if verbose else 0))
 
+    # ---- sequence spectrum (h10x_seq_spectrum_*, csrc/stage_s.hip) ----
+    def seq_spectrum(self, seqs, copy1min, copy2min, copyMmin, window=0):
+        """The moshes of the sequences against the read depths of the state (no depth range needed). Every mosh occurrence is absent from the
+        state or of depth class 0 (hashDepth < copy1min), 1 (< copy2min), 2 (< copyMmin) or M. Returns (figures, win_offsets, windows, spectrum,
+        totals): figures per sequence (len, moshes, absent, n0, n1, n2, nM, depthSum), windows the same fields without len per window of
+        `window` bases (window 0: none) in CSR form by win_offsets uint64[n + 1], spectrum uint64[1024, 8] counting the state's hashes by
+        (min(depth, 1023), min(copies, 7)) with copies = the times the sequences hold the hash, totals uint64[2, 4] = the hashes of each class
+        and those of them held at least once. The sums of the run are kept in self.seq_spectrum_info, copies[] for seq_copies()."""
+        ctx = self._seq_ctx("seqSpectrum")
+        codes, start = self._flatten_seqs(seqs)
+        n = len(start) - 1
+        self._chk_ctx(self._hip.h10x_seq_spectrum_begin(ctx, int(copy1min), int(copy2min), int(copyMmin), int(window)))
+        fig = np.zeros(max(n, 1), dtype=_SEQ_SPECTRUM_FIGURES); z = np.zeros(1, dtype=_SEQ_SPECTRUM_INFO)
+        self._chk_ctx(self._hip.h10x_seq_spectrum_add(ctx, codes.ctypes.data, start.ctypes.data, n, fig.ctypes.data, z.ctypes.data))
+        m = int(z["windows"][0])
+        off = np.zeros(n + 1, dtype=np.uint64); win = np.zeros(max(m, 1), dtype=_SEQ_SPECTRUM_WINDOW)
+        self._chk_ctx(self._hip.h10x_seq_spectrum_windows_get(ctx, off.ctypes.data, win.ctypes.data, m))
+        spectrum = np.zeros((SPECTRUM_DEPTH_BINS, SPECTRUM_COPY_BINS), dtype=np.uint64); totals = np.zeros((2, 4), dtype=np.uint64)
+        self._chk_ctx(self._hip.h10x_seq_spectrum_finish(ctx, spectrum.ctypes.data, totals.ctypes.data, z.ctypes.data))
+        self.seq_spectrum_info = {k: int(z[k][0]) for k in _SEQ_SPECTRUM_INFO.names}
+        return fig[:n].copy(), off, win[:m].copy(), spectrum, totals
+
+    def seq_copies(self, first=0, count=None):
+        """copies[first .. first + count) of the kept sequence spectrum as uint32 (count None: to the end): the times the sequences of the run
+        hold each hash of the state; copies[0] is 0."""
+        ctx = self._seq_ctx("seqSpectrum")
+        if count is None:
+            count = max(self.sizes()["hashNumber"] - int(first), 0)
+        out = np.zeros(max(int(count), 1), dtype=np.uint32)
+        self._chk_ctx(self._hip.h10x_seq_spectrum_copies_get(ctx, int(first), int(count), out.ctypes.data))
+        return out[:int(count)]
+
+    def write_seq_spectrum(self, copy1min, copy2min, copyMmin, window, seqfile, path, out=None, verbose=False):
+        """--seqSpectrum <copy1min> <copy2min> <copyMmin> <window> <seqfile> <path>: the spectrum of every sequence of a FASTA / FASTQ file (gzip
+        or plain) against the state, read slab by slab, written as a .sp file (read_seq_spectrum reads it); one line of counts with QV and
+        completeness, and with verbose one SEQ_SPECTRUM line per sequence, are appended to the file `out`."""
+        self._with_file(out, lambda f: self._host.h10x_session_seqSpectrum(self._s, int(copy1min), int(copy2min), int(copyMmin), int(window), os.fsencode(seqfile),
+                                                                           os.fsencode(path), f, 1 if verbose else 0))
+
     # ---- row links (h10x_row_links_*, csrc/stage_q.hip) ----
     def _row_links_ctx(self, cmd):
         """the session's context (it comes with the first state; the row layer itself reads none)"""
@@ -1344,6 +1391,11 @@ _ROW_LINKS_INFO = np.dtype([("lists", "<u8"), ("rowEntries", "<u8"), ("blocksUse
 _SEQ_SPAN_FIGURES = np.dtype([("len", "<u8"), ("moshes", "<u4"), ("found", "<u4"), ("inRange", "<u4"), ("extents", "<u4")])
 _SEQ_SPANS_INFO = np.dtype([(k, "<u8") for k in ("sequences", "bases", "moshes", "found", "inRange", "hits", "extentsAll", "extents", "sumSpan", "boundaries")] +
                            [(k, "<u4") for k in ("maxHits", "maxSpan", "batches", "windows", "nBlocks", "reserved")])
+SPECTRUM_DEPTH_BINS, SPECTRUM_COPY_BINS = 1024, 8            # H10X_SPECTRUM_DEPTH_BINS, H10X_SPECTRUM_COPY_BINS (include/h10x.h)
+_SEQ_SPECTRUM_WINDOW = np.dtype([(k, "<u4") for k in ("moshes", "absent", "n0", "n1", "n2", "nM")] + [("depthSum", "<u8")])
+_SEQ_SPECTRUM_FIGURES = np.dtype([("len", "<u8")] + [(k, "<u4") for k in ("moshes", "absent", "n0", "n1", "n2", "nM")] + [("depthSum", "<u8")])
+_SEQ_SPECTRUM_INFO = np.dtype([(k, "<u8") for k in ("sequences", "bases", "moshes", "absent", "n0", "n1", "n2", "nM", "depthSum", "windows")] +
+                              [("hashNumber", "<u4"), ("maxCopies", "<u4")])
 _SEQ_CODE = np.zeros(256, dtype=np.uint8)
 for _i, _c in enumerate("ACGT"):
     _SEQ_CODE[ord(_c)] = _SEQ_CODE[ord(_c.lower())] = _i
@@ -1487,6 +1539,99 @@ def read_seq_spans(path):
     info = {"version": version, "nBlocks": n_blocks, "minShare": min_share, "maxGap": max_gap, "window": window, "minCover": min_cover, "nSeq": n_seq,
             "extents": extents, "boundaries": boundaries, "nameBytes": name_bytes}
     return info, off, blk, first, last, hits, coff, cover, table, names
+
+
+def seq_qv(moshes, unsupported, k):
+    """QV of --seqSpectrum: -10 log10(1 - (1 - unsupported / moshes) ** (1 / k)); inf when nothing is unsupported, 0 without moshes"""
+    if not moshes:
+        return 0.0
+    if not unsupported:
+        return float("inf")
+    return -10.0 * float(np.log10(1.0 - (1.0 - unsupported / moshes) ** (1.0 / k))) + 0.0
+
+
+def read_seq_spectrum(path):
+    """A --seqSpectrum file (magic "10XP", u32 version 1, u32 hashNumber, u32 copy1min, u32 copy2min, u32 copyMmin, u32 window, u32 depthBins,
+    u32 copyBins, u32 0, u64 nSeq, u64 windows, u64 nameBytes; windows records {u32 moshes, absent, n0, n1, n2, nM; u64 depthSum}; nSeq records
+    {u64 len; the same seven}; nSeq + 1 u64 window offsets; 8 u64 totals; depthBins x copyBins u64 spectrum; hashNumber bytes min(copies, 255);
+    nSeq + 1 u64 name offsets; the names, NUL-terminated; little-endian; needs no device): (info, figures, win_offsets, windows, spectrum,
+    totals uint64[2, 4], copies uint8[hashNumber], names). Raises Hash10xError for a file that is not one or does not hold together: magic,
+    version, the bins, the file's length, the thresholds' order, the window offsets against ceil(len / window), moshes = absent + the four
+    classes in every record, the windows of a sequence summing to its figures, the spectrum and the totals summing to hashNumber - 1, the
+    totals against the spectrum's rows (thresholds up to 1023), present <= total, the spectrum's columns and the present hashes against the
+    copies bytes, the bytes' sum against the found occurrences, the names."""
+    with open(path, "rb") as f:
+        data = f.read()
+    if len(data) < 64 or data[:4] != b"10XP":
+        raise Hash10xError("%s: not a seq spectrum file (magic 10XP)" % path)
+    version, hash_number, c1, c2, cm, window, dbins, cbins, zero = (int(v) for v in np.frombuffer(data, dtype="<u4", count=9, offset=4))
+    n_seq, n_win, name_bytes = (int(v) for v in np.frombuffer(data, dtype="<u8", count=3, offset=40))
+    if version != 1:
+        raise Hash10xError("%s: seq spectrum version %d, this reader knows 1" % (path, version))
+    if (dbins, cbins) != (SPECTRUM_DEPTH_BINS, SPECTRUM_COPY_BINS):
+        raise Hash10xError("%s: a spectrum of %d x %d bins, this reader knows %d x %d" % (path, dbins, cbins, SPECTRUM_DEPTH_BINS, SPECTRUM_COPY_BINS))
+    need = 64 + 32 * n_win + 40 * n_seq + 16 * (n_seq + 1) + 64 + 8 * dbins * cbins + hash_number + name_bytes
+    if len(data) != need:
+        raise Hash10xError("%s: %d bytes, %d sequences, %d windows, %d hashes and %d name bytes need %d" % (path, len(data), n_seq, n_win, hash_number, name_bytes, need))
+    if zero:
+        raise Hash10xError("%s: the reserved word of the header is not 0" % path)
+    if not c1 <= c2 <= cm:
+        raise Hash10xError("%s: the thresholds %d %d %d do not ascend" % (path, c1, c2, cm))
+    at = 64
+    win = np.frombuffer(data, dtype=_SEQ_SPECTRUM_WINDOW, count=n_win, offset=at).copy(); at += 32 * n_win
+    fig = np.frombuffer(data, dtype=_SEQ_SPECTRUM_FIGURES, count=n_seq, offset=at).copy(); at += 40 * n_seq
+    off = np.frombuffer(data, dtype="<u8", count=n_seq + 1, offset=at).copy(); at += 8 * (n_seq + 1)
+    totals = np.frombuffer(data, dtype="<u8", count=8, offset=at).copy().reshape(2, 4); at += 64
+    spectrum = np.frombuffer(data, dtype="<u8", count=dbins * cbins, offset=at).copy().reshape(dbins, cbins); at += 8 * dbins * cbins
+    copies = np.frombuffer(data, dtype=np.uint8, count=hash_number, offset=at).copy(); at += hash_number
+    name_off = np.frombuffer(data, dtype="<u8", count=n_seq + 1, offset=at).copy(); at += 8 * (n_seq + 1)
+    blob = data[at:]
+    lens = fig["len"].astype(np.int64)
+    exp = np.zeros(n_seq + 1, dtype=np.uint64)
+    if window:
+        exp[1:] = np.cumsum((lens + window - 1) // window)
+    if not np.array_equal(off, exp) or int(off[-1]) != n_win:
+        raise Hash10xError("%s: the window offsets are not those of the lengths at window %d" % (path, window))
+    fields = ("moshes", "absent", "n0", "n1", "n2", "nM", "depthSum")
+    for rec, what in ((win, "window"), (fig, "sequence")):
+        if np.any(rec["moshes"].astype(np.int64) != sum(rec[k].astype(np.int64) for k in fields[1:6])):
+            raise Hash10xError("%s: a %s's moshes are not its absent and its four classes" % (path, what))
+    if window and n_seq:
+        live = off[:-1] < off[1:]
+        for k in fields:
+            sums = np.zeros(n_seq, dtype=np.uint64)
+            if n_win:
+                sums[live] = np.add.reduceat(win[k].astype(np.uint64), off[:-1][live].astype(np.int64))
+            if not np.array_equal(sums, fig[k].astype(np.uint64)):
+                raise Hash10xError("%s: the windows of a sequence do not sum to its %s" % (path, k))
+    hashes = max(hash_number - 1, 0)
+    if int(spectrum.sum()) != hashes or int(totals[0].sum()) != hashes:
+        raise Hash10xError("%s: the spectrum and the totals do not sum to the %d hashes" % (path, hashes))
+    if np.any(totals[1] > totals[0]):
+        raise Hash10xError("%s: more hashes of a class are present than there are" % path)
+    if cm <= SPECTRUM_DEPTH_BINS - 1:
+        edges = (0, c1, c2, cm, SPECTRUM_DEPTH_BINS)
+        for q in range(4):
+            rows = spectrum[edges[q]:edges[q + 1]]
+            if int(rows.sum()) != int(totals[0, q]) or int(rows[:, 1:].sum()) != int(totals[1, q]):
+                raise Hash10xError("%s: the totals of class %d are not those of the spectrum's rows" % (path, q))
+    if hash_number and copies[0]:
+        raise Hash10xError("%s: byte 0 of the copies is not 0" % path)
+    held = np.bincount(np.minimum(copies[1:], cbins - 1), minlength=cbins) if hash_number > 1 else np.zeros(cbins, dtype=np.int64)
+    if not np.array_equal(held.astype(np.uint64), spectrum.sum(axis=0)) or int((copies[1:] > 0).sum()) != int(totals[1].sum()):
+        raise Hash10xError("%s: the copies are not those of the spectrum's columns" % path)
+    found = int(fig["moshes"].astype(np.int64).sum() - fig["absent"].astype(np.int64).sum())
+    held_sum = int(copies.astype(np.int64).sum())
+    if held_sum > found or (held_sum < found and not np.any(copies == 255)):
+        raise Hash10xError("%s: the copies sum to %d and the sequences found %d" % (path, held_sum, found))
+    if name_off[0] != 0 or int(name_off[-1]) != name_bytes or np.any(name_off[1:] <= name_off[:-1]):
+        raise Hash10xError("%s: the name offsets do not ascend from 0 to the %d name bytes" % (path, name_bytes))
+    if any(blob[int(e) - 1] != 0 for e in name_off[1:]):
+        raise Hash10xError("%s: a name does not end in NUL" % path)
+    names = [blob[int(a):int(b) - 1].decode(errors="replace") for a, b in zip(name_off[:-1], name_off[1:])]
+    info = {"version": version, "hashNumber": hash_number, "copy1min": c1, "copy2min": c2, "copyMmin": cm, "window": window, "depthBins": dbins,
+            "copyBins": cbins, "nSeq": n_seq, "windows": n_win, "nameBytes": name_bytes}
+    return info, fig, off, win, spectrum, totals, copies, names
 
 
 _SL_RECORD = np.dtype([("len", "<u8"), ("headRows", "<u4"), ("tailRows", "<u4")])

@@ -294,6 +294,11 @@ struct Ctx {
   // sequence spans (stage_r.hip). The kept extents of the last h10x_seq_spans_run in row order, four columns of ssExtents entries, and the spanning coverage,
   // ssBoundaries entries; the offsets of both per sequence on the host. Kept until the next run, a new depth range, --clusterSplit or a new state
   DevBuf<u32> ssBlock, ssFirst, ssLast, ssHits, ssCover; std::vector<u64> ssHostOff, ssHostCoverOff; u64 ssExtents = 0, ssBoundaries = 0; u32 ssSeqs = 0; bool haveSeqSpans = false;
+  // sequence spectrum (stage_s.hip). spCopies[hashNumber]: the found occurrences per hash since h10x_seq_spectrum_begin; spWin: the window records of the last add,
+  // spWindows of them, their offsets per sequence on the host; spRun: the sums of the run. Open between begin and finish; kept until the next begin, --clusterSplit
+  // or a new state
+  DevBuf<u32> spCopies; DevBuf<h10x_seq_spectrum_window> spWin; std::vector<u64> spHostWinOff; u64 spWindows = 0, spThr[3] = {0, 0, 0}; u32 spSeqs = 0, spW = 0;
+  h10x_seq_spectrum_info spRun = {}; bool haveSpectrum = false, spOpen = false;
   int64_t optSeqSlab = 0;     // bases per device batch of the sequence layer (0 = the mosh sets' default, 2^26); results do not depend on it
   // the -r value prm.factor1 was drawn from (option "seqhash_seed"): a mosh set made from the state carries the hasher's second multiplier too (stage_o.hip)
   int32_t seed = 0; bool haveSeed = false;
@@ -588,6 +593,14 @@ int stageP_seqBlocks(Ctx *c, int64_t minShare, const u8 *codes, const u64 *seqSt
 int stageP_get(Ctx *c, u64 *offsets, u32 *block, u32 *count, u64 cap, int toDevice);
 void stageP_release(Ctx *c);
 int sp_check(Ctx *c, const char *cmd, int64_t minShare, bool hasher);   // the refusals of the sequence commands: ce_check, no range and, with hasher, the seed's
+int sp_check_hasher(Ctx *c, const char *cmd);                           // the seed's two checks alone
+// sequence spectrum (stage_s.hip): the classes of every mosh occurrence by the depth of its hash, the copies of every hash in the sequences, depth x copies
+int stageS_begin(Ctx *c, int64_t copy1min, int64_t copy2min, int64_t copyMmin, int64_t window);
+int stageS_add(Ctx *c, const u8 *codes, const u64 *seqStart, u32 nSeq, h10x_seq_spectrum_figures *fig, h10x_seq_spectrum_info *info);
+int stageS_windowsGet(Ctx *c, u64 *winOffsets, h10x_seq_spectrum_window *records, u64 cap);
+int stageS_finish(Ctx *c, u64 *spectrum, u64 *totals, h10x_seq_spectrum_info *info);
+int stageS_copiesGet(Ctx *c, u64 first, u64 count, u32 *out);
+void stageS_release(Ctx *c);
 // sequence spans (stage_r.hip): each block's extents on a sequence and the number of extents that span each window boundary
 int stageR_run(Ctx *c, int64_t minShare, int64_t maxGap, int64_t window, const u8 *codes, const u64 *seqStart, u32 nSeq, h10x_seq_span_figures *fig, h10x_seq_spans_info *info);
 int stageR_get(Ctx *c, u64 *offsets, u32 *block, u32 *first, u32 *last, u32 *hits, u64 cap);

@@ -240,7 +240,7 @@ const char *h10x_last_error(const h10x_ctx *h) { return h ? h->c.err.c_str() : "
 
 static void reset_state(Ctx &c) {
   c.haveState = false; c.haveRange = false; c.haveGood = false; c.goodFiguresPending = false; c.rangeMin = c.rangeMax = 0; c.depthBound = 0xFFFFFFFFu; c.rangeHiMax = 0;
-  release_share_results(&c); stageP_release(&c); stageQ_release(&c); stageR_release(&c);
+  release_share_results(&c); stageP_release(&c); stageQ_release(&c); stageR_release(&c); stageS_release(&c);
   c.within.release(); c.goodPos.release(); c.nGood.release(); c.goodEntries.release(); c.goodRow.release();
   // the tables of the state being replaced go back to the block cache NOW, not when their successors are swapped in: the second --readFQB of a
   // context then finds every block of the first one parked and allocates nothing (kept until the swap, rows[] and clusHash had no twin in the
@@ -428,7 +428,7 @@ int h10x_cluster_split(h10x_ctx *h) {
   if (!h) return -1;
   H10X_TRY(enter(h->c));
   release_share_results(&h->c);   // (and of the blocks this call renumbers)
-  stageP_release(&h->c); stageQ_release(&h->c); stageR_release(&h->c);
+  stageP_release(&h->c); stageQ_release(&h->c); stageR_release(&h->c); stageS_release(&h->c);
   return stageC_split(&h->c);
 }
 
@@ -764,6 +764,23 @@ int h10x_seq_spans_get_range(h10x_ctx *h, uint64_t firstRow, uint64_t count, uin
 }
 int h10x_seq_spans_cover_get(h10x_ctx *h, uint64_t *coverOffsets, uint32_t *cover, uint64_t cap) {
   if (!h) return -1; H10X_TRY(enter(h->c)); return stageR_coverGet(&h->c, (u64 *)coverOffsets, cover, cap);
+}
+
+// ---- sequence spectrum (stage_s.hip) ----
+int h10x_seq_spectrum_begin(h10x_ctx *h, int64_t copy1min, int64_t copy2min, int64_t copyMmin, int64_t window) {
+  if (!h) return -1; H10X_TRY(enter(h->c)); return stageS_begin(&h->c, copy1min, copy2min, copyMmin, window);
+}
+int h10x_seq_spectrum_add(h10x_ctx *h, const uint8_t *codes, const uint64_t *seqStart, uint32_t nSeq, h10x_seq_spectrum_figures *figures, h10x_seq_spectrum_info *info) {
+  if (!h || !info) return -1; H10X_TRY(enter(h->c)); return stageS_add(&h->c, codes, (const u64 *)seqStart, nSeq, figures, info);
+}
+int h10x_seq_spectrum_windows_get(h10x_ctx *h, uint64_t *winOffsets, h10x_seq_spectrum_window *records, uint64_t cap) {
+  if (!h) return -1; H10X_TRY(enter(h->c)); return stageS_windowsGet(&h->c, (u64 *)winOffsets, records, cap);
+}
+int h10x_seq_spectrum_finish(h10x_ctx *h, uint64_t *spectrum, uint64_t *totals, h10x_seq_spectrum_info *info) {
+  if (!h || !info) return -1; H10X_TRY(enter(h->c)); return stageS_finish(&h->c, (u64 *)spectrum, (u64 *)totals, info);
+}
+int h10x_seq_spectrum_copies_get(h10x_ctx *h, uint64_t first, uint64_t count, uint32_t *out) {
+  if (!h) return -1; H10X_TRY(enter(h->c)); return stageS_copiesGet(&h->c, first, count, out);
 }
 
 int h10x_timing_enable(h10x_ctx *h, int on) { if (!h) return -1; h->c.timing = on != 0; return 0; }

@@ -128,7 +128,11 @@ __global__ __launch_bounds__(256) void sp_gather_kernel(u32 nq, const u64 *__res
 int sp_check(Ctx *c, const char *cmd, int64_t minShare, bool hasher) {
   H10X_TRY(ce_check(c, cmd, minShare));
   if (!c->haveRange) return c->fail("!! you must set hashDepthRange before %s", cmd);
-  if (!hasher) return 0;
+  return hasher ? sp_check_hasher(c, cmd) : 0;
+}
+
+// the two checks of the hasher alone, for a command that needs no range (stage_s.hip)
+int sp_check_hasher(Ctx *c, const char *cmd) {
   if (!c->haveSeed) return c->fail("%s: the context does not know the seed of its hasher: set option seqhash_seed to the -r value", cmd);
   u64 f1 = 0, f2 = 0; h10x_factors_from_seed(c->seed, (uint64_t *)&f1, (uint64_t *)&f2);
   if (f1 != c->prm.factor1) return c->fail("%s: option seqhash_seed %d does not give the context's hash multiplier", cmd, c->seed);

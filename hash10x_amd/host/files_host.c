@@ -3,6 +3,7 @@
    without a GPU (the *_asan_driver.c programs). Every writer goes through OutFile: an output appears under its name only when it is whole. */
 #define _GNU_SOURCE
 #include "files_host.h"
+#include <math.h>
 #include <stdlib.h>
 #include <string.h>
 
@@ -327,6 +328,81 @@ no_memory:
   rc = put_err(err, errlen, "out of host memory for the table of %llu sequences", t.nSeq);
 done:
   h10x_out_abort(&o); free(table); free(offsets); free(coverOff); free(quad); free(cover); h10x_names_free(&names);
+  return rc;
+}
+
+/* ---- .sp: --seqSpectrum. As .ss: the window records of each slab go to the file as they come; the per-sequence records, the window offsets and the names are
+   kept on the host; the totals, the spectrum and the copies are asked for when the last slab is in, the copies in pieces of 2^22 hashes. ---- */
+double h10x_host_qv(uint64_t moshes, uint64_t unsupported, int k) {
+  if (!moshes) return 0.0;
+  if (!unsupported) return INFINITY;
+  return -10.0 * log10(1.0 - pow(1.0 - (double)unsupported / (double)moshes, 1.0 / (double)k)) + 0.0;   /* (+ 0.0: every mosh unsupported gives 0.00, not -0.00) */
+}
+
+int h10x_host_write_seq_spectrum(const char *path, const h10x_seq_spectrum_head *hd, h10x_seq_spectrum_slab_fn next, h10x_seq_spectrum_end_fn end,
+                                 h10x_seq_spectrum_copies_fn copies, void *user, FILE *verbose, h10x_seq_spectrum_totals *totals, char *err, int errlen) {
+  enum { PIECE = 1 << 22, BINS = H10X_SPECTRUM_DEPTH_BINS * H10X_SPECTRUM_COPY_BINS };
+  h10x_seq_spectrum_totals t; memset(&t, 0, sizeof t);
+  h10x_seq_spectrum_figures *table = 0; uint64_t *offsets = 0, *spectrum = 0; uint32_t *piece = 0; unsigned char *bytes = 0; NameTable names; memset(&names, 0, sizeof names);
+  size_t capTable = 0, capOff = 0;
+  OutFile o; unsigned char head[64]; memset(head, 0, sizeof head);
+  if (h10x_out_open(&o, path, err, errlen)) return -1;
+  int rc = h10x_out_write(&o, head, 1, sizeof head);
+  while (!rc) {
+    h10x_seq_spectrum_slab b; memset(&b, 0, sizeof b);
+    const int got = next(user, &b);
+    if (got < 0) { rc = -2; break; }                                  /* the callback's own error stands */
+    if (!got) break;
+    const uint64_t wins = b.nSeq ? b.winOff[b.nSeq] : 0;
+    if (h10x_grow((void **)&table, &capTable, (size_t)(t.nSeq + b.nSeq), sizeof *table) || h10x_grow((void **)&offsets, &capOff, (size_t)(t.nSeq + b.nSeq + 1), 8)) goto no_memory;
+    offsets[0] = 0;
+    if ((rc = h10x_out_write(&o, b.win, sizeof *b.win, (size_t)wins))) break;
+    for (uint32_t q = 0; q < b.nSeq; ++q) {
+      const uint64_t at = t.nSeq + q;
+      const h10x_seq_spectrum_figures *g = b.fig + q;
+      const char *name = b.names + b.nameOff[q];
+      if (h10x_names_add(&names, name)) goto no_memory;
+      table[at] = *g;
+      offsets[at + 1] = t.windows + b.winOff[q + 1];
+      const uint32_t found = g->moshes - g->absent;
+      if (verbose)
+        fprintf(verbose, "SEQ_SPECTRUM  %s len %llu moshes %u absent %u copy0 %u copy1 %u copy2 %u copyM %u meanDepth %.1f QV %.2f\n", name, (unsigned long long)g->len,
+                g->moshes, g->absent, g->n0, g->n1, g->n2, g->nM, found ? (double)g->depthSum / (double)found : 0.0,
+                h10x_host_qv(g->moshes, (uint64_t)g->absent + g->n0, hd->k));
+      t.bases += g->len; t.moshes += g->moshes; t.absent += g->absent; t.n0 += g->n0; t.n1 += g->n1; t.n2 += g->n2; t.nM += g->nM; t.depthSum += g->depthSum;
+    }
+    t.nSeq += b.nSeq; t.windows += wins;
+  }
+  if (!rc) {
+    const size_t pieceLen = hd->hashNumber < PIECE ? (hd->hashNumber ? hd->hashNumber : 1) : PIECE;
+    spectrum = (uint64_t *)calloc((size_t)BINS + 8, 8); piece = (uint32_t *)malloc(pieceLen * 4); bytes = (unsigned char *)malloc(pieceLen);
+    if (!spectrum || !piece || !bytes) goto no_memory;
+    if (end(user, spectrum + 8, spectrum) < 0) rc = -2;               /* (the totals stand before the spectrum in the file) */
+  }
+  if (!rc) {
+    for (int q = 0; q < 4; ++q) { t.total[q] = spectrum[q]; t.present[q] = spectrum[4 + q]; }
+    rc = h10x_out_write(&o, table, sizeof *table, (size_t)t.nSeq) || h10x_out_write(&o, offsets ? offsets : &zero64, 8, (size_t)t.nSeq + 1) ||
+         h10x_out_write(&o, spectrum, 8, (size_t)BINS + 8) ? -1 : 0;
+  }
+  for (uint64_t at = 0; !rc && at < hd->hashNumber; at += PIECE) {
+    const uint64_t m = hd->hashNumber - at < PIECE ? hd->hashNumber - at : PIECE;
+    if (copies(user, at, m, piece) < 0) { rc = -2; break; }
+    for (uint64_t i = 0; i < m; ++i) bytes[i] = (unsigned char)(piece[i] < 255 ? piece[i] : 255);
+    if (!at) bytes[0] = 0;                                            /* (index 0 is no hash) */
+    rc = h10x_out_write(&o, bytes, 1, (size_t)m);
+  }
+  if (!rc) {
+    Head h = head_start(head, "10XP"); put_u32(&h, hd->hashNumber); put_u32(&h, hd->copy1min); put_u32(&h, hd->copy2min); put_u32(&h, hd->copyMmin); put_u32(&h, hd->window);
+    put_u32(&h, H10X_SPECTRUM_DEPTH_BINS); put_u32(&h, H10X_SPECTRUM_COPY_BINS); put_u32(&h, 0); put_u64(&h, t.nSeq); put_u64(&h, t.windows); put_u64(&h, names.nBytes);
+    rc = h10x_out_write(&o, names.off ? names.off : &zero64, 8, (size_t)t.nSeq + 1) || h10x_out_write(&o, names.bytes, 1, (size_t)names.nBytes) ||
+         h10x_out_rewrite(&o, head, h.n) || h10x_out_commit(&o) ? -1 : 0;
+  }
+  if (!rc && totals) *totals = t;
+  goto done;
+no_memory:
+  rc = put_err(err, errlen, "out of host memory for the table of %llu sequences", t.nSeq);
+done:
+  h10x_out_abort(&o); free(table); free(offsets); free(spectrum); free(piece); free(bytes); h10x_names_free(&names);
   return rc;
 }
 

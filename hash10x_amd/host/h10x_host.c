@@ -1893,6 +1893,60 @@ int h10x_session_seqSpans(h10x_session *s, int minShare, int maxGap, int window,
   return 0;
 }
 
+/* ---- --seqSpectrum <copy1min> <copy2min> <copyMmin> <window> <seqfile> <out.sp>: the moshes of every sequence of a file against the read depths, the copies of
+   every hash in the sequences and depth x copies (h10x_seq_spectrum_*). The slabs come from the sequence file through the device; h10x_host_write_seq_spectrum
+   (files_host.c) asks for one after the other, then for the spectrum and the copies, and writes the file. ---- */
+typedef struct { h10x_session *s; h10x_seqreader *r; uint64_t slab; h10x_seq_spectrum_figures *fig; uint64_t *winOff; h10x_seq_spectrum_window *win; size_t capSeq, capOff, capWin; } SpFeed;
+
+static int sp_next_from_file(void *user, h10x_seq_spectrum_slab *b) {
+  SpFeed *z = (SpFeed *)user; h10x_session *s = z->s;
+  const uint8_t *codes; const uint64_t *seqStart, *nameOff; const char *names; uint32_t nSeq = 0;
+  const int got = h10x_seq_next_named(z->r, z->slab, &codes, &seqStart, &nSeq, &names, &nameOff);
+  if (got < 0) return fail(s, "%s", h10x_seq_error(z->r));
+  if (!got) return 0;
+  if (h10x_grow((void **)&z->fig, &z->capSeq, (size_t)nSeq + 1, sizeof *z->fig) || h10x_grow((void **)&z->winOff, &z->capOff, (size_t)nSeq + 1, 8))
+    return fail(s, "out of host memory for %u sequences", nSeq);
+  h10x_seq_spectrum_info info;
+  if (h10x_seq_spectrum_add(s->ctx, codes, seqStart, nSeq, z->fig, &info)) return fail_ctx(s);
+  if (h10x_grow((void **)&z->win, &z->capWin, (size_t)info.windows + 1, sizeof *z->win)) return fail(s, "out of host memory for %llu windows", (unsigned long long)info.windows);
+  if (h10x_seq_spectrum_windows_get(s->ctx, z->winOff, z->win, info.windows)) return fail_ctx(s);
+  b->nSeq = nSeq; b->fig = z->fig; b->winOff = z->winOff; b->win = z->win; b->names = names; b->nameOff = nameOff;
+  return 1;
+}
+static int sp_end(void *user, uint64_t *spectrum, uint64_t *totals) {
+  SpFeed *z = (SpFeed *)user; h10x_seq_spectrum_info info;
+  return h10x_seq_spectrum_finish(z->s->ctx, spectrum, totals, &info) ? fail_ctx(z->s) : 0;
+}
+static int sp_copies(void *user, uint64_t first, uint64_t count, uint32_t *out) {
+  SpFeed *z = (SpFeed *)user;
+  return h10x_seq_spectrum_copies_get(z->s->ctx, first, count, out) ? fail_ctx(z->s) : 0;
+}
+
+int h10x_session_seqSpectrum(h10x_session *s, int copy1min, int copy2min, int copyMmin, int window, const char *seqPath, const char *outPath, FILE *out, int verbose) {
+  if (!s->ctx) return fail(s, "!! seqSpectrum: no hash state loaded: use readFQB or readHash first");
+  if (whole_state(s, "seqSpectrum", NO_STATE)) return -1;
+  if (h10x_seq_spectrum_begin(s->ctx, copy1min, copy2min, copyMmin, window)) return fail_ctx(s);   /* the refusals, before any file is touched */
+  h10x_sizes zs; if (h10x_get_sizes(s->ctx, &zs)) return fail_ctx(s);
+  char msg[512] = ""; int fatal = 0;
+  SpFeed z; memset(&z, 0, sizeof z);
+  z.s = s; { const int v = h10x_session_get(s, "seq_slab"); z.slab = v > 0 ? (uint64_t)v : 0; }
+  if (!(z.r = h10x_seq_open(seqPath, msg, (int)sizeof msg, &fatal))) return fail(s, "%s%sfailed to open sequence file %s", msg, msg[0] ? "\n" : "", seqPath);
+  const int k = h10x_session_get(s, "k");
+  const h10x_seq_spectrum_head head = {zs.hashNumber, (uint32_t)copy1min, (uint32_t)copy2min, (uint32_t)copyMmin, (uint32_t)window, k};
+  h10x_seq_spectrum_totals t;
+  const int w = h10x_host_write_seq_spectrum(outPath, &head, sp_next_from_file, sp_end, sp_copies, &z, verbose ? out : 0, &t, s->err, (int)sizeof s->err);
+  h10x_seq_close(z.r); free(z.fig); free(z.winOff); free(z.win);
+  if (w) return -1;                                                                       /* (-2: the callback has set the session's text) */
+  const uint64_t have = t.present[1] + t.present[2] + t.present[3], all = t.total[1] + t.total[2] + t.total[3];
+  if (out) fprintf(out, "  seq spectrum at copy1min %d copy2min %d copyMmin %d, window %d: %llu sequences, %llu bases, %llu moshes, %llu absent, copy0 %llu copy1 %llu copy2 %llu "
+                   "copyM %llu, QV %.2f, present %llu of %llu copy1, %llu of %llu copy2, %llu of %llu copyM, completeness %.2f %%\n", copy1min, copy2min, copyMmin, window,
+                   (unsigned long long)t.nSeq, (unsigned long long)t.bases, (unsigned long long)t.moshes, (unsigned long long)t.absent, (unsigned long long)t.n0,
+                   (unsigned long long)t.n1, (unsigned long long)t.n2, (unsigned long long)t.nM, h10x_host_qv(t.moshes, t.absent + t.n0, k),
+                   (unsigned long long)t.present[1], (unsigned long long)t.total[1], (unsigned long long)t.present[2], (unsigned long long)t.total[2],
+                   (unsigned long long)t.present[3], (unsigned long long)t.total[3], all ? 100.0 * (double)have / (double)all : 0.0);
+  return 0;
+}
+
 /* ---- --seqLinks <minShare> <minBlocks> <endLen> <maxEnds> <seqfile> <out.sl>: which sequence ends share molecules (h10x_row_links_*). The sequence file is
    read in slabs; the host cuts each sequence's two ends, a slab of ends runs through h10x_seq_blocks_run and its rows go from device memory to the
    accumulator (h10x_row_links_add_kept): the rows never reach the host, which keeps per sequence its length, the two row counts and the name. The links

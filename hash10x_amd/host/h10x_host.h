@@ -252,6 +252,42 @@ int  h10x_host_write_seq_spans(const char *path, const h10x_seq_spans_head *head
                                h10x_seq_spans_totals *totals, char *err, int errlen);
 int  h10x_session_seqSpans(h10x_session *s, int minShare, int maxGap, int window, int minCover, const char *seqPath, const char *outPath, FILE *out, int verbose);
 
+/* --seqSpectrum <copy1min> <copy2min> <copyMmin> <window> <seqfile> <out.sp> (addition; include/h10x.h "sequence spectrum"): the moshes of every sequence of a
+   FASTA / FASTQ file classed by the read depth of their hash (absent; copy0 below copy1min; copy1; copy2; copyM from copyMmin), per sequence and, for window >= 1,
+   per window of that many bases; how many times the sequences hold every hash of the state; and the depth x copies matrix with the hashes of each class that the
+   sequences hold at all. It needs no depth range. The file is read in slabs of "seq_slab" bases as --seqBlocks reads it; each slab runs through
+   h10x_seq_spectrum_add and its window records are appended to the file at once; the host keeps per sequence the 40-byte record, one offset and the name.
+   The file is written as <out.sp>.part and renamed when whole. Little-endian: "10XP", u32 version 1, u32 hashNumber, u32 copy1min, u32 copy2min, u32 copyMmin,
+   u32 window, u32 depthBins (1024), u32 copyBins (8), u32 0, u64 nSeq, u64 windows, u64 nameBytes (filled in at the end); windows records {u32 moshes, absent,
+   n0, n1, n2, nM; u64 depthSum}; nSeq records {u64 len; u32 moshes, absent, n0, n1, n2, nM; u64 depthSum}; nSeq + 1 u64 window offsets; 8 u64 totals
+   (total[4], present[4]); depthBins x copyBins u64 spectrum, row = depth bin; hashNumber bytes min(copies[x], 255), byte 0 = 0; nSeq + 1 u64 name offsets; the
+   names, NUL-terminated, cut at the first blank or tab.
+   out gets "  seq spectrum at copy1min a copy2min b copyMmin c, window W: n sequences, b bases, m moshes, x absent, copy0 p copy1 q copy2 r copyM s, QV v,
+   present h1 of t1 copy1, h2 of t2 copy2, hM of tM copyM, completeness z %"; QV = h10x_host_qv(moshes, absent + copy0, k), completeness = 100 (h1 + h2 + hM) /
+   (t1 + t2 + tM), 0 without such hashes. verbose != 0 adds per sequence "SEQ_SPECTRUM  <name> len l moshes m absent x copy0 p copy1 q copy2 r copyM s meanDepth
+   %.1f QV %.2f" (meanDepth over the found occurrences, 0.0 without any). Soft errors: no state ("!! seqSpectrum: no hash state loaded ..."), "!! seqSpectrum
+   needs 0 <= copy1min <= copy2min <= copyMmin", "!! seqSpectrum window -1 must be >= 0"; a sequence file or an output path that cannot be opened fails without
+   "!!". In every failure no file is written and no .part is left behind.
+   h10x_host_write_seq_spectrum is the writer alone: `next` gives one slab per call (1, 0 at the end, < 0 on its own error), `end` the totals and the spectrum
+   once the last slab is in, `copies` copies[first .. first + count) in pieces of at most 2^22; 0, -1 with err set, or -2 when a callback failed (err untouched).
+   h10x_host_qv: -10 log10(1 - (1 - unsupported / moshes)^(1 / k)); infinity when nothing is unsupported, 0 without moshes. */
+typedef struct { uint32_t hashNumber, copy1min, copy2min, copyMmin, window; int k; } h10x_seq_spectrum_head;
+typedef struct {
+  uint32_t nSeq;
+  const h10x_seq_spectrum_figures *fig;      /* nSeq */
+  const uint64_t *winOff;                    /* nSeq + 1: the slab's windows, from 0 */
+  const h10x_seq_spectrum_window *win;       /* winOff[nSeq] */
+  const char *names; const uint64_t *nameOff;   /* sequence s is called names + nameOff[s] */
+} h10x_seq_spectrum_slab;
+typedef struct { uint64_t nSeq, bases, moshes, absent, n0, n1, n2, nM, depthSum, windows, total[4], present[4]; } h10x_seq_spectrum_totals;
+typedef int (*h10x_seq_spectrum_slab_fn)(void *user, h10x_seq_spectrum_slab *slab);
+typedef int (*h10x_seq_spectrum_end_fn)(void *user, uint64_t *spectrum, uint64_t *totals);
+typedef int (*h10x_seq_spectrum_copies_fn)(void *user, uint64_t first, uint64_t count, uint32_t *out);
+double h10x_host_qv(uint64_t moshes, uint64_t unsupported, int k);
+int  h10x_host_write_seq_spectrum(const char *path, const h10x_seq_spectrum_head *head, h10x_seq_spectrum_slab_fn next, h10x_seq_spectrum_end_fn end,
+                                  h10x_seq_spectrum_copies_fn copies, void *user, FILE *verbose, h10x_seq_spectrum_totals *totals, char *err, int errlen);
+int  h10x_session_seqSpectrum(h10x_session *s, int copy1min, int copy2min, int copyMmin, int window, const char *seqPath, const char *outPath, FILE *out, int verbose);
+
 /* --writeMosh <bits> <copy1min> <copy2min> <copyMmin> <out.mosh> (addition; include/h10x.h "the state as a mosh set"): the in-range hashes of the state as
    an MSHSTv1 file that moshutils, moshasm and moshmap read: the state's hash values, depths saturated to 16 bits, copy classes from depth by the three
    thresholds of moshutils -s and, where a --hashCopies result is kept, corrected by linkage. bits = the table bits of the set, 0 = the state's -B. The file

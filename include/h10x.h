@@ -736,6 +736,56 @@ int  h10x_seq_spans_get(h10x_ctx *ctx, uint64_t *offsets, uint32_t *block, uint3
 int  h10x_seq_spans_get_range(h10x_ctx *ctx, uint64_t firstRow, uint64_t count, uint32_t *block, uint32_t *first, uint32_t *last, uint32_t *hits);
 int  h10x_seq_spans_cover_get(h10x_ctx *ctx, uint64_t *coverOffsets, uint32_t *cover, uint64_t cap);
 
+/* ---- sequence spectrum (csrc/stage_s.hip): the hashes of sequences against the read depths of the state (--seqSpectrum) ----
+   There is no reference function. State: a loaded, unsharded context, with or without a depth range, before or after --cluster /
+   --clusterSplit: only hashDepth[] and the probe table are read. Hasher as "from a sequence to its blocks" above.
+   Parameters 0 <= copy1min <= copy2min <= copyMmin and window W >= 0.
+   Occurrences. Occurrence i of the moshes of sequence s (length L) has position p_i, the 0-based start of its k-mer, and the index x_i of
+   its hash in the state (0: absent; a table entry >= hashNumber counts as absent). Class of an occurrence: absent, or by d = hashDepth[x_i]
+   class 0 (d < copy1min), 1 (d < copy2min), 2 (d < copyMmin), else M.
+   Per sequence {len; moshes, absent, n0, n1, n2, nM; depthSum = the sum of d over its found occurrences}.
+   Windows (W >= 1): window j = 0 .. ceil(L / W) - 1 of s holds the occurrences with p_i / W == j; one record {moshes, absent, n0, n1, n2,
+   nM, depthSum} each, in CSR form over the sequences: winOffsets[nSeq + 1]. L = 0 and W = 0 give no windows. The windows of a sequence sum
+   field by field to its figures.
+   Copies: copies[x], x = 1 .. hashNumber - 1, = the found occurrences with x_i = x over ALL sequences between one begin and its finish.
+   Spectrum: S[min(hashDepth[x], H10X_SPECTRUM_DEPTH_BINS - 1)][min(copies[x], H10X_SPECTRUM_COPY_BINS - 1)] counts the hashes x >= 1;
+   totals[q] = the hashes of class q = 0, 1, 2, M by the same thresholds, totals[4 + q] = those of them with copies >= 1.
+   h10x_seq_spectrum_begin releases a kept result, checks (a refused begin keeps nothing) and zeroes copies[] on the device.
+   h10x_seq_spectrum_add: per slab of "seq_slab" bases (whole sequences; a longer one goes alone) the scan, one look-up per occurrence
+     (which also adds 1 to copies[x]), a sort by ordinal, and one wave per window and per sequence that finds its occurrences by two searches
+     and folds them; no atomic in the tally. figures[nSeq] may be NULL; info = the sums of THIS call. The windows of this call stay on the
+     device until the next add; h10x_seq_spectrum_windows_get copies out winOffsets[nSeq + 1] (from 0) and the first min(cap, windows) records.
+   h10x_seq_spectrum_finish bins every hash into spectrum[DEPTH_BINS * COPY_BINS] (row = depth bin) and totals[8], closes the run (a later
+     add needs a new begin) and fills info with the sums of the whole run and the largest copies[] value. Any pointer but info may be NULL.
+   h10x_seq_spectrum_copies_get: copies[first .. first + count) as uint32, from begin until the kept result is released.
+   The result depends on none of "seq_slab", how the sequences are split over add calls, the order in which anything lands, or the run.
+   The kept result is released by the next begin (also a refused one), h10x_cluster_split, a new state and h10x_destroy; a new depth range
+   keeps it. It neither releases nor changes the kept results of the other sequence and share commands. Refused without a state, on a sharded
+   context, for "!! seqSpectrum needs 0 <= copy1min <= copy2min <= copyMmin", "!! seqSpectrum window -1 must be >= 0", without the hasher's
+   seed as h10x_seq_hashes is; add / windows_get / finish / copies_get without a begin fail, and so does a sequence of more than 2^32 - 1
+   windows. */
+#define H10X_SPECTRUM_DEPTH_BINS 1024
+#define H10X_SPECTRUM_COPY_BINS 8
+typedef struct {
+  uint64_t len;
+  uint32_t moshes, absent, n0, n1, n2, nM;
+  uint64_t depthSum;
+} h10x_seq_spectrum_figures;                  /* 40 bytes */
+typedef struct {
+  uint32_t moshes, absent, n0, n1, n2, nM;
+  uint64_t depthSum;
+} h10x_seq_spectrum_window;                   /* 32 bytes */
+typedef struct {
+  uint64_t sequences, bases, moshes, absent, n0, n1, n2, nM, depthSum, windows;
+  uint32_t hashNumber, maxCopies;
+} h10x_seq_spectrum_info;
+int  h10x_seq_spectrum_begin(h10x_ctx *ctx, int64_t copy1min, int64_t copy2min, int64_t copyMmin, int64_t window);
+int  h10x_seq_spectrum_add(h10x_ctx *ctx, const uint8_t *codes, const uint64_t *seqStart, uint32_t nSeq, h10x_seq_spectrum_figures *figures,
+                           h10x_seq_spectrum_info *info);
+int  h10x_seq_spectrum_windows_get(h10x_ctx *ctx, uint64_t *winOffsets, h10x_seq_spectrum_window *records, uint64_t cap);
+int  h10x_seq_spectrum_finish(h10x_ctx *ctx, uint64_t *spectrum, uint64_t *totals, h10x_seq_spectrum_info *info);
+int  h10x_seq_spectrum_copies_get(h10x_ctx *ctx, uint64_t first, uint64_t count, uint32_t *out);
+
 /* ---- readsets (csrc/stage_h.hip): the Readset object of the reference's moshasm (moshasm.c) over a mosh set ----
    Long reads kept as their mosh hits only: per read the set indices hit, in position order (top bit = the forward hash was strictly
    the smaller, seqhash.c:67), and the 16-bit distance of each hit to the one before it. Read 0 is the reference's burned entry. The
